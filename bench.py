@@ -22,10 +22,19 @@ N > 1 ranks (one process per GPU):
       collective per step; the ranks' running means are combined by one RCCL
       reduce after the timed steps (validated, not timed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (driver launch for N > 1)
 
-Rank 0 prints one JSON line (contract in the task statement), with
+A plain run does what the headline figure needs and no more: it prepares the scene, lets the
+renderer probe its policies, runs the W warmup steps, times the K steps and prints the line
+(``roofline``, ``cpu_baseline`` and ``quality`` null). --dump-outputs DIR then writes what the
+timed steps computed, rank 0's running means after the last timed step, as DIR/accum.npy (f32,
+H x W x 4; BASIC: DIR/basic_image.npy, f64) -- a fixed seeded sample of its pixels, with their
+indices in DIR/accum_pixels.npy, when the image is larger than 64 MB. The scene, the camera and
+the frame sequence are the same from run to run, so two builds compare output for output.
+
+Everything else runs only with --full (each leg with its own --no-* switch, as before): rank 0
+then prints the line with
 ``roofline`` for a frame: the work the hardware counters measured for every kernel
 of a frame (camera-ray pass, frame kernel, tile reorder, running-mean update: VALU
 wave-instructions, DRAM-side bytes; committed under profiles/<round>/counters.json by
@@ -74,6 +83,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="c2")
     ap.add_argument("--builder", default=None, help="override the config's BVH builder")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the running means they computed as DIR/accum.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: the reference algorithm's fetch bytes and the roofline, "
+                         "per_call, reset_ms_per_frame, the serial-frames run, cpu_baseline, the PSNR check, "
+                         "and for N > 1 gather_every_frame (each with its own --no-* switch)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-psnr", action="store_true", help="skip the spp-matched PSNR check")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
@@ -109,6 +124,10 @@ def dist_env():
 
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not args.full:  # a plain run: the timed steps only
+        args.no_cpu_baseline = args.no_psnr = args.no_reset = args.no_serial = args.no_per_call = True
     rank, world, local = dist_env()
     if world != args.gpus and world > 1:
         raise SystemExit(f"WORLD_SIZE={world} but --gpus {args.gpus}")
@@ -149,14 +168,16 @@ def main():
 
     # ---- algorithmic bytes per ray of the reference algorithm, counted on the GPU by the
     # instrumented kernel variant (no culling, closest-hit shadows: exactly pass1.fsh's fetches)
-    rc = Renderer(cfg.width, cfg.height, cfg.integrator, max_bounce=cfg.max_bounce, device=local,
-                  flags=FLAG_COUNT_FETCHES, **split)
-    rc.upload_scene(tris, nodes)
-    rc.upload_env(hdr)
-    rc.render_frame(eye, rot, 0)
-    cs = rc.stats()
-    rc.close()
-    bytes_per_ray = (48 * cs.node_fetch + 72 * cs.tri_fetch + 72 * cs.mat_fetch + 12 * cs.tex_fetch) / max(cs.rays, 1)
+    bytes_per_ray = None
+    if args.full:
+        rc = Renderer(cfg.width, cfg.height, cfg.integrator, max_bounce=cfg.max_bounce, device=local,
+                      flags=FLAG_COUNT_FETCHES, **split)
+        rc.upload_scene(tris, nodes)
+        rc.upload_env(hdr)
+        rc.render_frame(eye, rot, 0)
+        cs = rc.stats()
+        rc.close()
+        bytes_per_ray = (48 * cs.node_fetch + 72 * cs.tri_fetch + 72 * cs.mat_fetch + 12 * cs.tex_fetch) / max(cs.rays, 1)
 
     # ---- multi-GPU: RCCL gather of every rank's screen-tile shard to rank 0;
     # the renderer runs on torch's current stream so the collective orders after the frame
@@ -203,11 +224,13 @@ def main():
     sync_all()
     t1 = time.perf_counter()
     st = r.stats()
+    if args.dump_outputs:  # before any further leg renders into the same running means
+        dump_outputs(args.dump_outputs, cfg, r, gather, rank)
     # N > 1: the same steps with one gather per frame (one frame per launch), the cadence at which
     # the reference presents (IS main.cpp:706), timed the same way -- reported next to the batched
     # figure, whose image reaches rank 0 once per batch of `batch` frames
     per_frame_ms = per_frame_rays = None
-    if gather is not None and batch > 1:
+    if args.full and gather is not None and batch > 1:
         sync_all()
         r.reset_stats()
         t4 = time.perf_counter()
@@ -321,12 +344,14 @@ def main():
         # the device: the roofline then divides by the wall time per frame (frame kernel + reorder +
         # running-mean update) instead
         pipelined = st.frames_in_flight > 1
-        roofline = make_roofline(args, cfg, ms_per_step if pipelined else kernel_ms_avg, rays_per_frame,
-                                 bytes_per_ray, n, "frame")
-        roofline["time_basis"] = ("wall ms per frame (frames in flight)" if pipelined
-                                  else "frame kernel HIP-event ms")
-        roofline["launch_ms"] = round(kernel_ms_avg, 4)
-        roofline["kernel"] = ("regenKernel<%s>" if st.regen else "renderKernel<%s>") % cfg.integrator
+        roofline = None
+        if args.full:
+            roofline = make_roofline(args, cfg, ms_per_step if pipelined else kernel_ms_avg, rays_per_frame,
+                                     bytes_per_ray, n, "frame")
+            roofline["time_basis"] = ("wall ms per frame (frames in flight)" if pipelined
+                                      else "frame kernel HIP-event ms")
+            roofline["launch_ms"] = round(kernel_ms_avg, 4)
+            roofline["kernel"] = ("regenKernel<%s>" if st.regen else "renderKernel<%s>") % cfg.integrator
         if serial_ms is not None:
             kb = make_roofline(args, cfg, serial_ms, rays_per_frame, bytes_per_ray, n, "frame_serial")
             roofline["kernel_basis"] = {
@@ -379,6 +404,33 @@ def main():
     r.close()
     if n > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs writes at most this much
+DUMP_SEED = 20240601  # of the pixel sample a larger image is cut down to
+
+
+def dump_outputs(out_dir, cfg, r, gather, rank):
+    """What the timed steps computed, as rank 0 holds it after the last of them: the running means
+    (N > 1, --shard tiles --gather accum: every rank's tiles, gathered) as <out_dir>/accum.npy, f32
+    H x W x 4; BASIC: the reference's double image, <out_dir>/basic_image.npy. An image above
+    DUMP_MAX_BYTES is cut down to a fixed, seeded sample of its pixels (rows of the flattened
+    image, ascending), whose indices go to <out_dir>/<name>_pixels.npy."""
+    if gather is not None:
+        gather.synchronize()
+    r.synchronize()
+    if rank != 0:
+        return
+    name, a = ("basic_image", r.basic_image()) if cfg.integrator == "basic" else ("accum", r.accum())
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    if a.nbytes > DUMP_MAX_BYTES:
+        px = a.reshape(-1, a.shape[-1])
+        keep = (DUMP_MAX_BYTES - 4096) // (px.itemsize * px.shape[1] + 8)  # the pixel and its index (f64: exact)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(px.shape[0], size=keep, replace=False))
+        np.save(out / f"{name}_pixels.npy", idx.astype(np.float64))
+        a = px[idx]
+    np.save(out / f"{name}.npy", np.ascontiguousarray(a))
 
 
 def make_roofline(args, cfg, kernel_ms, rays_per_frame, bytes_per_ray, n, basis="frame"):

@@ -31,7 +31,7 @@ def test_bench_two_ranks_print_the_line(gather):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"),
            "--gpus", "2", "--dist-backend", "gloo", "--same-device", "--steps", "4", "--warmup", "1",
-           "--no-cpu-baseline", "--no-psnr", "--no-reset", "--gather", gather]
+           "--full", "--no-cpu-baseline", "--no-psnr", "--no-reset", "--gather", gather]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(ROOT),
                          env={**os.environ, "OMP_NUM_THREADS": "4"})
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]

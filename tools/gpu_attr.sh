@@ -13,7 +13,7 @@ for v in "$@"; do
     name="${p%%:*}"; ctr="${p#*:}"
     if [ "$v" = base ]; then unset PT_VARIANT; else export PT_VARIANT=$v; fi
     timeout -s KILL 300 rocprofv3 --pmc $ctr -f csv -d "$OUT/$name" -o run -- \
-      python3 "$REPO/bench.py" --config "$CFG" --steps 16 --warmup 2 --no-cpu-baseline --no-psnr --no-reset --no-serial \
+      python3 "$REPO/bench.py" --full --config "$CFG" --steps 16 --warmup 2 --no-cpu-baseline --no-psnr --no-reset --no-serial \
       > "$OUT/$name.log" 2>&1; rc=$?
     echo "$v $name=$rc"; [ $rc -eq 0 ] || exit $rc
   done

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 for d in $DEPTHS; do
   OUT="$REPO/gpurun_out/ktrace_${CFG}_d$d"; mkdir -p "$OUT"
   PT_PIPE_DEPTH=$d timeout -k 10 180 rocprofv3 --kernel-trace --stats -f csv -d "$OUT" -o run -- \
-    python3 "$REPO/bench.py" --config $CFG --steps $K --warmup 5 --no-cpu-baseline --no-psnr --no-serial \
+    python3 "$REPO/bench.py" --full --config $CFG --steps $K --warmup 5 --no-cpu-baseline --no-psnr --no-serial \
     --no-reset > "$OUT/log.txt" 2>&1 || exit $?
   find "$OUT" -name '*kernel_trace.csv' -exec cp {} "$OUT/kernel_trace.csv" \;
   find "$OUT" -name '*kernel_stats.csv' -exec cp {} "$OUT/kernel_stats.csv" \;

@@ -8,4 +8,4 @@ CFG=${1:-c2}
 OUT="$REPO/gpurun_out/sq_$CFG"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM -f csv -d "$OUT" -o run -- \
-  python3 "$REPO/bench.py" --config $CFG --steps 16 --warmup 2 --no-cpu-baseline --no-psnr --no-reset --no-serial > "$OUT/log.txt" 2>&1
+  python3 "$REPO/bench.py" --full --config $CFG --steps 16 --warmup 2 --no-cpu-baseline --no-psnr --no-reset --no-serial > "$OUT/log.txt" 2>&1
