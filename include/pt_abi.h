@@ -26,14 +26,16 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 7  /* 2: in-process multi-GPU fields at the end of pt_config / pt_frame_stats;
+#define PT_ABI_VERSION 8  /* 2: in-process multi-GPU fields at the end of pt_config / pt_frame_stats;
                              3: scene-upload fields at the end of pt_frame_stats, pt_build_bvh_device;
                              4: BASIC shapes as doubles, its double image, the replayed random stream;
                              5: the displayed frame of a screen-tile split (pt_display_*);
                              6: batches of frames (pt_render_frames_async, pt_config.frame_batch,
                                 pt_frame_stats.frames), pt_config.hw_queues;
                              7: pt_unpack_ranks (every other rank's f32 gather in one launch);
-                                PT_FLAG_WAVEFRONT retired; pt_frame_stats.env_compact, tree4_nodes */
+                                PT_FLAG_WAVEFRONT retired; pt_frame_stats.env_compact, tree4_nodes;
+                             8: guide buffers and the edge-avoiding a-trous denoised display (pt_render_guides,
+                                pt_denoise, pt_display_denoised); no existing struct changes */
 
 /* error codes */
 #define PT_OK 0
@@ -284,6 +286,62 @@ int pt_unpack_ranks(pt_ctx* ctx, int world, const void* const* dpacked);
 int pt_display_pack(pt_ctx* ctx, float limit, float gamma, void* dpacked);
 int pt_display_own(pt_ctx* ctx, float limit, float gamma, void* dimage);
 int pt_display_unpack(pt_ctx* ctx, int world, const void* const* dpacked, void* dimage);
+
+/* Guide buffers and the denoised display. The interactive frame is 1 spp per display(): for the
+ * first seconds after a camera move the running mean is noisy. pt_render_guides traces the camera
+ * ray through every pixel centre once per camera, and pt_denoise filters the running mean with an
+ * edge-avoiding a-trous wavelet (Dammertz et al. 2010) steered by those guides; pt_display_denoised
+ * presents the result through the 8-bit display path. The accumulation is only read: progressive
+ * frames continue from it unchanged. The filter is an exact sequence of IEEE f32 operations
+ * (tests/denoise_ref.py restates it; the GPU output equals it bit for bit). */
+typedef struct pt_denoise_params {
+  int   passes;       /* 1..8; pass i uses tap stride 2^i */
+  float sigma_c;      /* colour term, on tone-mapped colour, halved every pass; <= 0: off */
+  float sigma_z;      /* plane-distance term, relative to the centre's hit distance; <= 0: off */
+  float sigma_a;      /* albedo term; <= 0: off */
+  int   normal_log2;  /* normal weight max(0, Np.Nq)^(2^normal_log2), 0..10; -1: off */
+  float limit;        /* the tonemap limit used inside the colour term (pass3: 1.5) */
+} pt_denoise_params;
+#define PT_DENOISE_PARAMS_SIZE 24 /* sizeof(pt_denoise_params), asserted by the library (pt_denoise_params_size) */
+
+void pt_denoise_defaults(pt_denoise_params* prm);  /* 5, 2.0, 0.02, 0.2, 6, 1.5 */
+int pt_denoise_params_size(void);                  /* sizeof(pt_denoise_params) of the loaded library */
+
+/* The camera's first hit of every pixel of the whole frame (a tile_world > 1 context's non-owned
+ * pixels included): startPath's ray with the jitter terms 0 (the pixel centre), pt_trace_closest's
+ * hit search (reference tie rules), then the integrators' hit record. Three float4 planes,
+ * width x height each, row 0 = the bottom row like the accumulation:
+ *   pos_t   = (P.x, P.y, P.z, t)
+ *   nrm_tri = (N.x, N.y, N.z, int bits of the uploaded triangle index), N the facing-flipped
+ *             shading normal the integrators use
+ *   albedo  = (baseColor.rgb, 1)
+ * a miss: (0, 0, 0, 2147483648.f), (0, 0, 0, bits(-1)), (0, 0, 0, 0). Context-owned device memory,
+ * valid until the next pt_render_guides, pt_upload_scene or pt_destroy. Asynchronous, on the
+ * context's stream; pt_frame_stats is not touched (no rays, launches or frames counted). With
+ * n_devices > 1 they are rendered on device_ids[0]. Not for PT_BASIC_CPU_COMPAT. */
+int pt_render_guides(pt_ctx* ctx, const float eye[3], const float cameraRotate[16]);
+/* each width*height*4 f32, nullable, host or device memory; synchronous */
+int pt_download_guides(pt_ctx* ctx, float* pos_t, float* nrm_tri, float* albedo);
+int pt_guides_device_ptr(pt_ctx* ctx, void** pos_t, void** nrm_tri, void** albedo);  /* each nullable */
+
+/* The a-trous filter of the accumulation, steered by the last pt_render_guides (PT_E_INVALID
+ * before one, or after pt_upload_scene invalidated it). prm NULL = pt_denoise_defaults. For pass
+ * i = 0 .. passes-1 (stride s = 2^i, colour sigma sigma_c 2^-i, c the pass's input, tm(c) =
+ * pt_tonemap's expression with gamma off and limit prm->limit): a miss pixel is copied; a hit pixel
+ * p sums the 25 taps q = p + s (dx, dy) that are inside the image and hits, with
+ *   k = H[|dx|] H[|dy|], H = {0.375, 0.25, 0.0625};  n = max(0, Np.Nq) squared normal_log2 times;
+ *   a = |Np.(Pq - Pp)| / (sigma_z t_p) + |tm(cq) - tm(cp)|^2 / sigma_c_i^2 + |Aq - Ap|^2 / sigma_a^2;
+ *   w = (k n) exp(-a);   out.rgb = sum(cq w) / sum(w) (cp.rgb when the sum is not > 0), out.w = cp.w.
+ * The last pass writes d_out_rgba (width*height*4 f32 device memory), or with NULL a
+ * context-owned buffer (pt_denoised_device_ptr). Asynchronous, on the context's stream, after
+ * the frames rendered so far. */
+int pt_denoise(pt_ctx* ctx, const pt_denoise_params* prm, void* d_out_rgba);
+int pt_denoised_device_ptr(pt_ctx* ctx, void** dptr);
+/* the last pt_denoise's image, width*height*4 f32 into host or device memory; synchronous */
+int pt_download_denoised(pt_ctx* ctx, float* rgba);
+/* pt_display_own's tonemap and 8-bit store of the last pt_denoise's image (every pixel, whatever
+ * tile_world is), into a width x height RGBA8 device image. PT_E_INVALID before any pt_denoise. */
+int pt_display_denoised(pt_ctx* ctx, float limit, float gamma, void* dimage);
 
 /* Stream interop: render on the caller's HIP stream (e.g. torch's current
  * stream). NULL restores the context's own stream. */

@@ -13,9 +13,10 @@ from . import _build
 
 _lib = None
 
-ABI_VERSION = 7  # include/pt_abi.h PT_ABI_VERSION
+ABI_VERSION = 8  # include/pt_abi.h PT_ABI_VERSION
 # an older tuning build (tools/tune.py A/B against a previous round's library) loads when its structs
-# match: ABI 7 only added pt_unpack_ranks, which such a build does not have
+# match: ABI 7 only added pt_unpack_ranks and ABI 8 the guide buffers and the denoiser, which such a
+# build does not have
 ABI_STRUCTS_SINCE = 6
 c_float_p = C.POINTER(C.c_float)
 c_double_p = C.POINTER(C.c_double)
@@ -43,6 +44,14 @@ class PtFrameStats(C.Structure):
         ("upload_ms", C.c_float), ("accel_build_ms", C.c_float), ("accel_device", C.c_int),
         ("accel_nodes", C.c_int), ("accel_depth", C.c_int), ("regen", C.c_int),
         ("frames", C.c_int64), ("frame_batch", C.c_int), ("env_compact", C.c_int), ("tree4_nodes", C.c_int),
+    ]
+
+
+class PtDenoiseParams(C.Structure):
+    """pt_denoise_params (include/pt_abi.h): PT_DENOISE_PARAMS_SIZE bytes."""
+    _fields_ = [
+        ("passes", C.c_int), ("sigma_c", C.c_float), ("sigma_z", C.c_float), ("sigma_a", C.c_float),
+        ("normal_log2", C.c_int), ("limit", C.c_float),
     ]
 
 
@@ -88,6 +97,16 @@ SIGNATURES = {
     "pt_display_pack": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
     "pt_display_own": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
     "pt_display_unpack": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    "pt_denoise_defaults": (None, [C.POINTER(PtDenoiseParams)]),
+    "pt_denoise_params_size": (C.c_int, []),
+    "pt_render_guides": (C.c_int, [C.c_void_p, c_float_p, c_float_p]),
+    "pt_download_guides": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p]),
+    "pt_guides_device_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p)]),
+    "pt_denoise": (C.c_int, [C.c_void_p, C.POINTER(PtDenoiseParams), C.c_void_p]),
+    "pt_denoised_device_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "pt_download_denoised": (C.c_int, [C.c_void_p, c_float_p]),
+    "pt_display_denoised": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
     "pt_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pt_synchronize": (C.c_int, [C.c_void_p]),
     "pt_get_stats": (C.c_int, [C.c_void_p, C.POINTER(PtFrameStats)]),

@@ -622,4 +622,18 @@ __device__ __forceinline__ V3 sampleBRDF(float xi_1, float xi_2, float xi_3, V3 
   return v3(0, 1, 0);
 }
 
+// ------------------------------------------------------------ display
+// pass3.fsh:14-24 tonemap (+ optional gamma, commented out in the reference)
+__device__ __forceinline__ V3 tonemapPixel(float4 c, float limit, float gamma) {
+  float lum = 0.3f * c.x + 0.6f * c.y + 0.1f * c.z;
+  float s = 1.0f / (1.0f + lum / limit);
+  float r = c.x * s, g = c.y * s, b = c.z * s;
+  if (gamma > 0.0f) {
+    r = ptm_powf(r, 1.0f / gamma);
+    g = ptm_powf(g, 1.0f / gamma);
+    b = ptm_powf(b, 1.0f / gamma);
+  }
+  return v3(r, g, b);
+}
+
 }  // namespace pt

@@ -406,6 +406,44 @@ hipError_t launchRegen(const RenderParams& p, int integrator, int grid, hipStrea
 int regenLdsStack();
 int regenTop4(const RegenShape& r, int integrator);  // 4-wide nodes the wide regen kernel stages in LDS (PT_REGEN_TOP4[_3])
 hipError_t launchTrace(const TraceParams& p, int grid, hipStream_t s, bool cull);
+// Guide buffers (pt_guides.hip): the camera's first hit of every pixel centre, one lane per pixel,
+// one wave per 8x8 tile (a grid-stride loop over the tiles), three float4 planes
+struct GuideParams {
+  SceneView scene;
+  int width, height;
+  float eye[3];
+  float cam[16];
+  float4* posT;    // (P, t); a miss (0, 0, 0, PT_INF)
+  float4* nrmTri;  // (N, triangle index bits); a miss (0, 0, 0, bits(-1))
+  float4* albedo;  // (baseColor, 1); a miss 0
+  int* ovf;        // traversal stack overflow (per thread ovfDepth ints), may be null
+  int ovfDepth;
+};
+hipError_t launchGuides(const GuideParams& p, int grid, hipStream_t s, bool cull);
+// The edge-avoiding a-trous filter (pt_denoise.hip), one launch per pass. Every pass reads its
+// input colour `in` and that colour tone-mapped `tmIn` (both float4 planes), and writes `out` and,
+// for the next pass, tm(out) to `tmOut` (null on the last pass); launchAtrousTm writes the first
+// pass's tm plane from the accumulation.
+struct AtrousParams {
+  int width, height;
+  int stride;                // 2^pass
+  const float4* in;
+  const float4* tmIn;
+  const float4* posT;
+  const float4* nrmTri;
+  const float4* albedo;
+  float4* out;
+  float4* tmOut;
+  float sigmaZ;              // <= 0: term off
+  float colDen, albDen;      // sigma_c_i^2, sigma_a^2
+  int colOn, albOn;
+  int normalLog2;            // -1: term off
+  float limit;
+};
+constexpr int ATROUS_TILE = 16;     // a block's 16 x 16 output pixels
+constexpr int ATROUS_LDS_STRIDE = 2;  // passes of stride <= this stage their tile + halo in LDS
+hipError_t launchAtrousTm(const float4* in, float4* tm, int n, float limit, hipStream_t s);
+hipError_t launchAtrous(const AtrousParams& p, hipStream_t s);
 hipError_t launchBasic(const BasicParams& p, hipStream_t s);
 // BASIC checkpoints: the double image from the f32 sums (widened), or the f32 sums from the double image
 hipError_t launchBasicWiden(const float4* accum, double* image, long n, hipStream_t s);

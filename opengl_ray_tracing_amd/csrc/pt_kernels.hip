@@ -31,83 +31,6 @@ namespace pt {
 
 
 // ------------------------------------------------------------ integrators
-template <bool CULL, bool COUNT>
-struct Tracer {
-  const SceneView& S;
-  Stack& st;
-  Counters& C;
-  const float4* top;  // LDS copy of the top of the tree traversed first (null = none)
-  // closest hit: the triangle (-1 = miss) and its t. With S.fast, through the
-  // runtime's tree and checked against the reference's (pt_trace.h refReachable).
-  __device__ __forceinline__ int trace(V3 o, V3 d, float& t) {
-    if (PT_WIDE4 && !COUNT && S.fast) {  // the 4-wide runtime tree (PT_WIDE4), checked as the binary one
-      bool tie = false;
-      int tri = traceRay4<CULL, Stack, (PT_WIDE4 == 2)>(S, o, d, t, st, C, false, top, &tie);
-      if (tie || (tri >= 0 && !refReachable(S, tri, o, d, t))) {
-        C.rays--;
-        tri = traceRay<false, CULL, false, Stack>(S, o, d, t, st, C);
-      }
-      return tri;
-    }
-    if (!COUNT && S.fast) {
-      bool tie = false;
-      const SceneView F = fastView(S);
-      const int pos = traceRay<false, CULL, false, Stack, (LDS_NODES > 0), true, FAST_KIND>(F, o, d, t, st, C, false, top, &tie);
-      int tri = pos >= 0 ? S.fastTri[pos] : -1;
-      if (tie || (tri >= 0 && !refReachable(S, tri, o, d, t))) {
-        C.rays--;  // the same ray, counted once
-        tri = traceRay<false, CULL, false, Stack>(S, o, d, t, st, C);
-      }
-      return tri;
-    }
-    return traceRay<false, CULL, COUNT, Stack, (LDS_NODES > 0)>(S, o, d, t, st, C, false, top);
-  }
-  __device__ __forceinline__ bool closest(V3 o, V3 d, Hit& h) {
-    float t;
-    const int tri = trace(o, d, t);
-    if (tri < 0) return false;
-    finishHit(S, tri, o, d, t, h);
-    return true;
-  }
-  __device__ __forceinline__ bool occluded(V3 o, V3 d) {
-    float t;
-    if (PT_WIDE4 && !COUNT && S.fast) {
-      bool tie = false;
-      const int tri = traceRay4<CULL, Stack, (PT_WIDE4 == 2)>(S, o, d, t, st, C, true, top, &tie);
-      if (tri < 0) return false;
-      if (refReachable(S, tri, o, d, t)) return true;
-      C.rays--;
-      return traceRay<true, CULL, false, Stack>(S, o, d, t, st, C) >= 0;
-    }
-    if (!COUNT && S.fast) {
-      const SceneView F = fastView(S);
-      const int pos = traceRay<true, CULL, false, Stack, (LDS_NODES > 0), false, FAST_KIND>(F, o, d, t, st, C, false, top);
-      if (pos < 0) return false;
-      if (refReachable(S, S.fastTri[pos], o, d, t)) return true;
-      C.rays--;
-      return traceRay<true, CULL, false, Stack>(S, o, d, t, st, C) >= 0;
-    }
-    // COUNT reproduces the reference's closest-hit shadow query fetch by fetch
-    return traceRay<!COUNT, CULL, COUNT, Stack, (LDS_NODES > 0)>(S, o, d, t, st, C, false, top) >= 0;
-  }
-  // closest (anyhit false) or env-shadow (anyhit true: >= 0 = occluded) query through ONE call site
-  // of the traversal, so a path loop that traces its shadow and BRDF rays from the same place
-  // keeps one copy of the walk (and its registers) live: trace() / occluded() per lane
-  __device__ __forceinline__ int traceK(V3 o, V3 d, bool anyhit, float& t) {
-    if (PT_WIDE4 && !COUNT && S.fast) {
-      bool tie = false;
-      int tri = traceRay4<CULL, Stack, (PT_WIDE4 == 2)>(S, o, d, t, st, C, anyhit, top, &tie);
-      if ((tie && !anyhit) || (tri >= 0 && !refReachable(S, tri, o, d, t))) {
-        C.rays--;  // the same ray, counted once
-        tri = traceRay<false, CULL, false, Stack>(S, o, d, t, st, C, anyhit);
-      }
-      return tri;
-    }
-    if (anyhit) return occluded(o, d) ? 0 : -1;
-    return trace(o, d, t);
-  }
-};
-
 // pathTracing O:329-364
 template <class T>
 __device__ V3 pathLambert(T& tr, const Env& env, Hit hit, int maxBounce, uint32_t& seed, Counters& C, bool count) {
@@ -1025,18 +948,7 @@ __global__ __launch_bounds__(BLOCK) void traceKernel(TraceParams p) {
 }
 
 // ------------------------------------------------------------ epilogues
-// pass3.fsh:14-24 tonemap (+ optional gamma, commented out in the reference)
-__device__ __forceinline__ V3 tonemapPixel(float4 c, float limit, float gamma) {
-  float lum = 0.3f * c.x + 0.6f * c.y + 0.1f * c.z;
-  float s = 1.0f / (1.0f + lum / limit);
-  float r = c.x * s, g = c.y * s, b = c.z * s;
-  if (gamma > 0.0f) {
-    r = ptm_powf(r, 1.0f / gamma);
-    g = ptm_powf(g, 1.0f / gamma);
-    b = ptm_powf(b, 1.0f / gamma);
-  }
-  return v3(r, g, b);
-}
+// (tonemapPixel: pt_device.h, shared with the denoiser's colour term)
 __global__ void tonemapKernel(const float4* accum, float* rgb, int n, float limit, float gamma) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

@@ -218,6 +218,17 @@ struct pt_ctx {
   int* d_tri = nullptr;
   size_t traceCap = 0;
   float* d_rgb = nullptr;
+  // guide buffers of the last pt_render_guides (valid for the scene version they were traced in) and
+  // the denoiser's images: two ping-pong colour planes, their tone-mapped planes, and the
+  // image the last pt_denoise wrote (one of the two, or the caller's)
+  float4* d_guide[3] = {};   // pos_t, nrm_tri, albedo
+  bool guidesValid = false;
+  unsigned guideVersion = 0;
+  int* d_guideOvf = nullptr;  // the guide kernel's own stack overflow area (frames in flight use d_ovf)
+  size_t guideOvfInts = 0;
+  float4* d_dn[2] = {};
+  float4* d_dnTm[2] = {};
+  const float4* denoised = nullptr;
   // in-process multi-GPU (pt_config.n_devices > 1): this context renders as
   // screen-tile rank 0 on device_ids[0] and owns the other ranks' contexts and
   // the per-frame gather of their tiles into its accumulation
@@ -505,6 +516,8 @@ void pt_destroy(pt_ctx* ctx) {
   dfree(ctx->d_basicImg); dfree(ctx->d_stream); dfree(ctx->d_offsets); dfree(ctx->d_overruns);
   dfree(ctx->d_accum); dfree(ctx->d_ctl); dfree(ctx->d_ovf); dfree(ctx->d_cost); dfree(ctx->d_order);
   dfree(ctx->d_rays); dfree(ctx->d_t); dfree(ctx->d_tri); dfree(ctx->d_rgb);
+  for (auto& g : ctx->d_guide) dfree(g);
+  dfree(ctx->d_guideOvf); dfree(ctx->d_dn[0]); dfree(ctx->d_dn[1]); dfree(ctx->d_dnTm[0]); dfree(ctx->d_dnTm[1]);
   freePrimaryBins(ctx->bins);
   for (int k = 0; k < PIPE; k++) {
     if (ctx->slotStream[k]) (void)hipStreamSynchronize(ctx->slotStream[k]);
@@ -2248,6 +2261,171 @@ int pt_display_unpack(pt_ctx* ctx, int world, const void* const* dpacked, void* 
     d.count[k] = packParams(ctx, k, world).count;
   }
   CK(launchDisplayUnpack(d, world, reinterpret_cast<uchar4*>(dimage), ctx->stream));
+  return PT_OK;
+}
+
+// ------------------------------------------------------------ guide buffers and the denoised display
+static_assert(sizeof(pt_denoise_params) == PT_DENOISE_PARAMS_SIZE, "pt_denoise_params layout");
+
+void pt_denoise_defaults(pt_denoise_params* prm) {
+  if (!prm) return;
+  prm->passes = 5;
+  prm->sigma_c = 2.0f;
+  prm->sigma_z = 0.02f;
+  prm->sigma_a = 0.2f;
+  prm->normal_log2 = 6;
+  prm->limit = 1.5f;
+}
+
+int pt_denoise_params_size(void) { return (int)sizeof(pt_denoise_params); }
+
+// a context that can hold guides: a GL integrator with a scene
+static int guideContext(pt_ctx* ctx, const char* what) {
+  if (ctx->cfg.integrator == PT_BASIC_CPU_COMPAT)
+    return fail(ctx, PT_E_INVALID, std::string(what) + ": not for PT_BASIC_CPU_COMPAT contexts");
+  if (!ctx->d_bvh) return fail(ctx, PT_E_NOSCENE, std::string(what) + ": no scene");
+  return PT_OK;
+}
+static int guidesReady(pt_ctx* ctx, const char* what) {
+  if (int rc = guideContext(ctx, what)) return rc;
+  if (!ctx->guidesValid || ctx->guideVersion != ctx->sceneVersion)
+    return fail(ctx, PT_E_INVALID, std::string(what) + ": no guides of this scene (pt_render_guides first)");
+  return PT_OK;
+}
+
+int pt_render_guides(pt_ctx* ctx, const float eye[3], const float cameraRotate[16]) {
+  if (!ctx || !eye || !cameraRotate) return PT_E_INVALID;
+  if (int rc = guideContext(ctx, "pt_render_guides")) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const int W = ctx->cfg.width, H = ctx->cfg.height;
+  const size_t npix = (size_t)W * H;
+  for (auto& g : ctx->d_guide)
+    if (!g) CK(hipMalloc(&g, npix * sizeof(float4)));
+  const long tiles = (long)((W + 7) / 8) * ((H + 7) / 8);
+  const int grid = (int)std::min<long>((tiles + BLOCK / 64 - 1) / (BLOCK / 64), (long)ctx->numCU * 8);
+  // the kernel's own overflow area: frames in flight keep using d_ovf meanwhile
+  const int ovfDepth = ctx->maxStack > LDS_STACK ? ctx->maxStack - LDS_STACK / 2 : 0;
+  const size_t need = (size_t)grid * BLOCK * (size_t)ovfDepth;
+  if (need > ctx->guideOvfInts) {
+    CK(hipStreamSynchronize(ctx->stream));  // an earlier guide launch may still use the old area
+    dfree(ctx->d_guideOvf);
+    ctx->guideOvfInts = 0;
+    CK(hipMalloc(&ctx->d_guideOvf, need * sizeof(int)));
+    ctx->guideOvfInts = need;
+  }
+  GuideParams p;
+  p.scene = sceneView(ctx);
+  // the hit search of pt_trace_closest: the runtime's own tree, results reference-exact
+  p.scene.fast = ctx->fastReady && !(ctx->cfg.flags & (PT_FLAG_REFERENCE_TREE | PT_FLAG_COUNT_FETCHES)) ? 1 : 0;
+  p.width = W;
+  p.height = H;
+  std::memcpy(p.eye, eye, sizeof(p.eye));
+  std::memcpy(p.cam, cameraRotate, sizeof(p.cam));
+  p.posT = ctx->d_guide[0];
+  p.nrmTri = ctx->d_guide[1];
+  p.albedo = ctx->d_guide[2];
+  p.ovf = ovfDepth ? ctx->d_guideOvf : nullptr;
+  p.ovfDepth = ovfDepth;
+  const bool cull = !(ctx->cfg.flags & (PT_FLAG_NO_CULL | PT_FLAG_COUNT_FETCHES));
+  CK(launchGuides(p, grid, ctx->stream, cull));
+  ctx->guidesValid = true;
+  ctx->guideVersion = ctx->sceneVersion;
+  return PT_OK;
+}
+
+int pt_download_guides(pt_ctx* ctx, float* pos_t, float* nrm_tri, float* albedo) {
+  if (!ctx) return PT_E_INVALID;
+  if (int rc = guidesReady(ctx, "pt_download_guides")) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const size_t bytes = (size_t)ctx->cfg.width * ctx->cfg.height * sizeof(float4);
+  float* dst[3] = {pos_t, nrm_tri, albedo};
+  for (int k = 0; k < 3; k++)
+    if (dst[k]) CK(hipMemcpyAsync(dst[k], ctx->d_guide[k], bytes, hipMemcpyDefault, ctx->stream));  // host or device
+  CK(hipStreamSynchronize(ctx->stream));
+  return PT_OK;
+}
+
+int pt_guides_device_ptr(pt_ctx* ctx, void** pos_t, void** nrm_tri, void** albedo) {
+  if (!ctx) return PT_E_INVALID;
+  if (int rc = guidesReady(ctx, "pt_guides_device_ptr")) return rc;
+  if (pos_t) *pos_t = ctx->d_guide[0];
+  if (nrm_tri) *nrm_tri = ctx->d_guide[1];
+  if (albedo) *albedo = ctx->d_guide[2];
+  return PT_OK;
+}
+
+int pt_denoise(pt_ctx* ctx, const pt_denoise_params* prm, void* d_out_rgba) {
+  if (!ctx) return PT_E_INVALID;
+  if (int rc = guidesReady(ctx, "pt_denoise")) return rc;
+  pt_denoise_params P;
+  pt_denoise_defaults(&P);
+  if (prm) P = *prm;
+  if (P.passes < 1 || P.passes > 8) return fail(ctx, PT_E_INVALID, "pt_denoise: passes must be 1..8");
+  if (P.normal_log2 < -1 || P.normal_log2 > 10) return fail(ctx, PT_E_INVALID, "pt_denoise: normal_log2 must be -1..10");
+  if (!(P.limit > 0.0f)) return fail(ctx, PT_E_INVALID, "pt_denoise: limit must be > 0");
+  // the accumulation as the frames rendered so far leave it
+  if (int rc = joinGather(ctx)) return rc;
+  if (int rc = joinPipe(ctx)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const int W = ctx->cfg.width, H = ctx->cfg.height;
+  const size_t npix = (size_t)W * H;
+  for (int k = 0; k < 2; k++) {
+    if (!ctx->d_dn[k]) CK(hipMalloc(&ctx->d_dn[k], npix * sizeof(float4)));
+    if (!ctx->d_dnTm[k]) CK(hipMalloc(&ctx->d_dnTm[k], npix * sizeof(float4)));
+  }
+  CK(launchAtrousTm(ctx->d_accum, ctx->d_dnTm[0], (int)npix, P.limit, ctx->stream));
+  AtrousParams a;
+  a.width = W;
+  a.height = H;
+  a.posT = ctx->d_guide[0];
+  a.nrmTri = ctx->d_guide[1];
+  a.albedo = ctx->d_guide[2];
+  a.sigmaZ = P.sigma_z;
+  a.albDen = P.sigma_a * P.sigma_a;
+  a.albOn = P.sigma_a > 0.0f;
+  a.normalLog2 = P.normal_log2;
+  a.limit = P.limit;
+  const float4* in = ctx->d_accum;
+  for (int i = 0; i < P.passes; i++) {
+    const bool last = i == P.passes - 1;
+    const float sc = P.sigma_c * (1.0f / (float)(1 << i));  // halved every pass
+    a.stride = 1 << i;
+    a.colDen = sc * sc;
+    a.colOn = sc > 0.0f;
+    a.in = in;
+    a.tmIn = ctx->d_dnTm[i & 1];
+    a.out = last && d_out_rgba ? reinterpret_cast<float4*>(d_out_rgba) : ctx->d_dn[i & 1];
+    a.tmOut = last ? nullptr : ctx->d_dnTm[(i + 1) & 1];
+    CK(launchAtrous(a, ctx->stream));
+    in = a.out;
+  }
+  ctx->denoised = in;
+  return PT_OK;
+}
+
+int pt_denoised_device_ptr(pt_ctx* ctx, void** dptr) {
+  if (!ctx || !dptr) return PT_E_INVALID;
+  if (!ctx->denoised) return fail(ctx, PT_E_INVALID, "pt_denoised_device_ptr: no pt_denoise yet");
+  *dptr = const_cast<float4*>(ctx->denoised);
+  return PT_OK;
+}
+
+int pt_download_denoised(pt_ctx* ctx, float* rgba) {
+  if (!ctx || !rgba) return PT_E_INVALID;
+  if (!ctx->denoised) return fail(ctx, PT_E_INVALID, "pt_download_denoised: no pt_denoise yet");
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const size_t bytes = (size_t)ctx->cfg.width * ctx->cfg.height * sizeof(float4);
+  CK(hipMemcpyAsync(rgba, ctx->denoised, bytes, hipMemcpyDefault, ctx->stream));  // host or device
+  CK(hipStreamSynchronize(ctx->stream));
+  return PT_OK;
+}
+
+int pt_display_denoised(pt_ctx* ctx, float limit, float gamma, void* dimage) {
+  if (!ctx || !dimage || !(limit > 0.0f)) return PT_E_INVALID;
+  if (!ctx->denoised) return fail(ctx, PT_E_INVALID, "pt_display_denoised: no pt_denoise yet");
+  CK(hipSetDevice(ctx->cfg.device_id));
+  PackParams p = packParams(ctx, 0, 1);  // every pixel: the denoised image is the whole frame
+  CK(launchDisplayOwn(p, ctx->denoised, limit, gamma, reinterpret_cast<uchar4*>(dimage), ctx->stream));
   return PT_OK;
 }
 

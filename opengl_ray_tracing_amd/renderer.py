@@ -296,6 +296,57 @@ class Renderer:
         arr = (C.c_void_p * world)(*[C.c_void_p(int(x)) if x else C.c_void_p() for x in dpacked])
         self._ck(self._lib.pt_display_unpack(self._h, int(world), arr, C.c_void_p(dimage)), "pt_display_unpack")
 
+    def render_guides(self, eye, camera_rotate):
+        """Guide buffers of this camera (pt_render_guides): every pixel centre's first hit. Asynchronous."""
+        e = np.ascontiguousarray(eye, np.float32)
+        r = np.ascontiguousarray(camera_rotate, np.float32).reshape(16)
+        self._ck(self._lib.pt_render_guides(self._h, _fp(e), _fp(r)), "pt_render_guides")
+
+    def guides(self) -> dict:
+        """The guide planes, (h, w, 4) f32 each, row 0 = bottom: "pos_t" (P, t), "nrm_tri" (N, the
+        triangle index's int bits) and "albedo" (baseColor, 1); "tri" is nrm_tri's last channel
+        viewed as int32 (-1 = miss)."""
+        out = {k: np.empty((self.height, self.width, 4), np.float32) for k in ("pos_t", "nrm_tri", "albedo")}
+        self._ck(self._lib.pt_download_guides(self._h, _fp(out["pos_t"]), _fp(out["nrm_tri"]), _fp(out["albedo"])),
+                 "pt_download_guides")
+        out["tri"] = out["nrm_tri"][..., 3].view(np.int32)
+        return out
+
+    def guides_device_ptrs(self):
+        p = [C.c_void_p() for _ in range(3)]
+        self._ck(self._lib.pt_guides_device_ptr(self._h, *[C.byref(x) for x in p]), "pt_guides_device_ptr")
+        return tuple(x.value for x in p)
+
+    def denoise(self, out_dptr: int | None = None, download: bool = True, **params):
+        """The edge-avoiding a-trous filter of the accumulation (pt_denoise), steered by the last
+        render_guides. params: passes, sigma_c, sigma_z, sigma_a, normal_log2, limit (defaults:
+        pt_denoise_defaults). With out_dptr (H x W x 4 f32 device memory) asynchronous, returns
+        None; without, returns the denoised image (h, w, 4) -- or, with download False, leaves it
+        in the context's buffer (denoised_device_ptr, display_denoised) without synchronising."""
+        prm = _native.PtDenoiseParams()
+        self._lib.pt_denoise_defaults(C.byref(prm))
+        for k, v in params.items():
+            if k not in ("passes", "sigma_c", "sigma_z", "sigma_a", "normal_log2", "limit"):
+                raise TypeError(f"denoise() has no parameter {k!r}")
+            setattr(prm, k, int(v) if k in ("passes", "normal_log2") else float(v))
+        self._ck(self._lib.pt_denoise(self._h, C.byref(prm), C.c_void_p(out_dptr) if out_dptr else None),
+                 "pt_denoise")
+        if out_dptr or not download:
+            return None
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(self._lib.pt_download_denoised(self._h, _fp(out)), "pt_download_denoised")
+        return out
+
+    def denoised_device_ptr(self) -> int:
+        p = C.c_void_p()
+        self._ck(self._lib.pt_denoised_device_ptr(self._h, C.byref(p)), "pt_denoised_device_ptr")
+        return p.value
+
+    def display_denoised(self, dimage: int, limit: float = 1.5, gamma: float = 0.0):
+        """The last denoise()'s image through the 8-bit display path into an H x W x 4 u8 device image."""
+        self._ck(self._lib.pt_display_denoised(self._h, float(limit), float(gamma), C.c_void_p(dimage)),
+                 "pt_display_denoised")
+
     def set_stream(self, stream_ptr: int | None):
         self._ck(self._lib.pt_set_stream(self._h, C.c_void_p(stream_ptr) if stream_ptr else None), "pt_set_stream")
 

@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Device time of the guide buffers, the a-trous passes and the denoised display on the GPU.
+
+    python tools/denoise_time.py [c2 c4 ...] [--reps 100] [--out out/denoise_time.json]
+
+Method: the renderer runs on a torch stream, HIP events (torch.cuda.Event) around `reps`
+repetitions after a warm-up, profiler off, each config at its own size (c2 / c4: 1080p).
+ * guides: pt_render_guides.
+ * denoise[k]: pt_denoise with k passes (the tone-mapped plane of the accumulation + k passes).
+ * pass[s]: denoise[k] - denoise[k-1] for s = 2^(k-1) (pass[1] includes the accumulation's
+   tone-mapped plane; the last pass of a call writes no tone-mapped plane), and its compulsory
+   80 B/pixel (16 B colour in, 48 B guides, 16 B colour out) over that time.
+ * display: pt_display_denoised.
+ * frame: wall time per iteration of pt_denoise (defaults) + pt_display_denoised + one synchronous
+   pt_render_frame -- what a display() pays per presented frame (60 Hz: 16.6 ms).
+One JSON line per config.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+HBM_COPY_TBS = 6.29  # measured HBM copy rate
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("configs", nargs="*", default=["c2", "c4"])
+    ap.add_argument("--reps", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+
+    from opengl_ray_tracing_amd import Renderer, orbit_camera, scenes
+    if not torch.cuda.is_available():
+        raise RuntimeError("denoise_time: no GPU visible")
+    lines = []
+    for name in a.configs:
+        cfg, tris, nodes, hdr = scenes.build_config(name)
+        eye, rot = orbit_camera(*cfg.camera)
+        w, h = cfg.width, cfg.height
+        stream = torch.cuda.Stream()
+        with Renderer(w, h, cfg.integrator, max_bounce=cfg.max_bounce) as r:
+            r.upload_scene(tris, nodes)
+            r.upload_env(hdr)
+            r.set_stream(stream.cuda_stream)
+            frame = 0
+            for _ in range(32):  # past the runtime's policy probe, a settled running mean
+                r.render_frame(eye, rot, frame)
+                frame += 1
+            image = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+
+            def timed(fn):
+                for _ in range(a.warmup):
+                    fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(a.reps):
+                    fn()
+                e1.record(stream)
+                e1.synchronize()
+                return e0.elapsed_time(e1) / a.reps
+
+            res = {"config": name, "width": w, "height": h, "reps": a.reps}
+            res["guides_ms"] = timed(lambda: r.render_guides(eye, rot))
+            cum = [0.0] + [timed(lambda k=k: r.denoise(download=False, passes=k)) for k in range(1, 9)]
+            res["denoise_ms_by_passes"] = {str(k): cum[k] for k in range(1, 9)}
+            res["pass_ms_by_stride"] = {str(1 << (k - 1)): cum[k] - cum[k - 1] for k in range(1, 9)}
+            res["pass_TBs_of_80B"] = {s: 80.0 * w * h / (ms * 1e-3) / 1e12 for s, ms in res["pass_ms_by_stride"].items()}
+            res["hbm_copy_TBs"] = HBM_COPY_TBS
+            res["denoise_default_ms"] = timed(lambda: r.denoise(download=False))
+            res["display_ms"] = timed(lambda: r.display_denoised(image.data_ptr(), 1.5, 0.0))
+            # the presented frame: filter + display + one synchronous progressive frame
+            r.synchronize()
+            st0 = r.stats()
+            t0 = time.perf_counter()
+            for _ in range(a.reps):
+                r.denoise(download=False)
+                r.display_denoised(image.data_ptr(), 1.5, 0.0)
+                r.render_frame(eye, rot, frame)
+                frame += 1
+            res["frame_wall_ms"] = (time.perf_counter() - t0) * 1e3 / a.reps
+            st1 = r.stats()
+            res["render_frame_kernel_ms"] = (st1.kernel_ms_total - st0.kernel_ms_total) / a.reps
+            res["fits_60hz"] = res["frame_wall_ms"] <= 1000.0 / 60.0
+        line = json.dumps(res)
+        print(line, flush=True)
+        lines.append(line)
+    if a.out:
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

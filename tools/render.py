@@ -4,6 +4,7 @@ configuration progressively and write the image.
 
     python tools/render.py --config c2 --frames 64 --out gpurun_out/c2.png   # pass3 tonemap + PNG
     python tools/render.py --config c4 --frames 16 --out gpurun_out/c4.pfm   # linear accumulation
+    python tools/render.py --config c4 --frames 4 --denoise --out out/c4.png  # + out/c4_denoised.png
 
 PNG: pass3's tonemap (pass3.fsh:14-24, limit 1.5) then imshow's gamma 2.2
 (BasicRayTracingWithC++/main.cpp:169-190); the BASIC config skips the tonemap
@@ -26,6 +27,7 @@ def main():
     ap.add_argument("--out", default="gpurun_out/render.png")
     ap.add_argument("--builder", default=None)
     ap.add_argument("--flags", type=int, default=0)
+    ap.add_argument("--denoise", action="store_true", help="also write <out>_denoised.png (pt_denoise, defaults)")
     a = ap.parse_args()
     import numpy as np
 
@@ -57,6 +59,17 @@ def main():
             Image.fromarray(imshow_bytes(r.basic_image())).save(a.out)
         else:
             write_png(a.out, r.tonemap(1.5), 2.2, flip_rows=True)
+        if a.denoise and not basic:
+            # the edge-avoiding a-trous filter of the running mean (pt_denoise, default parameters),
+            # through the same tonemap and gamma, beside the plain image
+            r.render_guides(eye, rot)
+            c = r.denoise()[..., :3]
+            lum = np.float32(0.3) * c[..., 0] + np.float32(0.6) * c[..., 1] + np.float32(0.1) * c[..., 2]
+            tm = c * (np.float32(1) / (np.float32(1) + lum / np.float32(1.5)))[..., None]
+            out = Path(a.out)
+            dn = str(out.with_name(out.stem + "_denoised.png"))
+            write_png(dn, np.ascontiguousarray(tm, np.float32), 2.2, flip_rows=True)
+            print(f"{a.config}: denoised -> {dn}")
     print(f"{a.config}: {a.frames} frames in {dt * 1e3:.1f} ms, {st.rays / dt / 1e6:.1f} Mrays/s -> {a.out}")
 
 
