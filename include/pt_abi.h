@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 8  /* 2: in-process multi-GPU fields at the end of pt_config / pt_frame_stats;
+#define PT_ABI_VERSION 9  /* 2: in-process multi-GPU fields at the end of pt_config / pt_frame_stats;
                              3: scene-upload fields at the end of pt_frame_stats, pt_build_bvh_device;
                              4: BASIC shapes as doubles, its double image, the replayed random stream;
                              5: the displayed frame of a screen-tile split (pt_display_*);
@@ -35,7 +35,10 @@ extern "C" {
                              7: pt_unpack_ranks (every other rank's f32 gather in one launch);
                                 PT_FLAG_WAVEFRONT retired; pt_frame_stats.env_compact, tree4_nodes;
                              8: guide buffers and the edge-avoiding a-trous denoised display (pt_render_guides,
-                                pt_denoise, pt_display_denoised); no existing struct changes */
+                                pt_denoise, pt_display_denoised); no existing struct changes;
+                             9: the running mean reprojected across camera moves (pt_temporal_resolve,
+                                pt_temporal_commit, pt_display_resolved) and pt_denoise_from; no existing
+                                struct changes */
 
 /* error codes */
 #define PT_OK 0
@@ -336,12 +339,83 @@ int pt_guides_device_ptr(pt_ctx* ctx, void** pos_t, void** nrm_tri, void** albed
  * context-owned buffer (pt_denoised_device_ptr). Asynchronous, on the context's stream, after
  * the frames rendered so far. */
 int pt_denoise(pt_ctx* ctx, const pt_denoise_params* prm, void* d_out_rgba);
+/* pt_denoise reading d_in_rgba (width*height*4 f32 device memory, e.g. pt_resolved_device_ptr)
+ * instead of the accumulation; NULL = the accumulation (pt_denoise is this call with NULL). The
+ * input's .w is carried through. d_in_rgba is only read; it must not be d_out_rgba or the
+ * context's own denoised buffer (pt_denoised_device_ptr): PT_E_INVALID. */
+int pt_denoise_from(pt_ctx* ctx, const pt_denoise_params* prm, const void* d_in_rgba, void* d_out_rgba);
 int pt_denoised_device_ptr(pt_ctx* ctx, void** dptr);
 /* the last pt_denoise's image, width*height*4 f32 into host or device memory; synchronous */
 int pt_download_denoised(pt_ctx* ctx, float* rgba);
 /* pt_display_own's tonemap and 8-bit store of the last pt_denoise's image (every pixel, whatever
  * tile_world is), into a width x height RGBA8 device image. PT_E_INVALID before any pt_denoise. */
 int pt_display_denoised(pt_ctx* ctx, float limit, float gamma, void* dimage);
+
+/* The running mean reprojected across camera moves. Every caller of pt_render_frame restarts at
+ * frameCounter = 0 when the camera moves, so during a drag each presented picture is a 1-spp image
+ * and what the previous cameras accumulated is lost. The scene is static: the first-hit position P
+ * that pt_render_guides holds for a pixel projects straight into the previous camera, with no new
+ * ray. pt_temporal_resolve fetches the previous camera's resolved image there (bilinear, each tap
+ * tested against the centre's plane and normal) and blends it with the running mean of the new
+ * camera, weighted by sample count; pt_temporal_commit makes the resolved image and the current
+ * guides the history of the next camera. The accumulation is only read and pt_frame_stats is not
+ * touched. The step is an exact sequence of IEEE f32 operations (tests/temporal_ref.py restates it;
+ * the GPU output equals it bit for bit).
+ *
+ * The display() loop:  if (cameraMoved) { pt_temporal_commit; pt_render_guides; frameCounter = 0; }
+ *                      pt_render_frame; pt_temporal_resolve(frames = frameCounter + 1);
+ *                      pt_denoise_from(resolved); pt_display_denoised.
+ *
+ * Limits: the history holds the radiance the previous cameras saw, so view-dependent (glossy)
+ * shading lags behind the camera: lower max_history there. */
+typedef struct pt_temporal_params {
+  float sigma_z;      /* a history tap is accepted when |Np.(Pq - Pp)| <= sigma_z * t_p; >= 0 */
+  float normal_cos;   /* ... and Np.Nq >= normal_cos, in [-1, 1] */
+  float max_history;  /* cap of the reprojected sample count, >= 1 */
+} pt_temporal_params;
+#define PT_TEMPORAL_PARAMS_SIZE 12 /* sizeof(pt_temporal_params), asserted by the library (pt_temporal_params_size) */
+
+void pt_temporal_defaults(pt_temporal_params* prm);  /* 0.02, 0.9, 32 */
+int pt_temporal_params_size(void);                   /* sizeof(pt_temporal_params) of the loaded library */
+
+/* One resolve of the whole frame (whatever tile_world is: rank 0 calls it after the unpack), steered
+ * by the last pt_render_guides, which must be of the camera the accumulation was rendered with
+ * (PT_E_INVALID before one or after pt_upload_scene invalidated it, as pt_denoise). prm NULL =
+ * pt_temporal_defaults. frames = the frames in the accumulation, frameCounter + 1 (0: PT_E_INVALID).
+ * With c the accumulation, kf = (float)frames, E' / M' the history camera's eye and cameraRotate,
+ * c0 = M'[0..2], c1 = M'[4..6], c2 = M'[8..10], dot(a, b) = (ax bx + ay by) + az bz, per pixel p:
+ *   out = (c.rgb, kf)
+ *   with a history, for a hit pixel:
+ *     v = Pp - E';  a = dot(c0, v);  b = dot(c1, v);  cz = dot(c2, v);  s = -1.5 / cz
+ *     fx = (a s + 1) (0.5 W) - 0.5;  fy = (b s + 1) (0.5 H) - 0.5
+ *     ok = cz < 0 && -1 < fx < W && -1 < fy < H;  (ix, iy) = floor(fx, fy);  (tx, ty) = the fractions
+ *     the taps q = (ix + i, iy + j), j = 0, 1 outer, i = 0, 1 inner, bilinear weight wt: valid when q is
+ *     inside the image, a hit of the history, hist[q].w > 0, |Np.(Pq - Pp)| <= sigma_z t_p and
+ *     Np.Nq >= normal_cos;  wv = valid ? wt : 0;  sw += wv;  sum += hist[q].rgb wv;  sn += hist[q].w wv
+ *     ok && sw > 0:  hc = sum / sw;  n = min(sn / sw, max_history);  wgt = kf / (n + kf);
+ *                    out = (hc (1 - wgt) + c.rgb wgt, n + kf)
+ * A miss pixel shows the environment texel directly and takes no history. Without a history (before
+ * the first commit, after pt_temporal_reset, pt_upload_scene or pt_upload_env) out is the
+ * accumulation's rgb, bit for bit, with count kf. The width x height float4 plane goes to
+ * d_out_rgba (device memory), or with NULL to a context-owned buffer (pt_resolved_device_ptr).
+ * Resolving again without a commit recomputes from the same history. Asynchronous, on the context's
+ * stream, after the frames rendered so far. With n_devices > 1 on device_ids[0]. Not for
+ * PT_BASIC_CPU_COMPAT. */
+int pt_temporal_resolve(pt_ctx* ctx, const pt_temporal_params* prm, uint32_t frames, void* d_out_rgba);
+/* The last resolved image, the current guides' pos_t and nrm_tri and the camera they were rendered
+ * with become the history. Nothing is copied: the context keeps two resolved planes and two sets of
+ * pos_t / nrm_tri; every later pt_render_guides writes the set that is not the history (so
+ * pt_guides_device_ptr may alternate), and the current guides stay valid and readable until then.
+ * PT_E_INVALID when no pt_temporal_resolve has run since the last commit, reset or
+ * pt_render_guides, or when the last resolve went to a caller's buffer (d_out_rgba != NULL): the
+ * library keeps no reference to memory the caller may overwrite -- resolve with NULL to commit. */
+int pt_temporal_commit(pt_ctx* ctx);
+int pt_temporal_reset(pt_ctx* ctx);  /* drops the history (as pt_upload_scene and pt_upload_env do) */
+/* the last pt_temporal_resolve's image (PT_E_INVALID before one) */
+int pt_resolved_device_ptr(pt_ctx* ctx, void** dptr);
+int pt_download_resolved(pt_ctx* ctx, float* rgba);  /* host or device memory, width*height*4 f32; synchronous */
+/* pt_display_denoised of the last pt_temporal_resolve's image */
+int pt_display_resolved(pt_ctx* ctx, float limit, float gamma, void* dimage);
 
 /* Stream interop: render on the caller's HIP stream (e.g. torch's current
  * stream). NULL restores the context's own stream. */

@@ -50,6 +50,7 @@ SOURCES = {
     "pt_guides.o": ("hip", CSRC / "pt_guides.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", CSRC / "pt_trace.h",
                                                      INCLUDE / "pt_fmath.h"]),
     "pt_denoise.o": ("hip", CSRC / "pt_denoise.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]),
+    "pt_temporal.o": ("hip", CSRC / "pt_temporal.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]),
     "pt_runtime.o": ("cxx", CSRC / "pt_runtime.cpp", [CSRC / "pt_kernels.h", INCLUDE / "pt_abi.h", INCLUDE / "pt_scene.h",
                                                        INCLUDE / "pt_fmath.h", CSRC / "pt_rccl.h"]),
     "pt_rccl.o": ("cxx", CSRC / "pt_rccl.cpp", [CSRC / "pt_rccl.h"]),

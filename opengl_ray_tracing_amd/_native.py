@@ -13,10 +13,10 @@ from . import _build
 
 _lib = None
 
-ABI_VERSION = 8  # include/pt_abi.h PT_ABI_VERSION
+ABI_VERSION = 9  # include/pt_abi.h PT_ABI_VERSION
 # an older tuning build (tools/tune.py A/B against a previous round's library) loads when its structs
-# match: ABI 7 only added pt_unpack_ranks and ABI 8 the guide buffers and the denoiser, which such a
-# build does not have
+# match: ABI 7 only added pt_unpack_ranks, ABI 8 the guide buffers and the denoiser and ABI 9 the
+# temporal resolve, which such a build does not have
 ABI_STRUCTS_SINCE = 6
 c_float_p = C.POINTER(C.c_float)
 c_double_p = C.POINTER(C.c_double)
@@ -45,6 +45,11 @@ class PtFrameStats(C.Structure):
         ("accel_nodes", C.c_int), ("accel_depth", C.c_int), ("regen", C.c_int),
         ("frames", C.c_int64), ("frame_batch", C.c_int), ("env_compact", C.c_int), ("tree4_nodes", C.c_int),
     ]
+
+
+class PtTemporalParams(C.Structure):
+    """pt_temporal_params (include/pt_abi.h): PT_TEMPORAL_PARAMS_SIZE bytes."""
+    _fields_ = [("sigma_z", C.c_float), ("normal_cos", C.c_float), ("max_history", C.c_float)]
 
 
 class PtDenoiseParams(C.Structure):
@@ -107,6 +112,15 @@ SIGNATURES = {
     "pt_denoised_device_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "pt_download_denoised": (C.c_int, [C.c_void_p, c_float_p]),
     "pt_display_denoised": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
+    "pt_denoise_from": (C.c_int, [C.c_void_p, C.POINTER(PtDenoiseParams), C.c_void_p, C.c_void_p]),
+    "pt_temporal_defaults": (None, [C.POINTER(PtTemporalParams)]),
+    "pt_temporal_params_size": (C.c_int, []),
+    "pt_temporal_resolve": (C.c_int, [C.c_void_p, C.POINTER(PtTemporalParams), C.c_uint32, C.c_void_p]),
+    "pt_temporal_commit": (C.c_int, [C.c_void_p]),
+    "pt_temporal_reset": (C.c_int, [C.c_void_p]),
+    "pt_resolved_device_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "pt_download_resolved": (C.c_int, [C.c_void_p, c_float_p]),
+    "pt_display_resolved": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
     "pt_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pt_synchronize": (C.c_int, [C.c_void_p]),
     "pt_get_stats": (C.c_int, [C.c_void_p, C.POINTER(PtFrameStats)]),

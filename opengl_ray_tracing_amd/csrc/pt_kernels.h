@@ -444,6 +444,25 @@ constexpr int ATROUS_TILE = 16;     // a block's 16 x 16 output pixels
 constexpr int ATROUS_LDS_STRIDE = 2;  // passes of stride <= this stage their tile + halo in LDS
 hipError_t launchAtrousTm(const float4* in, float4* tm, int n, float limit, hipStream_t s);
 hipError_t launchAtrous(const AtrousParams& p, hipStream_t s);
+// The temporal resolve (pt_temporal.hip): the running mean `accum` blended, weighted by sample count,
+// with the previous camera's resolved image `hist` fetched through the current first-hit positions
+// (pt_abi.h pt_temporal_resolve). hist null: no history (out = accum's rgb, count `frames`).
+struct TemporalParams {
+  int width, height;
+  const float4* accum;       // the running mean of the current camera
+  const float4* posT;        // the current guides
+  const float4* nrmTri;
+  const float4* hist;        // the history's resolved image (rgb, sample count), may be null
+  const float4* histPosT;    // and the guides it was committed with
+  const float4* histNrmTri;
+  float4* out;
+  float eye[3];              // the history camera: eye and the rotation's first three columns
+  float c0[3], c1[3], c2[3];
+  float sigmaZ, normalCos, maxHistory;
+  float frames;              // (float)frames of the accumulation
+};
+constexpr int TEMPORAL_TILE = 16;  // a block's 16 x 16 pixels, each wave an 8 x 8 quadrant
+hipError_t launchTemporal(const TemporalParams& p, hipStream_t s);
 hipError_t launchBasic(const BasicParams& p, hipStream_t s);
 // BASIC checkpoints: the double image from the f32 sums (widened), or the f32 sums from the double image
 hipError_t launchBasicWiden(const float4* accum, double* image, long n, hipStream_t s);

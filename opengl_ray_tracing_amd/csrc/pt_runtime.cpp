@@ -221,7 +221,12 @@ struct pt_ctx {
   // guide buffers of the last pt_render_guides (valid for the scene version they were traced in) and
   // the denoiser's images: two ping-pong colour planes, their tone-mapped planes, and the
   // image the last pt_denoise wrote (one of the two, or the caller's)
-  float4* d_guide[3] = {};   // pos_t, nrm_tri, albedo
+  float4* d_guide[3] = {};   // pos_t, nrm_tri, albedo of the current set (guideSet)
+  // pos_t / nrm_tri exist twice: pt_temporal_commit marks the current set as the history's, and
+  // pt_render_guides then writes the other one (albedo is not part of the history: one plane)
+  float4* d_guidePN[2][2] = {};
+  int guideSet = 0;
+  float guideEye[3] = {}, guideCam[16] = {};  // the camera of the current guides
   bool guidesValid = false;
   unsigned guideVersion = 0;
   int* d_guideOvf = nullptr;  // the guide kernel's own stack overflow area (frames in flight use d_ovf)
@@ -229,6 +234,15 @@ struct pt_ctx {
   float4* d_dn[2] = {};
   float4* d_dnTm[2] = {};
   const float4* denoised = nullptr;
+  // the temporal resolve: two resolved planes (the one the last resolve wrote and, after a commit,
+  // the history's), the image the last resolve wrote (one of the two, or the caller's), the history
+  float4* d_res[2] = {};
+  int resCur = 0;                  // the plane the next context-owned resolve writes
+  const float4* resolved = nullptr;
+  bool resolvedFresh = false;      // a resolve since the last commit / reset / pt_render_guides
+  bool histValid = false;
+  int histSet = 0, histRes = 0;    // the history's guide set and resolved plane
+  float histEye[3] = {}, histCam[16] = {};
   // in-process multi-GPU (pt_config.n_devices > 1): this context renders as
   // screen-tile rank 0 on device_ids[0] and owns the other ranks' contexts and
   // the per-frame gather of their tiles into its accumulation
@@ -516,7 +530,9 @@ void pt_destroy(pt_ctx* ctx) {
   dfree(ctx->d_basicImg); dfree(ctx->d_stream); dfree(ctx->d_offsets); dfree(ctx->d_overruns);
   dfree(ctx->d_accum); dfree(ctx->d_ctl); dfree(ctx->d_ovf); dfree(ctx->d_cost); dfree(ctx->d_order);
   dfree(ctx->d_rays); dfree(ctx->d_t); dfree(ctx->d_tri); dfree(ctx->d_rgb);
-  for (auto& g : ctx->d_guide) dfree(g);
+  dfree(ctx->d_guide[2]);
+  for (auto& set : ctx->d_guidePN) for (auto& g : set) dfree(g);
+  dfree(ctx->d_res[0]); dfree(ctx->d_res[1]);
   dfree(ctx->d_guideOvf); dfree(ctx->d_dn[0]); dfree(ctx->d_dn[1]); dfree(ctx->d_dnTm[0]); dfree(ctx->d_dnTm[1]);
   freePrimaryBins(ctx->bins);
   for (int k = 0; k < PIPE; k++) {
@@ -957,9 +973,16 @@ static std::string prepareScene(const float* tris, int nTri, const float* nodes,
 static int syncStreams(pt_ctx* ctx);
 static int ensureBasicImage(pt_ctx* ctx);
 
+// the temporal history shows another scene or another light after an upload
+static void dropHistory(pt_ctx* ctx) {
+  ctx->histValid = false;
+  ctx->resolvedFresh = false;
+}
+
 static int uploadScene(pt_ctx* ctx, const float* tris, const SceneHost& h) {
   if (int rc = syncStreams(ctx)) return rc;  // no frame in flight reads the buffers replaced here
   ctx->policyKey++;  // the tree / split policies are measured again at the next restart
+  dropHistory(ctx);
   CK(hipSetDevice(ctx->cfg.device_id));
   int rc;
   if ((rc = upload(ctx, &ctx->d_pairs, h.pairs)) || (rc = upload(ctx, &ctx->d_geo, h.geo)) ||
@@ -1281,6 +1304,7 @@ static int envOne(pt_ctx* ctx, const float* hdr, int w, int h, const float* cach
 
 int pt_upload_env(pt_ctx* ctx, const float* hdr, int w, int h, const float* cache) {
   if (!ctx) return PT_E_INVALID;
+  dropHistory(ctx);
   if (ctx->peers.empty()) return envOne(ctx, hdr, w, h, cache);
   // a device group computes calculateHdrCache once (on rank 0's GPU) and uploads it everywhere
   std::vector<float> own;
@@ -2299,8 +2323,15 @@ int pt_render_guides(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
   CK(hipSetDevice(ctx->cfg.device_id));
   const int W = ctx->cfg.width, H = ctx->cfg.height;
   const size_t npix = (size_t)W * H;
-  for (auto& g : ctx->d_guide)
+  // the set that is not the history's
+  const int set = ctx->histValid ? 1 - ctx->histSet : ctx->guideSet;
+  for (auto& g : ctx->d_guidePN[set])
     if (!g) CK(hipMalloc(&g, npix * sizeof(float4)));
+  if (!ctx->d_guide[2]) CK(hipMalloc(&ctx->d_guide[2], npix * sizeof(float4)));
+  ctx->guideSet = set;
+  ctx->d_guide[0] = ctx->d_guidePN[set][0];
+  ctx->d_guide[1] = ctx->d_guidePN[set][1];
+  ctx->resolvedFresh = false;  // a resolve of the previous guides is not committed with these
   const long tiles = (long)((W + 7) / 8) * ((H + 7) / 8);
   const int grid = (int)std::min<long>((tiles + BLOCK / 64 - 1) / (BLOCK / 64), (long)ctx->numCU * 8);
   // the kernel's own overflow area: frames in flight keep using d_ovf meanwhile
@@ -2330,6 +2361,8 @@ int pt_render_guides(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
   CK(launchGuides(p, grid, ctx->stream, cull));
   ctx->guidesValid = true;
   ctx->guideVersion = ctx->sceneVersion;
+  std::memcpy(ctx->guideEye, eye, sizeof(ctx->guideEye));
+  std::memcpy(ctx->guideCam, cameraRotate, sizeof(ctx->guideCam));
   return PT_OK;
 }
 
@@ -2355,6 +2388,10 @@ int pt_guides_device_ptr(pt_ctx* ctx, void** pos_t, void** nrm_tri, void** albed
 }
 
 int pt_denoise(pt_ctx* ctx, const pt_denoise_params* prm, void* d_out_rgba) {
+  return pt_denoise_from(ctx, prm, nullptr, d_out_rgba);
+}
+
+int pt_denoise_from(pt_ctx* ctx, const pt_denoise_params* prm, const void* d_in_rgba, void* d_out_rgba) {
   if (!ctx) return PT_E_INVALID;
   if (int rc = guidesReady(ctx, "pt_denoise")) return rc;
   pt_denoise_params P;
@@ -2363,6 +2400,10 @@ int pt_denoise(pt_ctx* ctx, const pt_denoise_params* prm, void* d_out_rgba) {
   if (P.passes < 1 || P.passes > 8) return fail(ctx, PT_E_INVALID, "pt_denoise: passes must be 1..8");
   if (P.normal_log2 < -1 || P.normal_log2 > 10) return fail(ctx, PT_E_INVALID, "pt_denoise: normal_log2 must be -1..10");
   if (!(P.limit > 0.0f)) return fail(ctx, PT_E_INVALID, "pt_denoise: limit must be > 0");
+  // the passes ping-pong through the context's two planes: an input that is one of them, or the
+  // output, would be overwritten while it is read
+  if (d_in_rgba && (d_in_rgba == d_out_rgba || d_in_rgba == ctx->d_dn[0] || d_in_rgba == ctx->d_dn[1]))
+    return fail(ctx, PT_E_INVALID, "pt_denoise_from: the input must not be the output or the context's denoised buffer");
   // the accumulation as the frames rendered so far leave it
   if (int rc = joinGather(ctx)) return rc;
   if (int rc = joinPipe(ctx)) return rc;
@@ -2373,7 +2414,8 @@ int pt_denoise(pt_ctx* ctx, const pt_denoise_params* prm, void* d_out_rgba) {
     if (!ctx->d_dn[k]) CK(hipMalloc(&ctx->d_dn[k], npix * sizeof(float4)));
     if (!ctx->d_dnTm[k]) CK(hipMalloc(&ctx->d_dnTm[k], npix * sizeof(float4)));
   }
-  CK(launchAtrousTm(ctx->d_accum, ctx->d_dnTm[0], (int)npix, P.limit, ctx->stream));
+  const float4* in = d_in_rgba ? reinterpret_cast<const float4*>(d_in_rgba) : ctx->d_accum;
+  CK(launchAtrousTm(in, ctx->d_dnTm[0], (int)npix, P.limit, ctx->stream));
   AtrousParams a;
   a.width = W;
   a.height = H;
@@ -2385,7 +2427,6 @@ int pt_denoise(pt_ctx* ctx, const pt_denoise_params* prm, void* d_out_rgba) {
   a.albOn = P.sigma_a > 0.0f;
   a.normalLog2 = P.normal_log2;
   a.limit = P.limit;
-  const float4* in = ctx->d_accum;
   for (int i = 0; i < P.passes; i++) {
     const bool last = i == P.passes - 1;
     const float sc = P.sigma_c * (1.0f / (float)(1 << i));  // halved every pass
@@ -2426,6 +2467,120 @@ int pt_display_denoised(pt_ctx* ctx, float limit, float gamma, void* dimage) {
   CK(hipSetDevice(ctx->cfg.device_id));
   PackParams p = packParams(ctx, 0, 1);  // every pixel: the denoised image is the whole frame
   CK(launchDisplayOwn(p, ctx->denoised, limit, gamma, reinterpret_cast<uchar4*>(dimage), ctx->stream));
+  return PT_OK;
+}
+
+// ------------------------------------------------------------ the temporal resolve
+static_assert(sizeof(pt_temporal_params) == PT_TEMPORAL_PARAMS_SIZE, "pt_temporal_params layout");
+
+void pt_temporal_defaults(pt_temporal_params* prm) {
+  if (!prm) return;
+  prm->sigma_z = 0.02f;
+  prm->normal_cos = 0.9f;
+  prm->max_history = 32.0f;
+}
+
+int pt_temporal_params_size(void) { return (int)sizeof(pt_temporal_params); }
+
+int pt_temporal_resolve(pt_ctx* ctx, const pt_temporal_params* prm, uint32_t frames, void* d_out_rgba) {
+  if (!ctx) return PT_E_INVALID;
+  if (int rc = guidesReady(ctx, "pt_temporal_resolve")) return rc;
+  pt_temporal_params P;
+  pt_temporal_defaults(&P);
+  if (prm) P = *prm;
+  if (frames == 0) return fail(ctx, PT_E_INVALID, "pt_temporal_resolve: frames must be >= 1 (frameCounter + 1)");
+  if (!(P.sigma_z >= 0.0f)) return fail(ctx, PT_E_INVALID, "pt_temporal_resolve: sigma_z must be >= 0");
+  if (!(P.normal_cos >= -1.0f && P.normal_cos <= 1.0f))
+    return fail(ctx, PT_E_INVALID, "pt_temporal_resolve: normal_cos must be in [-1, 1]");
+  if (!(P.max_history >= 1.0f)) return fail(ctx, PT_E_INVALID, "pt_temporal_resolve: max_history must be >= 1");
+  // the accumulation as the frames rendered so far leave it
+  if (int rc = joinGather(ctx)) return rc;
+  if (int rc = joinPipe(ctx)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const int W = ctx->cfg.width, H = ctx->cfg.height;
+  const size_t npix = (size_t)W * H;
+  float4* out = reinterpret_cast<float4*>(d_out_rgba);
+  if (!out) {
+    // never the history's plane: a second resolve recomputes from the same history
+    const int k = ctx->histValid ? 1 - ctx->histRes : ctx->resCur;
+    if (!ctx->d_res[k]) CK(hipMalloc(&ctx->d_res[k], npix * sizeof(float4)));
+    ctx->resCur = k;
+    out = ctx->d_res[k];
+  }
+  TemporalParams t;
+  t.width = W;
+  t.height = H;
+  t.accum = ctx->d_accum;
+  t.posT = ctx->d_guide[0];
+  t.nrmTri = ctx->d_guide[1];
+  t.hist = t.histPosT = t.histNrmTri = nullptr;
+  if (ctx->histValid) {
+    t.hist = ctx->d_res[ctx->histRes];
+    t.histPosT = ctx->d_guidePN[ctx->histSet][0];
+    t.histNrmTri = ctx->d_guidePN[ctx->histSet][1];
+  }
+  t.out = out;
+  for (int k = 0; k < 3; k++) {
+    t.eye[k] = ctx->histEye[k];
+    t.c0[k] = ctx->histCam[k];
+    t.c1[k] = ctx->histCam[4 + k];
+    t.c2[k] = ctx->histCam[8 + k];
+  }
+  t.sigmaZ = P.sigma_z;
+  t.normalCos = P.normal_cos;
+  t.maxHistory = P.max_history;
+  t.frames = (float)frames;
+  CK(launchTemporal(t, ctx->stream));
+  ctx->resolved = out;
+  ctx->resolvedFresh = true;
+  return PT_OK;
+}
+
+int pt_temporal_commit(pt_ctx* ctx) {
+  if (!ctx) return PT_E_INVALID;
+  if (int rc = guidesReady(ctx, "pt_temporal_commit")) return rc;
+  if (!ctx->resolvedFresh)
+    return fail(ctx, PT_E_INVALID, "pt_temporal_commit: no pt_temporal_resolve since the last commit, reset or pt_render_guides");
+  if (ctx->resolved != ctx->d_res[ctx->resCur])
+    return fail(ctx, PT_E_INVALID, "pt_temporal_commit: the last resolve went to a caller's buffer (resolve with NULL to commit)");
+  ctx->histRes = ctx->resCur;
+  ctx->histSet = ctx->guideSet;
+  std::memcpy(ctx->histEye, ctx->guideEye, sizeof(ctx->histEye));
+  std::memcpy(ctx->histCam, ctx->guideCam, sizeof(ctx->histCam));
+  ctx->histValid = true;
+  ctx->resolvedFresh = false;
+  return PT_OK;
+}
+
+int pt_temporal_reset(pt_ctx* ctx) {
+  if (!ctx) return PT_E_INVALID;
+  dropHistory(ctx);
+  return PT_OK;
+}
+
+int pt_resolved_device_ptr(pt_ctx* ctx, void** dptr) {
+  if (!ctx || !dptr) return PT_E_INVALID;
+  if (!ctx->resolved) return fail(ctx, PT_E_INVALID, "pt_resolved_device_ptr: no pt_temporal_resolve yet");
+  *dptr = const_cast<float4*>(ctx->resolved);
+  return PT_OK;
+}
+
+int pt_download_resolved(pt_ctx* ctx, float* rgba) {
+  if (!ctx || !rgba) return PT_E_INVALID;
+  if (!ctx->resolved) return fail(ctx, PT_E_INVALID, "pt_download_resolved: no pt_temporal_resolve yet");
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const size_t bytes = (size_t)ctx->cfg.width * ctx->cfg.height * sizeof(float4);
+  CK(hipMemcpyAsync(rgba, ctx->resolved, bytes, hipMemcpyDefault, ctx->stream));  // host or device
+  CK(hipStreamSynchronize(ctx->stream));
+  return PT_OK;
+}
+
+int pt_display_resolved(pt_ctx* ctx, float limit, float gamma, void* dimage) {
+  if (!ctx || !dimage || !(limit > 0.0f)) return PT_E_INVALID;
+  if (!ctx->resolved) return fail(ctx, PT_E_INVALID, "pt_display_resolved: no pt_temporal_resolve yet");
+  CK(hipSetDevice(ctx->cfg.device_id));
+  PackParams p = packParams(ctx, 0, 1);  // every pixel: the resolved image is the whole frame
+  CK(launchDisplayOwn(p, ctx->resolved, limit, gamma, reinterpret_cast<uchar4*>(dimage), ctx->stream));
   return PT_OK;
 }
 

@@ -317,9 +317,10 @@ class Renderer:
         self._ck(self._lib.pt_guides_device_ptr(self._h, *[C.byref(x) for x in p]), "pt_guides_device_ptr")
         return tuple(x.value for x in p)
 
-    def denoise(self, out_dptr: int | None = None, download: bool = True, **params):
-        """The edge-avoiding a-trous filter of the accumulation (pt_denoise), steered by the last
-        render_guides. params: passes, sigma_c, sigma_z, sigma_a, normal_log2, limit (defaults:
+    def denoise(self, out_dptr: int | None = None, download: bool = True, src_dptr: int | None = None, **params):
+        """The edge-avoiding a-trous filter of the accumulation (pt_denoise) -- or, with src_dptr, of
+        an H x W x 4 f32 device image such as resolved_device_ptr() (pt_denoise_from) -- steered by
+        the last render_guides. params: passes, sigma_c, sigma_z, sigma_a, normal_log2, limit (defaults:
         pt_denoise_defaults). With out_dptr (H x W x 4 f32 device memory) asynchronous, returns
         None; without, returns the denoised image (h, w, 4) -- or, with download False, leaves it
         in the context's buffer (denoised_device_ptr, display_denoised) without synchronising."""
@@ -329,8 +330,11 @@ class Renderer:
             if k not in ("passes", "sigma_c", "sigma_z", "sigma_a", "normal_log2", "limit"):
                 raise TypeError(f"denoise() has no parameter {k!r}")
             setattr(prm, k, int(v) if k in ("passes", "normal_log2") else float(v))
-        self._ck(self._lib.pt_denoise(self._h, C.byref(prm), C.c_void_p(out_dptr) if out_dptr else None),
-                 "pt_denoise")
+        out_p = C.c_void_p(out_dptr) if out_dptr else None
+        if src_dptr:
+            self._ck(self._lib.pt_denoise_from(self._h, C.byref(prm), C.c_void_p(src_dptr), out_p), "pt_denoise_from")
+        else:
+            self._ck(self._lib.pt_denoise(self._h, C.byref(prm), out_p), "pt_denoise")
         if out_dptr or not download:
             return None
         out = np.empty((self.height, self.width, 4), np.float32)
@@ -346,6 +350,47 @@ class Renderer:
         """The last denoise()'s image through the 8-bit display path into an H x W x 4 u8 device image."""
         self._ck(self._lib.pt_display_denoised(self._h, float(limit), float(gamma), C.c_void_p(dimage)),
                  "pt_display_denoised")
+
+    def temporal_resolve(self, frames: int, out_dptr: int | None = None, download: bool = True, **params):
+        """The running mean of `frames` frames (frameCounter + 1) blended with the committed history
+        of the previous camera, reprojected through the last render_guides (pt_temporal_resolve).
+        params: sigma_z, normal_cos, max_history (defaults: pt_temporal_defaults). With out_dptr
+        (H x W x 4 f32 device memory) asynchronous, returns None -- such a resolve cannot be
+        committed; without, returns the resolved image (h, w, 4), .w = the sample count -- or, with
+        download False, leaves it in the context's buffer (resolved_device_ptr, display_resolved,
+        denoise(src_dptr=...)) without synchronising."""
+        prm = _native.PtTemporalParams()
+        self._lib.pt_temporal_defaults(C.byref(prm))
+        for k, v in params.items():
+            if k not in ("sigma_z", "normal_cos", "max_history"):
+                raise TypeError(f"temporal_resolve() has no parameter {k!r}")
+            setattr(prm, k, float(v))
+        self._ck(self._lib.pt_temporal_resolve(self._h, C.byref(prm), int(frames) & 0xFFFFFFFF,
+                                               C.c_void_p(out_dptr) if out_dptr else None), "pt_temporal_resolve")
+        if out_dptr or not download:
+            return None
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(self._lib.pt_download_resolved(self._h, _fp(out)), "pt_download_resolved")
+        return out
+
+    def temporal_commit(self):
+        """The last temporal_resolve's image and the current guides become the history (before the
+        camera moves: commit, then render_guides of the new camera)."""
+        self._ck(self._lib.pt_temporal_commit(self._h), "pt_temporal_commit")
+
+    def temporal_reset(self):
+        """Drops the history: the next temporal_resolve returns the running mean itself."""
+        self._ck(self._lib.pt_temporal_reset(self._h), "pt_temporal_reset")
+
+    def resolved_device_ptr(self) -> int:
+        p = C.c_void_p()
+        self._ck(self._lib.pt_resolved_device_ptr(self._h, C.byref(p)), "pt_resolved_device_ptr")
+        return p.value
+
+    def display_resolved(self, dimage: int, limit: float = 1.5, gamma: float = 0.0):
+        """The last temporal_resolve()'s image through the 8-bit display path into an H x W x 4 u8 device image."""
+        self._ck(self._lib.pt_display_resolved(self._h, float(limit), float(gamma), C.c_void_p(dimage)),
+                 "pt_display_resolved")
 
     def set_stream(self, stream_ptr: int | None):
         self._ck(self._lib.pt_set_stream(self._h, C.c_void_p(stream_ptr) if stream_ptr else None), "pt_set_stream")

@@ -1,0 +1,358 @@
+"""The temporal resolve on the GPU (pt_temporal_resolve, pt_temporal_commit, pt_display_resolved,
+pt_denoise_from) against the float32 restatement tests/temporal_ref.py, bit for bit: sizes from
+one pixel to several workgroups, camera moves from none to the opposite side, every parameter,
+both output kinds, the two-set guide scheme, the accumulation and the statistics left untouched,
+a screen-tile split, the 8-bit display, the history drops, the error paths and the quality gate.
+
+Reference: OpenglRayTracing/main.cpp mouse() / mouseWheel() (frameCounter = 0 on every camera
+move); IS pass1.fsh:846-850 (the camera ray the projection inverts); pass3.fsh:14-24 (the display).
+"""
+import ctypes as C
+import functools
+import re
+
+import numpy as np
+import pytest
+
+import denoise_ref as dr
+import temporal_ref as tr
+from opengl_ray_tracing_amd import Renderer, _native, orbit_camera, scenes
+from opengl_ray_tracing_amd._native import PtError
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+FRAMES = 2
+PARAMS = [dict(), dict(sigma_z=0.001), dict(normal_cos=0.999), dict(max_history=1.0)]
+
+
+def bits(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+@functools.lru_cache(maxsize=None)
+def config(name):
+    return scenes.build_config(name)
+
+
+def camera(name, delta=0.0):
+    """The config's camera moved `delta` degrees along its orbit."""
+    angle, up, rad = config(name)[0].camera
+    return orbit_camera(angle + delta, up, rad)
+
+
+def renderer(name, w, h, **kw):
+    cfg, tris, nodes, hdr = config(name)
+    r = Renderer(w, h, cfg.integrator, max_bounce=cfg.max_bounce, **kw)
+    r.upload_scene(tris, nodes)
+    r.upload_env(hdr)
+    return r
+
+
+def render_camera(r, eye, rot, frames=FRAMES):
+    """`frames` frames of a camera from frameCounter 0 and its guides -> (accumulation, guides)."""
+    for f in range(frames):
+        r.render_frame(eye, rot, f)
+    r.render_guides(eye, rot)
+    return r.accum(), r.guides()
+
+
+def device_plane(h, w, dtype="float32"):
+    import torch
+    t = torch.zeros((h, w, 4), dtype=getattr(torch, dtype), device="cuda:0")
+    torch.cuda.synchronize()  # the fill (torch's stream) before the renderer's stream writes it
+    return t
+
+
+# ------------------------------------------------------------------ bit-exact against the restatement
+@pytest.mark.parametrize("w,h", [(1, 1), (5, 3), (33, 31), (100, 76), (160, 90)])
+@pytest.mark.parametrize("name", ["c4", "c2"])
+def test_resolve_equals_the_restatement(name, w, h):
+    """Camera A (2 frames, no history: the accumulation with count 2), a commit, then the camera
+    moved by 0, 2, 20 and 180 degrees (2 frames): the defaults and each parameter changed in turn
+    into the context's buffer, the defaults into a caller's buffer. At 160x90 both branches are
+    exercised: at 2 degrees at least 0.9 of the hit pixels take history, at 20 degrees a share
+    strictly between 0.3 and 0.95."""
+    eyeA, rotA = camera(name)
+    with renderer(name, w, h) as r:
+        out = device_plane(h, w)
+        for delta in (0.0, 2.0, 20.0, 180.0):
+            r.temporal_reset()
+            acc, g = render_camera(r, eyeA, rotA)
+            got = r.temporal_resolve(FRAMES)
+            want = tr.resolve(acc, FRAMES, g, None)
+            assert np.array_equal(bits(got[..., :3]), bits(acc[..., :3])) and np.all(got[..., 3] == FRAMES)
+            assert np.array_equal(bits(got), bits(want))
+            r.temporal_commit()
+            hist = tr.commit(want, g, eyeA, rotA)
+            eyeB, rotB = camera(name, delta)
+            acc, g = render_camera(r, eyeB, rotB)
+            for prm in PARAMS:
+                got = r.temporal_resolve(FRAMES, **prm)
+                want = tr.resolve(acc, FRAMES, g, hist, **{**tr.DEFAULTS, **prm})
+                assert np.array_equal(bits(got), bits(want)), (delta, prm)
+                if not prm and (w, h) == (160, 90):
+                    hit = dr.hit_mask(g)
+                    share = float((got[..., 3][hit] > FRAMES).mean())
+                    print(f"{name} {delta:g} deg: {share:.3f} of the hit pixels take history")
+                    if delta == 2.0:
+                        assert share >= 0.9, share
+                    if delta == 20.0:
+                        assert 0.3 < share < 0.95, share
+            assert r.temporal_resolve(FRAMES, out.data_ptr()) is None
+            r.synchronize()
+            assert r.resolved_device_ptr() == out.data_ptr()
+            want = tr.resolve(acc, FRAMES, g, hist)
+            assert np.array_equal(bits(out.cpu().numpy()), bits(want)), delta
+            assert np.array_equal(bits(r.accum()), bits(acc))
+
+
+def test_three_camera_chain_with_a_count_cap():
+    """max_history = 2.5 over cameras 0, 2 and 4 degrees: counts 2, 4, then min(4, 2.5) + 2."""
+    w, h = 100, 76
+    hist = None
+    with renderer("c2", w, h) as r:
+        for k in range(3):
+            eye, rot = camera("c2", 2.0 * k)
+            acc, g = render_camera(r, eye, rot)
+            got = r.temporal_resolve(FRAMES, max_history=2.5)
+            want = tr.resolve(acc, FRAMES, g, hist, max_history=2.5)
+            assert np.array_equal(bits(got), bits(want)), k
+            r.temporal_commit()
+            hist = tr.commit(want, g, eye, rot)
+    assert got[..., 3].max() == 4.5 and (got[..., 3] == 4.5).sum() > 500
+
+
+# ------------------------------------------------------------------ the filter of the resolved image
+def test_denoise_from_the_resolved_image_and_from_null():
+    w, h = 100, 76
+    eyeA, rotA = camera("c2")
+    eyeB, rotB = camera("c2", 2.0)
+    with renderer("c2", w, h) as r:
+        render_camera(r, eyeA, rotA)
+        r.temporal_resolve(FRAMES, download=False)
+        r.temporal_commit()
+        acc, g = render_camera(r, eyeB, rotB)
+        res = r.temporal_resolve(FRAMES)
+        assert (res[..., 3] > FRAMES).any()
+        got = r.denoise(src_dptr=r.resolved_device_ptr(), passes=3)
+        want = dr.atrous(res, g, **{**dr.DEFAULTS, "passes": 3})
+        assert np.array_equal(bits(got), bits(want))  # .w, the sample count, is carried through
+        plain = r.denoise()
+        _native.check(r._lib.pt_denoise_from(r._h, None, None, None), r._h, "pt_denoise_from")
+        again = np.empty((h, w, 4), F)
+        _native.check(r._lib.pt_download_denoised(r._h, again.ctypes.data_as(_native.c_float_p)), r._h,
+                      "pt_download_denoised")
+        assert np.array_equal(bits(again), bits(plain))
+        assert np.array_equal(bits(plain), bits(dr.atrous(acc, g, **dr.DEFAULTS)))
+        # an input the passes would overwrite
+        with pytest.raises(PtError):
+            r.denoise(src_dptr=r.denoised_device_ptr())
+
+
+# ------------------------------------------------------------------ nothing else changes
+def test_accumulation_stats_and_guides_are_untouched():
+    """The accumulation is bit-identical before and after resolve and commit and later frames
+    equal a plain context's; rays, launches and frames do not change; the current guides still
+    download unchanged after a commit."""
+    w, h = 100, 76
+    eye, rot = camera("c2")
+    with renderer("c2", w, h) as r, renderer("c2", w, h) as plain:
+        for f in range(2):
+            plain.render_frame(eye, rot, f)
+        acc, g = render_camera(r, eye, rot)
+        ptrs = r.guides_device_ptrs()
+        before = r.stats()
+        r.temporal_resolve(FRAMES)
+        r.temporal_commit()
+        r.temporal_resolve(FRAMES)
+        after = r.stats()
+        assert (before.rays, before.launches, before.frames) == (after.rays, after.launches, after.frames)
+        assert np.array_equal(bits(r.accum()), bits(acc))
+        g2 = r.guides()
+        for k in ("pos_t", "nrm_tri", "albedo"):
+            assert np.array_equal(bits(g2[k]), bits(g[k])), k
+        assert r.guides_device_ptrs() == ptrs
+        for f in range(2, 4):
+            r.render_frame(eye, rot, f)
+            plain.render_frame(eye, rot, f)
+        assert np.array_equal(bits(r.accum()), bits(plain.accum()))
+
+
+def test_later_guides_do_not_clobber_the_history():
+    """Two pt_render_guides of different cameras after one commit write the set that is not the
+    history's: the next resolve equals the restatement with the committed history."""
+    w, h = 100, 76
+    eyeA, rotA = camera("c2")
+    with renderer("c2", w, h) as r:
+        acc, g = render_camera(r, eyeA, rotA)
+        want = tr.resolve(acc, FRAMES, g, None)
+        r.temporal_resolve(FRAMES, download=False)
+        r.temporal_commit()
+        hist = tr.commit(want, g, eyeA, rotA)
+        r.render_guides(*camera("c2", 40.0))
+        r.render_guides(*camera("c2", 7.0))
+        eyeB, rotB = camera("c2", 3.0)
+        acc, g = render_camera(r, eyeB, rotB)
+        got = r.temporal_resolve(FRAMES)
+        want = tr.resolve(acc, FRAMES, g, hist)
+        assert (want[..., 3] > FRAMES).sum() > 1000
+        assert np.array_equal(bits(got), bits(want))
+        assert np.array_equal(bits(r.temporal_resolve(FRAMES)), bits(want))  # idempotent without a commit
+
+
+def test_screen_tile_split_rank0_resolves_the_gathered_mean():
+    """Two tile_world = 2 contexts on one device: rank 0 unpacks rank 1's packed mean, renders the
+    guides, resolves and commits, then again at a second camera: an unsplit context's result."""
+    import torch
+    w, h, world = 100, 76, 2
+    cams = [camera("c2"), camera("c2", 2.0)]
+    want = []
+    with renderer("c2", w, h) as r:
+        for eye, rot in cams:
+            render_camera(r, eye, rot)
+            want.append(r.temporal_resolve(FRAMES))
+            r.temporal_commit()
+    got = []
+    ranks = [renderer("c2", w, h, tile_rank=k, tile_world=world) for k in range(world)]
+    try:
+        buf = torch.zeros((ranks[1].owned_pixel_count(), 3), dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()
+        for eye, rot in cams:
+            for rr in ranks:
+                for f in range(FRAMES):
+                    rr.render_frame(eye, rot, f)
+            ranks[1].pack_owned(buf.data_ptr())
+            ranks[1].synchronize()
+            ranks[0].unpack_rank(1, world, buf.data_ptr())
+            ranks[0].render_guides(eye, rot)
+            got.append(ranks[0].temporal_resolve(FRAMES))
+            ranks[0].temporal_commit()
+    finally:
+        for rr in ranks:
+            rr.close()
+    assert (want[1][..., 3] > FRAMES).sum() > 1000
+    for k in range(2):
+        assert np.array_equal(bits(got[k]), bits(want[k])), k
+
+
+# ------------------------------------------------------------------ display
+def _unorm8(x):
+    """round(clamp(x, 0, 1) * 255) as the display kernels compute it: one fused multiply-add
+    (exact in f64, then one rounding to f32), truncated."""
+    c = np.clip(np.nan_to_num(x.astype(F), nan=0.0), 0, 1).astype(np.float64)
+    return np.floor((c * 255.0 + 0.5).astype(F)).astype(np.uint8)
+
+
+@pytest.mark.parametrize("gamma", [0.0, 2.2])
+def test_display_resolved_is_pass3_of_the_resolved_image(gamma):
+    """Every pixel's pass3 tonemap of the resolved image (the GPU's own f32 tonemap, pt_tonemap of
+    that image uploaded as an accumulation) as an 8-bit unsigned-normalised RGBA pixel, alpha 255."""
+    w, h = 100, 76
+    with renderer("c2", w, h) as r:
+        render_camera(r, *camera("c2"))
+        r.temporal_resolve(FRAMES, download=False)
+        r.temporal_commit()
+        render_camera(r, *camera("c2", 2.0))
+        res = r.temporal_resolve(FRAMES)
+        img = device_plane(h, w, "uint8")
+        r.display_resolved(img.data_ptr(), 1.5, gamma)
+        r.synchronize()
+        r.set_accum(res)
+        t = r.tonemap(1.5, gamma)
+    got = img.cpu().numpy()
+    assert np.array_equal(got[..., :3], _unorm8(t)) and np.all(got[..., 3] == 255)
+
+
+# ------------------------------------------------------------------ the history drops
+def test_uploads_and_reset_drop_the_history():
+    w, h = 33, 31
+    cfg, tris, nodes, hdr = config("c2")
+    eye, rot = camera("c2")
+    with renderer("c2", w, h) as r:
+        drops = [r.temporal_reset, lambda: r.upload_scene(tris, nodes), lambda: r.upload_env(hdr)]
+        for k, drop in enumerate(drops):
+            render_camera(r, eye, rot)
+            r.temporal_resolve(FRAMES, download=False)
+            r.temporal_commit()
+            acc, g = render_camera(r, eye, rot)
+            assert (r.temporal_resolve(FRAMES)[..., 3] > FRAMES).any()  # there is a history
+            drop()
+            acc, g = render_camera(r, eye, rot)
+            got = r.temporal_resolve(FRAMES)
+            assert np.array_equal(bits(got[..., :3]), bits(acc[..., :3])) and np.all(got[..., 3] == FRAMES), k
+
+
+# ------------------------------------------------------------------ errors
+def rc_of(fn, *a, **kw):
+    with pytest.raises(PtError) as e:
+        fn(*a, **kw)
+    assert str(e.value).split(": ", 1)[1], "pt_last_error text"
+    return int(re.search(r"failed with (-?\d+)", str(e.value)).group(1))
+
+
+INVALID, NOSCENE = -1, -3
+
+
+def test_error_paths():
+    cfg, tris, nodes, hdr = config("c2")
+    eye, rot = camera("c2")
+    w, h = 33, 31
+    img = device_plane(h, w, "uint8")
+    out = device_plane(h, w)
+    with Renderer(w, h, "lambert") as r:
+        assert rc_of(r.temporal_resolve, 1) == NOSCENE
+        r.upload_scene(tris, nodes)
+        r.upload_env(hdr)
+        r.render_frame(eye, rot, 0)
+        assert rc_of(r.temporal_resolve, 1) == INVALID  # before any render_guides
+        r.render_guides(eye, rot)
+        for bad in (dict(frames=0), dict(frames=1, normal_cos=1.5), dict(frames=1, max_history=0.5),
+                    dict(frames=1, sigma_z=-0.01), dict(frames=1, normal_cos=-1.5)):
+            assert rc_of(r.temporal_resolve, **bad) == INVALID, bad
+        assert rc_of(r.temporal_commit) == INVALID  # the failed calls resolved nothing
+        assert rc_of(r.resolved_device_ptr) == INVALID
+        assert rc_of(r.display_resolved, img.data_ptr()) == INVALID
+        r.temporal_resolve(1, download=False)
+        r.display_resolved(img.data_ptr())
+        r.temporal_commit()
+        assert rc_of(r.temporal_commit) == INVALID  # no new resolve
+        r.temporal_resolve(1, download=False)
+        r.render_guides(eye, rot)
+        assert rc_of(r.temporal_commit) == INVALID  # the resolve was of the previous guides
+        # a resolve into a caller's buffer is not committed: the caller may overwrite that buffer
+        r.temporal_resolve(1, out.data_ptr())
+        assert rc_of(r.temporal_commit) == INVALID
+        r.temporal_resolve(1, download=False)
+        r.temporal_commit()
+        r.synchronize()
+    with Renderer(32, 32, "basic", basic_samples=1) as b:
+        b.upload_shapes(scenes.cornell_shapes())
+        assert rc_of(b.temporal_resolve, 1) == INVALID
+        assert rc_of(b.temporal_commit) == INVALID
+
+
+# ------------------------------------------------------------------ quality
+@pytest.mark.parametrize("name", ["c4", "c2"])
+def test_drag_gains_at_least_2_db_on_the_gpu(name):
+    """tests/test_temporal_ref.py's quality case with the GPU's own frames: 8 cameras 2 degrees
+    apart ending at the config's camera, 1 frame each at frameCounter 0, defaults; the last camera's
+    resolved image against its raw 1-spp image, by the 256-frame mean."""
+    w, h = 160, 90
+    with renderer(name, w, h) as r:
+        for k in range(8):
+            eye, rot = camera(name, -2.0 * (7 - k))
+            if k:
+                r.temporal_commit()
+            raw, g = render_camera(r, eye, rot, 1)
+            resolved = r.temporal_resolve(1)
+        only = r.denoise()
+        both = r.denoise(src_dptr=r.resolved_device_ptr())
+        r.render_frames(eye, rot, 1, 255)
+        r.synchronize()
+        clean = r.accum()
+    mask = dr.hit_mask(g)
+    p = [dr.psnr_tm(x, clean, mask) for x in (raw, resolved, only, both)]
+    print(f"{name}, 2 deg: raw 1 spp {p[0]:.2f} dB | resolved {p[1]:.2f} | a-trous only {p[2]:.2f} | "
+          f"resolved + a-trous {p[3]:.2f}")
+    assert p[1] - p[0] >= 2.0, (name, p)

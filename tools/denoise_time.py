@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Device time of the guide buffers, the a-trous passes and the denoised display on the GPU.
+"""Device time of the guide buffers, the a-trous passes, the denoised display and the temporal
+resolve on the GPU.
 
     python tools/denoise_time.py [c2 c4 ...] [--reps 100] [--out out/denoise_time.json]
 
@@ -13,6 +14,15 @@ repetitions after a warm-up, profiler off, each config at its own size (c2 / c4:
  * display: pt_display_denoised.
  * frame: wall time per iteration of pt_denoise (defaults) + pt_display_denoised + one synchronous
    pt_render_frame -- what a display() pays per presented frame (60 Hz: 16.6 ms).
+ * temporal: pt_temporal_resolve after a commit and a 1 degree camera move (new guides, 4 frames of
+   the new camera), 10 x reps repetitions, and its compulsory 112 B/pixel (6 planes read, 1 written:
+   232 MB at 1080p) over that time, against the HBM peak. Two things make that rate no HBM rate: the
+   7 planes fit the 256 MiB Infinity Cache, so back-to-back repetitions find them there (the a-trous
+   rows are measured the same way), and a miss pixel touches 48 B, not 112 (hit_share, and
+   temporal_touched_MB = (48 + 64 hit_share) B/pixel). temporal_cold: each repetition timed by its
+   own event pair after a read of a 1 GiB buffer has swept the caches (an event pair adds a few
+   microseconds). temporal_nohist: the call after pt_temporal_reset (a copy of the accumulation
+   with the count, 32 B/pixel).
 One JSON line per config.
 """
 from __future__ import annotations
@@ -26,6 +36,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 HBM_COPY_TBS = 6.29  # measured HBM copy rate
+HBM_PEAK_TBS = 8.0    # HBM3E peak of the MI355X
 
 
 def main():
@@ -90,6 +101,42 @@ def main():
             st1 = r.stats()
             res["render_frame_kernel_ms"] = (st1.kernel_ms_total - st0.kernel_ms_total) / a.reps
             res["fits_60hz"] = res["frame_wall_ms"] <= 1000.0 / 60.0
+            # the temporal resolve: the settled mean becomes the history, the camera moves 1 degree
+            r.temporal_resolve(frame, download=False)
+            r.temporal_commit()
+            angle, up, rad = cfg.camera
+            eye1, rot1 = orbit_camera(angle + 1.0, up, rad)
+            r.render_guides(eye1, rot1)
+            for f in range(4):
+                r.render_frame(eye1, rot1, f)
+            reps = a.reps
+            a.reps = 10 * reps  # a 30 us kernel: a longer window
+            res["temporal_ms"] = timed(lambda: r.temporal_resolve(4, download=False))
+            a.reps = reps
+            res["hit_share"] = float((r.guides()["tri"] >= 0).mean())
+            res["temporal_touched_MB"] = (48.0 + 64.0 * res["hit_share"]) * w * h / 1e6
+            res["temporal_GBs_touched"] = res["temporal_touched_MB"] / res["temporal_ms"]
+            sweep = torch.ones(1 << 28, dtype=torch.float32, device="cuda")  # 1 GiB, 4 x the Infinity Cache
+            torch.cuda.synchronize()
+            cold = 0.0
+            for _ in range(20):
+                with torch.cuda.stream(stream):
+                    sweep.sum()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                r.temporal_resolve(4, download=False)
+                e1.record(stream)
+                e1.synchronize()
+                cold += e0.elapsed_time(e1)
+            del sweep
+            res["temporal_cold_ms"] = cold / 20
+            res["temporal_cold_GBs_touched"] = res["temporal_touched_MB"] / res["temporal_cold_ms"]
+            res["temporal_MB_of_112B"] = 112.0 * w * h / 1e6
+            res["temporal_GBs_of_112B"] = 112.0 * w * h / (res["temporal_ms"] * 1e-3) / 1e9
+            res["hbm_peak_TBs"] = HBM_PEAK_TBS
+            res["temporal_share_of_hbm_peak"] = res["temporal_GBs_of_112B"] / (HBM_PEAK_TBS * 1e3)
+            r.temporal_reset()
+            res["temporal_nohist_ms"] = timed(lambda: r.temporal_resolve(4, download=False))
         line = json.dumps(res)
         print(line, flush=True)
         lines.append(line)
