@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 9  /* 2: in-process multi-GPU fields at the end of pt_config / pt_frame_stats;
+#define PT_ABI_VERSION 10 /* 2: in-process multi-GPU fields at the end of pt_config / pt_frame_stats;
                              3: scene-upload fields at the end of pt_frame_stats, pt_build_bvh_device;
                              4: BASIC shapes as doubles, its double image, the replayed random stream;
                              5: the displayed frame of a screen-tile split (pt_display_*);
@@ -38,7 +38,9 @@ extern "C" {
                                 pt_denoise, pt_display_denoised); no existing struct changes;
                              9: the running mean reprojected across camera moves (pt_temporal_resolve,
                                 pt_temporal_commit, pt_display_resolved) and pt_denoise_from; no existing
-                                struct changes */
+                                struct changes;
+                             10: per-pixel sample moments (PT_FLAG_MOMENTS, pt_download_moments) and the
+                                variance-guided filter (pt_denoise_var); no existing struct changes */
 
 /* error codes */
 #define PT_OK 0
@@ -76,6 +78,10 @@ extern "C" {
                                      of records) and the Lambert integrator on any scene default to */
 #define PT_FLAG_HOST_ACCEL 0x200u /* pt_upload_scene builds the runtime's own tree on the host (threaded binned
                                      SAH) instead of on the GPU (pt_build.hip) */
+#define PT_FLAG_MOMENTS 0x1000u   /* keep the running means of each sample's luminance and of its square beside
+                                     the running mean (pt_download_moments, pt_denoise_var); not with
+                                     PT_BASIC_CPU_COMPAT, PT_FLAG_COUNT_FETCHES, PT_FLAG_SERIAL_FRAMES,
+                                     tile_world > 1 or n_devices > 1 (pt_create: PT_E_INVALID) */
 
 /* in-process multi-GPU (pt_config.n_devices > 1) */
 #define PT_MAX_DEVICES 8
@@ -416,6 +422,73 @@ int pt_resolved_device_ptr(pt_ctx* ctx, void** dptr);
 int pt_download_resolved(pt_ctx* ctx, float* rgba);  /* host or device memory, width*height*4 f32; synchronous */
 /* pt_display_denoised of the last pt_temporal_resolve's image */
 int pt_display_resolved(pt_ctx* ctx, float limit, float gamma, void* dimage);
+
+/* Per-pixel sample moments. pt_denoise filters a converged image exactly as hard as a 1-spp one: nothing
+ * above knows how noisy a pixel still is. A PT_FLAG_MOMENTS context keeps, beside the running mean of
+ * the colour, the running means m1 and m2 of l and l l, l = (0.3 r + 0.6 g) + 0.1 b of each frame's
+ * sample colour (pt_tonemap's luminance), in a width x height plane of (m1, m2) pairs, row 0 = the
+ * bottom row, zero at creation. They take the accumulation's own weight: for frame frameCounter + f of a
+ * launch, w = 1 / (float)(frameCounter + f + 1), m1 = m1 (1 - w) + l w, m2 = m2 (1 - w) + (l l) w, each
+ * operation one IEEE f32 operation (tests/variance_ref.py restates it; the GPU equals it bit for bit),
+ * so frameCounter = 0 restarts them as it restarts the mean. The accumulation itself is bit for bit a
+ * plain context's. With sample_world > 1 the moments are of this context's own samples.
+ *
+ * The context counts the frames the moments hold: a launch with frameCounter == 0 sets the count to
+ * its frames, a launch whose frameCounter equals the count adds its frames, any other frameCounter
+ * sets it to 0 (not valid), and so do pt_upload_accum, pt_clear_accum (which also zeroes the plane),
+ * pt_upload_scene, pt_upload_env, pt_unpack_rank and pt_unpack_ranks. */
+int pt_moments_frames(pt_ctx* ctx, uint32_t* frames);  /* 0: not valid, or no PT_FLAG_MOMENTS */
+/* width*height*2 f32 into host or device memory, after the frames rendered so far; synchronous.
+ * PT_E_INVALID without PT_FLAG_MOMENTS. */
+int pt_download_moments(pt_ctx* ctx, float* m);
+int pt_moments_device_ptr(pt_ctx* ctx, void** dptr);   /* PT_E_INVALID without PT_FLAG_MOMENTS */
+
+/* The variance-guided a-trous filter (Schied et al. 2017, "Spatiotemporal Variance-Guided Filtering",
+ * its spatial part): pt_denoise's filter with the colour term replaced by a luminance term in units
+ * of each pixel's estimated standard deviation, so that it filters a noisy pixel hard and a converged
+ * one hardly at all. The filter is an exact sequence of IEEE f32 operations (correctly rounded sqrt,
+ * pt_fmath.h's exp; tests/variance_ref.py restates it; the GPU output equals it bit for bit). */
+typedef struct pt_denoise_var_params {
+  int   passes;        /* 1..8; pass i uses tap stride 2^i */
+  float sigma_l;       /* luminance term, in standard deviations, the same in every pass; <= 0: off */
+  float sigma_z;       /* as pt_denoise_params */
+  float sigma_a;       /* as pt_denoise_params */
+  int   normal_log2;   /* as pt_denoise_params */
+  float limit;         /* as pt_denoise_params */
+  int   min_temporal;  /* the moments are used once they hold this many frames; >= 2 */
+} pt_denoise_var_params;
+#define PT_DENOISE_VAR_PARAMS_SIZE 28 /* sizeof(pt_denoise_var_params), asserted by the library */
+
+void pt_denoise_var_defaults(pt_denoise_var_params* prm);  /* 5, 4.0, 0.02, 0.2, 6, 1.5, 8 */
+int pt_denoise_var_params_size(void);                      /* sizeof(pt_denoise_var_params) of the loaded library */
+
+/* Filters d_in_rgba (width*height*4 f32 device memory, e.g. pt_resolved_device_ptr; NULL = the
+ * accumulation; the aliasing rule of pt_denoise_from) into d_out_rgba, or with NULL into the context's
+ * denoised buffer: pt_denoised_device_ptr, pt_download_denoised and pt_display_denoised serve both
+ * filters. Needs valid guides, with pt_denoise's checks and error codes. prm NULL =
+ * pt_denoise_var_defaults. lum(c) = (0.3 r + 0.6 g) + 0.1 b, tm as in pt_denoise, max(x, y) = x > y ? x : y,
+ * kf = (float)pt_moments_frames.
+ * Step A, the variance v of the input's tone-mapped luminance, 0 at a miss pixel:
+ *   kf >= min_temporal:  L = lum(c_p);  q = 1 + L / limit;  gd = 1 / (q q) (the tonemap's slope);
+ *                        n_p = max(c_p.w, kf) (the accumulation's .w is 1, a resolved image's its sample
+ *                        count);  v = (max(m2 - m1 m1, 0) / n_p) (gd gd)
+ *   else, or without PT_FLAG_MOMENTS (rank 0 of a tile split; during a drag): over the 7 x 7 window
+ *                        around p (dy outer, dx inner, -3..3) the pixels q inside the image that are hits:
+ *                        l_q = lum(tm(c_q));  s1 += l_q;  s2 += l_q l_q;  cnt += 1;
+ *                        v = max(s2 / cnt - (s1 / cnt) (s1 / cnt), 0)
+ * Step B, pass i = 0 .. passes-1 (stride s = 2^i, inputs c and v, l = lum(tm(c))): a miss pixel copies c
+ * and v; a hit pixel p takes
+ *   vt_p = sum(v_q g) / sum(g) over its 3 x 3 neighbours q (dy outer, dx inner, -1..1) inside the image
+ *          that are hits, g = G[|dx|] G[|dy|], G = {0.5, 0.25};   lden = sigma_l sqrt(vt_p) + 1e-6
+ *   and the 25 taps q = p + s (dx, dy) of pt_denoise, with its k and n:
+ *   a = |Np.(Pq - Pp)| / (sigma_z t_p) + |l_q - l_p| / lden + |Aq - Ap|^2 / sigma_a^2;   w = (k n) exp(-a);
+ *   out.rgb = sum(c_q w) / sum(w),  v_out = sum(v_q (w w)) / (sum(w) sum(w))  (c_p.rgb and v_p when
+ *   sum(w) is not > 0),  out.w = c_p.w.
+ * Asynchronous, on the context's stream, after the frames rendered so far. */
+int pt_denoise_var(pt_ctx* ctx, const pt_denoise_var_params* prm, const void* d_in_rgba, void* d_out_rgba);
+/* Test hook: step A's plane of the last pt_denoise_var, width*height f32 into host or device memory;
+ * synchronous. PT_E_INVALID before one. */
+int pt_download_variance(pt_ctx* ctx, float* v);
 
 /* Stream interop: render on the caller's HIP stream (e.g. torch's current
  * stream). NULL restores the context's own stream. */

@@ -13,10 +13,11 @@ from . import _build
 
 _lib = None
 
-ABI_VERSION = 9  # include/pt_abi.h PT_ABI_VERSION
+ABI_VERSION = 10  # include/pt_abi.h PT_ABI_VERSION
 # an older tuning build (tools/tune.py A/B against a previous round's library) loads when its structs
-# match: ABI 7 only added pt_unpack_ranks, ABI 8 the guide buffers and the denoiser and ABI 9 the
-# temporal resolve, which such a build does not have
+# match: ABI 7 only added pt_unpack_ranks, ABI 8 the guide buffers and the denoiser, ABI 9 the
+# temporal resolve and ABI 10 the sample moments and the variance-guided filter, which such a build
+# does not have
 ABI_STRUCTS_SINCE = 6
 c_float_p = C.POINTER(C.c_float)
 c_double_p = C.POINTER(C.c_double)
@@ -57,6 +58,14 @@ class PtDenoiseParams(C.Structure):
     _fields_ = [
         ("passes", C.c_int), ("sigma_c", C.c_float), ("sigma_z", C.c_float), ("sigma_a", C.c_float),
         ("normal_log2", C.c_int), ("limit", C.c_float),
+    ]
+
+
+class PtDenoiseVarParams(C.Structure):
+    """pt_denoise_var_params (include/pt_abi.h): PT_DENOISE_VAR_PARAMS_SIZE bytes."""
+    _fields_ = [
+        ("passes", C.c_int), ("sigma_l", C.c_float), ("sigma_z", C.c_float), ("sigma_a", C.c_float),
+        ("normal_log2", C.c_int), ("limit", C.c_float), ("min_temporal", C.c_int),
     ]
 
 
@@ -121,6 +130,13 @@ SIGNATURES = {
     "pt_resolved_device_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "pt_download_resolved": (C.c_int, [C.c_void_p, c_float_p]),
     "pt_display_resolved": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
+    "pt_moments_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "pt_download_moments": (C.c_int, [C.c_void_p, c_float_p]),
+    "pt_moments_device_ptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "pt_denoise_var_defaults": (None, [C.POINTER(PtDenoiseVarParams)]),
+    "pt_denoise_var_params_size": (C.c_int, []),
+    "pt_denoise_var": (C.c_int, [C.c_void_p, C.POINTER(PtDenoiseVarParams), C.c_void_p, C.c_void_p]),
+    "pt_download_variance": (C.c_int, [C.c_void_p, c_float_p]),
     "pt_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pt_synchronize": (C.c_int, [C.c_void_p]),
     "pt_get_stats": (C.c_int, [C.c_void_p, C.POINTER(PtFrameStats)]),

@@ -196,6 +196,14 @@ __device__ __forceinline__ void stStream(float4* p, float4 v) {
   *p = v;
 #endif
 }
+__device__ __forceinline__ void stStream(float2* p, float2 v) {
+#if PT_NT_STREAM
+  const f32x2_t x = {v.x, v.y};
+  __builtin_nontemporal_store(x, reinterpret_cast<f32x2_t*>(p));
+#else
+  *p = v;
+#endif
+}
 
 // GL_NEAREST + GL_CLAMP_TO_EDGE addressing (OpenglRayTracing/main.cpp:184-194): the texel of (u, v)
 __device__ __forceinline__ void texXY(int w, int h, float u, float v, int& x, int& y) {
@@ -634,6 +642,18 @@ __device__ __forceinline__ V3 tonemapPixel(float4 c, float limit, float gamma) {
     b = ptm_powf(b, 1.0f / gamma);
   }
   return v3(r, g, b);
+}
+
+// pack (unpack) the pixels of shard tiles t % world == rank in (tile, row, col) order
+__device__ __forceinline__ bool packedPixel(const PackParams& p, long k, int& px, int& py) {
+  const long perTile = (long)p.shardSize * p.shardSize;
+  long j = k / perTile;
+  int within = (int)(k - j * perTile);
+  long g = j * p.world + p.rank;
+  int gy = (int)(g / p.shardsX), gx = (int)(g - (long)gy * p.shardsX);
+  px = gx * p.shardSize + within % p.shardSize;
+  py = gy * p.shardSize + within / p.shardSize;
+  return px < p.width && py < p.height;
 }
 
 }  // namespace pt

@@ -444,6 +444,42 @@ constexpr int ATROUS_TILE = 16;     // a block's 16 x 16 output pixels
 constexpr int ATROUS_LDS_STRIDE = 2;  // passes of stride <= this stage their tile + halo in LDS
 hipError_t launchAtrousTm(const float4* in, float4* tm, int n, float limit, hipStream_t s);
 hipError_t launchAtrous(const AtrousParams& p, hipStream_t s);
+// The variance-guided a-trous filter (pt_variance.hip, pt_abi.h pt_denoise_var). launchVarLum writes
+// l = lum(tm(in)) per pixel; launchVarInit (step A) the initial variance, to var0 and, beside l, to the
+// first pass's (l, v) plane: from the sample moments (non-null) or from l's 7 x 7 window.
+struct VarInitParams {
+  int width, height;
+  const float4* in;
+  const float4* nrmTri;
+  const float2* moments;     // (m1, m2) of the sample luminance; null: the spatial estimate
+  const float* lum;
+  float* var0;
+  float2* lv;
+  float kf;                  // (float)frames the moments hold
+  float limit;
+};
+// One launch per pass: reads the colour `in` and its (l, v) plane `lvIn`, writes `out` and, for the
+// next pass, (lum(tm(out)), v_out) to `lvOut` (null on the last pass).
+struct AtrousVarParams {
+  int width, height;
+  int stride;                // 2^pass
+  const float4* in;
+  const float2* lvIn;
+  const float4* posT;
+  const float4* nrmTri;
+  const float4* albedo;
+  float4* out;
+  float2* lvOut;
+  float sigmaL;              // <= 0: term off
+  float sigmaZ;              // <= 0: term off
+  float albDen;              // sigma_a^2
+  int albOn;
+  int normalLog2;            // -1: term off
+  float limit;
+};
+hipError_t launchVarLum(const float4* in, float* lum, int n, float limit, hipStream_t s);
+hipError_t launchVarInit(const VarInitParams& p, hipStream_t s);
+hipError_t launchAtrousVar(const AtrousVarParams& p, hipStream_t s);
 // The temporal resolve (pt_temporal.hip): the running mean `accum` blended, weighted by sample count,
 // with the previous camera's resolved image `hist` fetched through the current first-hit positions
 // (pt_abi.h pt_temporal_resolve). hist null: no history (out = accum's rgb, count `frames`).
@@ -484,5 +520,9 @@ hipError_t launchUnpack(const PackParams& p, float4* accum, const float* packed,
 // 1 / (frameCounter + f + 1)) (IS:868-871, pass2.fsh:15) -- each pixel read and written once
 hipError_t launchMix(const PackParams& p, float4* accum, const float* col, size_t colStride, int nFrames,
                      uint32_t frameCounter, hipStream_t s);
+// launchMix of a PT_FLAG_MOMENTS context (pt_moments.hip): the same update of accum, and with the same
+// weights the running means (m1, m2) of each sample's luminance l and of l * l in `moments`
+hipError_t launchMixMoments(const PackParams& p, float4* accum, float2* moments, const float* col, size_t colStride,
+                            int nFrames, uint32_t frameCounter, hipStream_t s);
 
 }  // namespace pt

@@ -965,17 +965,7 @@ __device__ __forceinline__ uint32_t unorm8(float x) {
   return (uint32_t)__builtin_fmaf(c, 255.0f, 0.5f);
 }
 
-// pack (unpack) the pixels of shard tiles t % world == rank in (tile, row, col) order
-__device__ __forceinline__ bool packedPixel(const PackParams& p, long k, int& px, int& py) {
-  const long perTile = (long)p.shardSize * p.shardSize;
-  long j = k / perTile;
-  int within = (int)(k - j * perTile);
-  long g = j * p.world + p.rank;
-  int gy = (int)(g / p.shardsX), gx = (int)(g - (long)gy * p.shardsX);
-  px = gx * p.shardSize + within % p.shardSize;
-  py = gy * p.shardSize + within / p.shardSize;
-  return px < p.width && py < p.height;
-}
+// (packedPixel: pt_device.h, shared with pt_moments.hip)
 // packed slots are (r, g, b): the running mean's alpha is 1 for every rendered pixel
 // (IS:868-871 writes vec4(color, 1)), so the gather moves 12 bytes per pixel, not 16
 __global__ void packKernel(PackParams p, const float4* accum, float* packed) {

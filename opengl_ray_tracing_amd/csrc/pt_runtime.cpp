@@ -243,6 +243,15 @@ struct pt_ctx {
   bool histValid = false;
   int histSet = 0, histRes = 0;    // the history's guide set and resolved plane
   float histEye[3] = {}, histCam[16] = {};
+  // PT_FLAG_MOMENTS: the running means (m1, m2) of the sample luminance beside the running mean of
+  // the colour (mixMomentsKernel), and the frames they hold (0: not valid, see noteMoments)
+  float2* d_mom = nullptr;
+  uint32_t momFrames = 0;
+  // pt_denoise_var: l = lum(tm(input)), step A's variance, the passes' two (l, v) planes
+  float* d_lum = nullptr;
+  float* d_var0 = nullptr;
+  float2* d_lv[2] = {};
+  bool varianceValid = false;  // d_var0 holds the last pt_denoise_var's step A
   // in-process multi-GPU (pt_config.n_devices > 1): this context renders as
   // screen-tile rank 0 on device_ids[0] and owns the other ranks' contexts and
   // the per-frame gather of their tiles into its accumulation
@@ -419,6 +428,10 @@ static int createOne(pt_ctx** out, const pt_config* cfg) {
   const size_t npix = (size_t)cfg->width * cfg->height;
   CKC(hipMalloc(&ctx->d_accum, npix * sizeof(float4)));
   CKC(hipMemset(ctx->d_accum, 0, npix * sizeof(float4)));
+  if (cfg->flags & PT_FLAG_MOMENTS) {
+    CKC(hipMalloc(&ctx->d_mom, npix * sizeof(float2)));
+    CKC(hipMemset(ctx->d_mom, 0, npix * sizeof(float2)));
+  }
   CKC(hipMalloc(&ctx->d_ctl, CTL_BYTES));
   CKC(hipMemset(ctx->d_ctl, 0, CTL_BYTES));
   ctx->shardsX = (cfg->width + ss - 1) / ss;
@@ -481,6 +494,20 @@ int pt_create(pt_ctx** out, const pt_config* cfg) {
     g_create_err = "pt_create: n_devices must be 0..8 and gather a PT_GATHER_* value";
     return PT_E_INVALID;
   }
+  if (cfg->flags & PT_FLAG_MOMENTS) {
+    // the moments are collected from the pipelined frames' colour buffer, which these do not have,
+    // and are this context's own: gathering them across ranks is not part of the library yet
+    const char* why = nullptr;
+    if (cfg->integrator == PT_BASIC_CPU_COMPAT) why = "PT_BASIC_CPU_COMPAT";
+    else if (cfg->flags & PT_FLAG_COUNT_FETCHES) why = "PT_FLAG_COUNT_FETCHES";
+    else if (cfg->flags & PT_FLAG_SERIAL_FRAMES) why = "PT_FLAG_SERIAL_FRAMES";
+    else if (cfg->tile_world > 1) why = "tile_world > 1";
+    else if (n > 1) why = "n_devices > 1";
+    if (why) {
+      g_create_err = std::string("pt_create: PT_FLAG_MOMENTS cannot be combined with ") + why;
+      return PT_E_INVALID;
+    }
+  }
   if (n <= 1) return createOne(out, cfg);
   if (cfg->tile_world > 1 || cfg->sample_world > 1 || cfg->integrator == PT_BASIC_CPU_COMPAT) {
     g_create_err = "pt_create: n_devices > 1 renders screen tiles of the GL integrators itself "
@@ -533,6 +560,7 @@ void pt_destroy(pt_ctx* ctx) {
   dfree(ctx->d_guide[2]);
   for (auto& set : ctx->d_guidePN) for (auto& g : set) dfree(g);
   dfree(ctx->d_res[0]); dfree(ctx->d_res[1]);
+  dfree(ctx->d_mom); dfree(ctx->d_lum); dfree(ctx->d_var0); dfree(ctx->d_lv[0]); dfree(ctx->d_lv[1]);
   dfree(ctx->d_guideOvf); dfree(ctx->d_dn[0]); dfree(ctx->d_dn[1]); dfree(ctx->d_dnTm[0]); dfree(ctx->d_dnTm[1]);
   freePrimaryBins(ctx->bins);
   for (int k = 0; k < PIPE; k++) {
@@ -979,10 +1007,15 @@ static void dropHistory(pt_ctx* ctx) {
   ctx->resolvedFresh = false;
 }
 
+// the sample moments no longer describe the accumulation (it was replaced, or the scene or the
+// light its samples saw): invalid until a launch restarts them at frameCounter 0
+static void dropMoments(pt_ctx* ctx) { ctx->momFrames = 0; }
+
 static int uploadScene(pt_ctx* ctx, const float* tris, const SceneHost& h) {
   if (int rc = syncStreams(ctx)) return rc;  // no frame in flight reads the buffers replaced here
   ctx->policyKey++;  // the tree / split policies are measured again at the next restart
   dropHistory(ctx);
+  dropMoments(ctx);
   CK(hipSetDevice(ctx->cfg.device_id));
   int rc;
   if ((rc = upload(ctx, &ctx->d_pairs, h.pairs)) || (rc = upload(ctx, &ctx->d_geo, h.geo)) ||
@@ -1305,6 +1338,7 @@ static int envOne(pt_ctx* ctx, const float* hdr, int w, int h, const float* cach
 int pt_upload_env(pt_ctx* ctx, const float* hdr, int w, int h, const float* cache) {
   if (!ctx) return PT_E_INVALID;
   dropHistory(ctx);
+  dropMoments(ctx);
   if (ctx->peers.empty()) return envOne(ctx, hdr, w, h, cache);
   // a device group computes calculateHdrCache once (on rank 0's GPU) and uploads it everywhere
   std::vector<float> own;
@@ -1856,7 +1890,8 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
   // -- no colour buffer round trip and no running-mean update launch: c4 per call 0.785 -> 0.772 ms.
   // The regen kernel keeps the update launch: the read of the running mean at each path's end stalls
   // its lock-step waves (c2 0.455 either way, c3 0.578 -> 0.587 ms)
-  const bool direct = piped && solo && nF == 1 && !regen && PT_DIRECT_SOLO;
+  // A PT_FLAG_MOMENTS context never does: its samples pass through the colour buffer to mixMomentsKernel.
+  const bool direct = piped && solo && nF == 1 && !regen && PT_DIRECT_SOLO && !ctx->d_mom;
   if (direct && ctx->mixPending && ctx->lastMixStream != S) CK(hipStreamWaitEvent(S, ctx->mixDone[ctx->lastCol], 0));
   p.sampleStride = c.sample_world > 0 ? (uint32_t)c.sample_world : 1u;
   // per-frame buffers indexed by the pixel's slot in this context's share (shareIndex): a 1/N share's
@@ -2015,7 +2050,12 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
     if (ctx->mixPending && ctx->lastMixStream != ctx->stream)  // the caller switched streams: keep frame order
       CK(hipStreamWaitEvent(ctx->stream, ctx->mixDone[ctx->lastCol], 0));
     ctx->lastMixStream = ctx->stream;
-    if (!direct)
+    if (ctx->d_mom) {
+      CK(launchMixMoments(packParams(ctx, c.tile_rank, c.tile_world), ctx->d_accum, ctx->d_mom, ctx->d_col[colIdx],
+                          shareN, nF, frameCounter, ctx->stream));
+      // the frames the moments hold: a restart, a continuation, or a gap (not valid)
+      ctx->momFrames = frameCounter == 0 ? (uint32_t)nF : (frameCounter == ctx->momFrames ? ctx->momFrames + (uint32_t)nF : 0u);
+    } else if (!direct)
       CK(launchMix(packParams(ctx, c.tile_rank, c.tile_world), ctx->d_accum, ctx->d_col[colIdx], shareN, nF,
                    frameCounter, ctx->stream));
     CK(hipEventRecord(ctx->mixDone[colIdx], ctx->stream));  // direct: the frame's kernels updated it
@@ -2177,6 +2217,7 @@ int pt_upload_basic_image(pt_ctx* ctx, const double* rgb) {
 int pt_upload_accum(pt_ctx* ctx, const float* accum) {
   if (!ctx || !accum) return PT_E_INVALID;
   if (int rc = joinGather(ctx)) return rc;
+  dropMoments(ctx);
   for (pt_ctx* m : members(ctx))
     if (int rc = uploadAccumOne(m, accum)) return fromPeer(ctx, m, rc);
   return PT_OK;
@@ -2193,6 +2234,10 @@ int pt_clear_accum(pt_ctx* ctx) {
     if (m->d_basicImg &&
         hipMemsetAsync(m->d_basicImg, 0, (size_t)m->cfg.width * m->cfg.height * 3 * sizeof(double), m->stream) != hipSuccess)
       return fail(ctx, PT_E_HIP, "pt_clear_accum (BASIC image)");
+    dropMoments(m);
+    if (m->d_mom &&
+        hipMemsetAsync(m->d_mom, 0, (size_t)m->cfg.width * m->cfg.height * sizeof(float2), m->stream) != hipSuccess)
+      return fail(ctx, PT_E_HIP, "pt_clear_accum (moments)");
   }
   // a group's next gather unpacks into rank 0's accumulation on the gather stream, which
   // is not ordered after rank 0's stream: the clear completes first
@@ -2470,6 +2515,125 @@ int pt_display_denoised(pt_ctx* ctx, float limit, float gamma, void* dimage) {
   return PT_OK;
 }
 
+// ------------------------------------------------------------ sample moments and the variance-guided filter
+static_assert(sizeof(pt_denoise_var_params) == PT_DENOISE_VAR_PARAMS_SIZE, "pt_denoise_var_params layout");
+
+int pt_moments_frames(pt_ctx* ctx, uint32_t* frames) {
+  if (!ctx || !frames) return PT_E_INVALID;
+  *frames = ctx->d_mom ? ctx->momFrames : 0u;
+  return PT_OK;
+}
+
+int pt_download_moments(pt_ctx* ctx, float* m) {
+  if (!ctx || !m) return PT_E_INVALID;
+  if (!ctx->d_mom) return fail(ctx, PT_E_INVALID, "pt_download_moments: not a PT_FLAG_MOMENTS context");
+  if (int rc = joinPipe(ctx)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const size_t bytes = (size_t)ctx->cfg.width * ctx->cfg.height * sizeof(float2);
+  CK(hipMemcpyAsync(m, ctx->d_mom, bytes, hipMemcpyDefault, ctx->stream));  // host or device
+  CK(hipStreamSynchronize(ctx->stream));
+  return PT_OK;
+}
+
+int pt_moments_device_ptr(pt_ctx* ctx, void** dptr) {
+  if (!ctx || !dptr) return PT_E_INVALID;
+  if (!ctx->d_mom) return fail(ctx, PT_E_INVALID, "pt_moments_device_ptr: not a PT_FLAG_MOMENTS context");
+  *dptr = ctx->d_mom;
+  return PT_OK;
+}
+
+void pt_denoise_var_defaults(pt_denoise_var_params* prm) {
+  if (!prm) return;
+  prm->passes = 5;
+  prm->sigma_l = 4.0f;
+  prm->sigma_z = 0.02f;
+  prm->sigma_a = 0.2f;
+  prm->normal_log2 = 6;
+  prm->limit = 1.5f;
+  prm->min_temporal = 8;
+}
+
+int pt_denoise_var_params_size(void) { return (int)sizeof(pt_denoise_var_params); }
+
+int pt_denoise_var(pt_ctx* ctx, const pt_denoise_var_params* prm, const void* d_in_rgba, void* d_out_rgba) {
+  if (!ctx) return PT_E_INVALID;
+  if (int rc = guidesReady(ctx, "pt_denoise_var")) return rc;
+  pt_denoise_var_params P;
+  pt_denoise_var_defaults(&P);
+  if (prm) P = *prm;
+  if (P.passes < 1 || P.passes > 8) return fail(ctx, PT_E_INVALID, "pt_denoise_var: passes must be 1..8");
+  if (P.normal_log2 < -1 || P.normal_log2 > 10)
+    return fail(ctx, PT_E_INVALID, "pt_denoise_var: normal_log2 must be -1..10");
+  if (!(P.limit > 0.0f)) return fail(ctx, PT_E_INVALID, "pt_denoise_var: limit must be > 0");
+  if (P.min_temporal < 2) return fail(ctx, PT_E_INVALID, "pt_denoise_var: min_temporal must be >= 2");
+  // the passes ping-pong through the context's two planes, as pt_denoise_from's
+  if (d_in_rgba && (d_in_rgba == d_out_rgba || d_in_rgba == ctx->d_dn[0] || d_in_rgba == ctx->d_dn[1]))
+    return fail(ctx, PT_E_INVALID, "pt_denoise_var: the input must not be the output or the context's denoised buffer");
+  // the accumulation and the moments as the frames rendered so far leave them
+  if (int rc = joinGather(ctx)) return rc;
+  if (int rc = joinPipe(ctx)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const int W = ctx->cfg.width, H = ctx->cfg.height;
+  const size_t npix = (size_t)W * H;
+  for (int k = 0; k < 2; k++) {
+    if (!ctx->d_dn[k]) CK(hipMalloc(&ctx->d_dn[k], npix * sizeof(float4)));
+    if (!ctx->d_lv[k]) CK(hipMalloc(&ctx->d_lv[k], npix * sizeof(float2)));
+  }
+  if (!ctx->d_lum) CK(hipMalloc(&ctx->d_lum, npix * sizeof(float)));
+  if (!ctx->d_var0) CK(hipMalloc(&ctx->d_var0, npix * sizeof(float)));
+  const float4* in = d_in_rgba ? reinterpret_cast<const float4*>(d_in_rgba) : ctx->d_accum;
+  CK(launchVarLum(in, ctx->d_lum, (int)npix, P.limit, ctx->stream));
+  // step A: from the moments once they hold min_temporal frames, else (or without them) spatial
+  const float kf = ctx->d_mom ? (float)ctx->momFrames : 0.0f;
+  VarInitParams v;
+  v.width = W;
+  v.height = H;
+  v.in = in;
+  v.nrmTri = ctx->d_guide[1];
+  v.moments = ctx->d_mom && kf >= (float)P.min_temporal ? ctx->d_mom : nullptr;
+  v.lum = ctx->d_lum;
+  v.var0 = ctx->d_var0;
+  v.lv = ctx->d_lv[0];
+  v.kf = kf;
+  v.limit = P.limit;
+  CK(launchVarInit(v, ctx->stream));
+  ctx->varianceValid = true;
+  AtrousVarParams a;
+  a.width = W;
+  a.height = H;
+  a.posT = ctx->d_guide[0];
+  a.nrmTri = ctx->d_guide[1];
+  a.albedo = ctx->d_guide[2];
+  a.sigmaL = P.sigma_l;
+  a.sigmaZ = P.sigma_z;
+  a.albDen = P.sigma_a * P.sigma_a;
+  a.albOn = P.sigma_a > 0.0f;
+  a.normalLog2 = P.normal_log2;
+  a.limit = P.limit;
+  for (int i = 0; i < P.passes; i++) {
+    const bool last = i == P.passes - 1;
+    a.stride = 1 << i;
+    a.in = in;
+    a.lvIn = ctx->d_lv[i & 1];
+    a.out = last && d_out_rgba ? reinterpret_cast<float4*>(d_out_rgba) : ctx->d_dn[i & 1];
+    a.lvOut = last ? nullptr : ctx->d_lv[(i + 1) & 1];
+    CK(launchAtrousVar(a, ctx->stream));
+    in = a.out;
+  }
+  ctx->denoised = in;
+  return PT_OK;
+}
+
+int pt_download_variance(pt_ctx* ctx, float* v) {
+  if (!ctx || !v) return PT_E_INVALID;
+  if (!ctx->varianceValid) return fail(ctx, PT_E_INVALID, "pt_download_variance: no pt_denoise_var yet");
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const size_t bytes = (size_t)ctx->cfg.width * ctx->cfg.height * sizeof(float);
+  CK(hipMemcpyAsync(v, ctx->d_var0, bytes, hipMemcpyDefault, ctx->stream));  // host or device
+  CK(hipStreamSynchronize(ctx->stream));
+  return PT_OK;
+}
+
 // ------------------------------------------------------------ the temporal resolve
 static_assert(sizeof(pt_temporal_params) == PT_TEMPORAL_PARAMS_SIZE, "pt_temporal_params layout");
 
@@ -2597,6 +2761,7 @@ int pt_unpack_ranks(pt_ctx* ctx, int world, const void* const* dpacked) {
     d.count[k] = packParams(ctx, k, world).count;
   }
   CK(launchUnpackRanks(d, world, ctx->d_accum, ctx->stream));
+  dropMoments(ctx);
   return PT_OK;
 }
 
@@ -2607,6 +2772,7 @@ int pt_unpack_rank(pt_ctx* ctx, int rank, int world, const void* dpacked) {
   CK(hipSetDevice(ctx->cfg.device_id));
   PackParams p = packParams(ctx, rank, world);
   CK(launchUnpack(p, ctx->d_accum, reinterpret_cast<const float*>(dpacked), ctx->stream));
+  dropMoments(ctx);
   return PT_OK;
 }
 

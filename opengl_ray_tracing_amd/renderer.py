@@ -37,6 +37,7 @@ FLAG_NO_BINS = 0x100
 FLAG_HOST_ACCEL = 0x200
 FLAG_MEGAKERNEL = 0x400
 FLAG_PRIMARY_PASS = 0x800
+FLAG_MOMENTS = 0x1000
 GATHER = {"auto": 0, "copy": 1, "rccl": 2}
 
 
@@ -83,8 +84,9 @@ class Renderer:
     def __init__(self, width: int, height: int, integrator="lambert", max_bounce: int = -1, device: int = 0,
                  tile_rank: int = 0, tile_world: int = 1, tile_size: int = 32, flags: int = 0,
                  basic_samples: int = 128, basic_seed: int = 0, sample_rank: int = 0, sample_world: int = 1,
-                 devices=None, gather="auto", frame_batch: int = 0):
-        """devices: a list of HIP device ids (2..8, repeats allowed) makes this one context render
+                 devices=None, gather="auto", frame_batch: int = 0, moments: bool = False):
+        """moments: keep the per-pixel sample moments beside the running mean (PT_FLAG_MOMENTS:
+        moments(), moments_frames(), and denoise_var()'s variance from them). devices: a list of HIP device ids (2..8, repeats allowed) makes this one context render
         screen tiles on all of them and gather them into the first device's accumulation every
         frame (pt_config.n_devices; gather "auto" / "copy" / "rccl"). frame_batch: most frames per
         launch of render_frames (0 = automatic: 2 x tile_world frames; tile_world on large Disney/MIS
@@ -96,7 +98,7 @@ class Renderer:
         cfg.max_bounce = int(max_bounce)
         cfg.device_id = int(device)
         cfg.tile_rank, cfg.tile_world, cfg.tile_size = int(tile_rank), int(tile_world), int(tile_size)
-        cfg.flags = int(flags)
+        cfg.flags = int(flags) | (FLAG_MOMENTS if moments else 0)
         cfg.basic_samples = int(basic_samples)
         cfg.basic_seed = int(basic_seed) & 0xFFFFFFFF
         cfg.sample_rank, cfg.sample_world = int(sample_rank), int(sample_world)
@@ -350,6 +352,53 @@ class Renderer:
         """The last denoise()'s image through the 8-bit display path into an H x W x 4 u8 device image."""
         self._ck(self._lib.pt_display_denoised(self._h, float(limit), float(gamma), C.c_void_p(dimage)),
                  "pt_display_denoised")
+
+    def moments(self) -> np.ndarray:
+        """The running means (m1, m2) of the sample luminance and of its square, (h, w, 2), row 0 =
+        bottom (pt_download_moments; a Renderer(..., moments=True))."""
+        out = np.empty((self.height, self.width, 2), np.float32)
+        self._ck(self._lib.pt_download_moments(self._h, _fp(out)), "pt_download_moments")
+        return out
+
+    def moments_frames(self) -> int:
+        """The frames the moments hold; 0 when they are not valid or the context keeps none."""
+        n = C.c_uint32()
+        self._ck(self._lib.pt_moments_frames(self._h, C.byref(n)), "pt_moments_frames")
+        return n.value
+
+    def moments_device_ptr(self) -> int:
+        p = C.c_void_p()
+        self._ck(self._lib.pt_moments_device_ptr(self._h, C.byref(p)), "pt_moments_device_ptr")
+        return p.value
+
+    def denoise_var(self, out_dptr: int | None = None, download: bool = True, src_dptr: int | None = None, **params):
+        """The variance-guided a-trous filter (pt_denoise_var) of the accumulation -- or, with
+        src_dptr, of an H x W x 4 f32 device image such as resolved_device_ptr() -- steered by the
+        last render_guides and by the sample moments (a Renderer(..., moments=True) that holds
+        min_temporal frames; else by a spatial variance estimate). params: passes, sigma_l, sigma_z,
+        sigma_a, normal_log2, limit, min_temporal (defaults: pt_denoise_var_defaults). Returns as
+        denoise() does; the image is the context's denoised image (denoised_device_ptr,
+        display_denoised)."""
+        prm = _native.PtDenoiseVarParams()
+        self._lib.pt_denoise_var_defaults(C.byref(prm))
+        for k, v in params.items():
+            if k not in ("passes", "sigma_l", "sigma_z", "sigma_a", "normal_log2", "limit", "min_temporal"):
+                raise TypeError(f"denoise_var() has no parameter {k!r}")
+            setattr(prm, k, int(v) if k in ("passes", "normal_log2", "min_temporal") else float(v))
+        out_p = C.c_void_p(out_dptr) if out_dptr else None
+        self._ck(self._lib.pt_denoise_var(self._h, C.byref(prm), C.c_void_p(src_dptr) if src_dptr else None, out_p),
+                 "pt_denoise_var")
+        if out_dptr or not download:
+            return None
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(self._lib.pt_download_denoised(self._h, _fp(out)), "pt_download_denoised")
+        return out
+
+    def variance(self) -> np.ndarray:
+        """The initial variance plane (h, w) of the last denoise_var (pt_download_variance)."""
+        out = np.empty((self.height, self.width), np.float32)
+        self._ck(self._lib.pt_download_variance(self._h, _fp(out)), "pt_download_variance")
+        return out
 
     def temporal_resolve(self, frames: int, out_dptr: int | None = None, download: bool = True, **params):
         """The running mean of `frames` frames (frameCounter + 1) blended with the committed history

@@ -23,6 +23,15 @@ repetitions after a warm-up, profiler off, each config at its own size (c2 / c4:
    own event pair after a read of a 1 GiB buffer has swept the caches (an event pair adds a few
    microseconds). temporal_nohist: the call after pt_temporal_reset (a copy of the accumulation
    with the count, 32 B/pixel).
+ * atrous / var / var_spatial _pass_ms_by_stride: pt_denoise and pt_denoise_var (variance from the
+   moments, and the spatial estimate) pass by pass in one more context of the same process that
+   holds 32 frames of moments, and var_over_atrous_by_stride, their ratio per stride ([1] includes
+   what precedes the first pass: one tone-mapped plane there, the luminance plane and step A here).
+ * batch12 / single _launch_ms_plain / _moments: a 12-frame and a 1-frame launch (frame kernel and
+   running-mean update, back to back on one stream) of a plain and of a PT_FLAG_MOMENTS context;
+   single_call_wall_ms_*: a synchronous pt_render_frame each. The kernels' own times (mixKernel,
+   mixMomentsKernel, varLumKernel, varInitKernel, atrousVarKernel) come from running this script
+   under rocprofv3 --kernel-trace --stats.
 One JSON line per config.
 """
 from __future__ import annotations
@@ -137,6 +146,56 @@ def main():
             res["temporal_share_of_hbm_peak"] = res["temporal_GBs_of_112B"] / (HBM_PEAK_TBS * 1e3)
             r.temporal_reset()
             res["temporal_nohist_ms"] = timed(lambda: r.temporal_resolve(4, download=False))
+        # the variance-guided filter against pt_denoise, and the running-mean update with the sample
+        # moments against the plain one: two contexts in this same process
+        ctxs = {}
+        for key, moments in (("plain", False), ("moments", True)):
+            q = Renderer(w, h, cfg.integrator, max_bounce=cfg.max_bounce, frame_batch=12, moments=moments)
+            q.upload_scene(tris, nodes)
+            q.upload_env(hdr)
+            q.set_stream(stream.cuda_stream)
+            for f in range(32):  # past the policy probe; the moments hold 32 frames
+                q.render_frame(eye, rot, f)
+            q.render_guides(eye, rot)
+            q.synchronize()
+            ctxs[key] = q
+        try:
+            q = ctxs["moments"]
+            assert q.moments_frames() == 32
+            for key, fn in (("atrous", lambda k: q.denoise(download=False, passes=k)),
+                            ("var", lambda k: q.denoise_var(download=False, passes=k)),
+                            ("var_spatial", lambda k: q.denoise_var(download=False, passes=k, min_temporal=1000))):
+                cum = [0.0] + [timed(lambda k=k: fn(k)) for k in range(1, 6)]
+                res[f"{key}_ms_by_passes"] = {str(k): cum[k] for k in range(1, 6)}
+                # [1] includes what precedes the first pass: pt_denoise's tone-mapped plane; pt_denoise_var's
+                # luminance plane and step A
+                res[f"{key}_pass_ms_by_stride"] = {str(1 << (k - 1)): cum[k] - cum[k - 1] for k in range(1, 6)}
+            res["var_over_atrous_by_stride"] = {s: res["var_pass_ms_by_stride"][s] / res["atrous_pass_ms_by_stride"][s]
+                                                for s in res["var_pass_ms_by_stride"]}
+            res["var_default_ms"] = timed(lambda: q.denoise_var(download=False))
+            # launches of 12 frames and of 1 frame, frame kernel and running-mean update together: the
+            # difference between the two contexts is what the moments cost a launch (a 1-frame launch of
+            # the plain context issued while nothing is in flight mixes inside its frame kernel; the
+            # kernels' own times: rocprofv3 --kernel-trace --stats of this script, mixKernel / mixMomentsKernel)
+            fc = {"plain": 32, "moments": 32}
+            for n, label in ((12, "batch12"), (1, "single")):
+                for key, c in ctxs.items():
+                    def launch(c=c, key=key, n=n):
+                        c.render_frames(eye, rot, fc[key], n)
+                        fc[key] += n
+                    res[f"{label}_launch_ms_{key}"] = timed(launch)
+                res[f"{label}_moments_over_plain"] = res[f"{label}_launch_ms_moments"] / res[f"{label}_launch_ms_plain"]
+            # each single frame waited for: the display() call, where the plain context mixes in its frame kernel
+            for key, c in ctxs.items():
+                c.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.reps):
+                    c.render_frame(eye, rot, fc[key])
+                    fc[key] += 1
+                res[f"single_call_wall_ms_{key}"] = (time.perf_counter() - t0) * 1e3 / a.reps
+        finally:
+            for q in ctxs.values():
+                q.close()
         line = json.dumps(res)
         print(line, flush=True)
         lines.append(line)

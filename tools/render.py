@@ -5,6 +5,7 @@ configuration progressively and write the image.
     python tools/render.py --config c2 --frames 64 --out gpurun_out/c2.png   # pass3 tonemap + PNG
     python tools/render.py --config c4 --frames 16 --out gpurun_out/c4.pfm   # linear accumulation
     python tools/render.py --config c4 --frames 4 --denoise --out out/c4.png  # + out/c4_denoised.png
+    python tools/render.py --config c4 --frames 64 --denoise var --out out/c4.png  # pt_denoise_var instead
     python tools/render.py --config c2 --drag 8 --step 2 --out out/c2.png     # a camera drag, see below
 
 PNG: pass3's tonemap (pass3.fsh:14-24, limit 1.5) then imshow's gamma 2.2
@@ -15,7 +16,8 @@ like the reference CPU tracer. PFM: the linear running mean.
 with --frames frames (default 1 with --drag) from frameCounter 0, resolved against the history of
 the cameras before it (pt_temporal_resolve / pt_temporal_commit). Writes the last camera's raw
 running mean to <out>, the resolved image to <out>_resolved.png and the resolved image through the
-a-trous filter (pt_denoise_from) to <out>_resolved_denoised.png.
+a-trous filter (pt_denoise_from; with --denoise var the variance-guided one, pt_denoise_var) to
+<out>_resolved_denoised.png.
 """
 from __future__ import annotations
 
@@ -34,7 +36,9 @@ def main():
     ap.add_argument("--out", default="gpurun_out/render.png")
     ap.add_argument("--builder", default=None)
     ap.add_argument("--flags", type=int, default=0)
-    ap.add_argument("--denoise", action="store_true", help="also write <out>_denoised.png (pt_denoise, defaults)")
+    ap.add_argument("--denoise", nargs="?", const="atrous", default=None, choices=["atrous", "var"],
+                    help="also write <out>_denoised.png: pt_denoise (default), or with `var` the variance-guided "
+                         "pt_denoise_var steered by the sample moments")
     ap.add_argument("--drag", type=int, default=0, help="render a drag of N cameras with the temporal resolve")
     ap.add_argument("--step", type=float, default=2.0, help="--drag: degrees between two cameras")
     a = ap.parse_args()
@@ -54,7 +58,7 @@ def main():
         tm = c[..., :3] * (np.float32(1) / (np.float32(1) + lum / np.float32(1.5)))[..., None]
         write_png(path, np.ascontiguousarray(tm, np.float32), 2.2, flip_rows=True)
 
-    kw = dict(basic_samples=a.frames) if basic else {}
+    kw = dict(basic_samples=a.frames) if basic else dict(moments=a.denoise == "var")
     with Renderer(cfg.width, cfg.height, cfg.integrator, max_bounce=cfg.max_bounce, flags=a.flags, **kw) as r:
         if basic:
             r.upload_shapes(scenes.cornell_shapes())
@@ -94,15 +98,15 @@ def main():
             resolved = r.temporal_resolve(a.frames)
             name = str(out.with_name(out.stem + "_resolved.png"))
             write_tm_png(name, resolved)
-            both = r.denoise(src_dptr=r.resolved_device_ptr())
+            both = (r.denoise_var if a.denoise == "var" else r.denoise)(src_dptr=r.resolved_device_ptr())
             name2 = str(out.with_name(out.stem + "_resolved_denoised.png"))
             write_tm_png(name2, both)
             print(f"{a.config}: drag of {a.drag} cameras, {a.step:g} deg apart -> {name}, {name2}")
         if a.denoise and not basic:
-            # the edge-avoiding a-trous filter of the running mean (pt_denoise, default parameters),
-            # through the same tonemap and gamma, beside the plain image
+            # the edge-avoiding a-trous filter of the running mean (pt_denoise or pt_denoise_var, default
+            # parameters), through the same tonemap and gamma, beside the plain image
             r.render_guides(eye, rot)
-            c = r.denoise()[..., :3]
+            c = (r.denoise_var() if a.denoise == "var" else r.denoise())[..., :3]
             lum = np.float32(0.3) * c[..., 0] + np.float32(0.6) * c[..., 1] + np.float32(0.1) * c[..., 2]
             tm = c * (np.float32(1) / (np.float32(1) + lum / np.float32(1.5)))[..., None]
             out = Path(a.out)
