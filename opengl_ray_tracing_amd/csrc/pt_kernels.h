@@ -86,6 +86,10 @@ constexpr int WAVE_TRACE_WORDS = PT_PHASE_STATS ? PHASE_WORDS : 6;  // u64 per w
 // Device-scope atomics are serialised per cache line at the memory side (~88
 // same-line ops/us), so every hot counter lives on its own 256-byte line.
 constexpr int CTL_LINE_INTS = 64;
+// records (16 bytes) of one queue's live-item segment for a launch of nFrames frames: the count's own
+// line, then room for every item of the queue, a whole number of lines (RenderParams::liveItems)
+constexpr int LIVE_HEAD = 16;
+__host__ __device__ constexpr int liveStride(int perQueue, int nFrames) { return LIVE_HEAD + ((perQueue * nFrames + 15) & ~15); }
 constexpr int NUM_QUEUES = PT_NUM_QUEUES;  // work counters, queue q owned by blocks with blockIdx % NUM_QUEUES == q
 static_assert((NUM_QUEUES & (NUM_QUEUES - 1)) == 0 && NUM_QUEUES <= 64, "NUM_QUEUES: power of two <= 64");
 constexpr int RAY_SHARDS = 64;     // sharded ray counters (u64, one per 256-byte line)
@@ -247,6 +251,12 @@ struct RenderParams {
   // need a path (primMask[f * numItems + w]: not sky, inside the image) and their results in slot
   // order at primHit + (f * numItems + w) * 64 (primOfSlot); sky slots cost no bytes
   unsigned long long* primMask;
+  // ... and, for the regen kernels, each work queue's live items (liveListKernel, after the pass):
+  // queue q's claims in claim order without those whose mask is 0 (all sky, or outside the image).
+  // Queue q's segment starts at liveItems + q * liveStride(perQueue, nFrames): one 256-byte line
+  // whose first int is the number of live items, then the records {tile, frame, mask lo, mask hi};
+  // null = every item is claimed (large scenes, pt_runtime.cpp; no pass)
+  uint4* liveItems;
   int zeroQueue;  // the camera-ray pass zeroes `queue` for the frame kernel after it (no memset)
   int* queue;           // NUM_QUEUES counters (stride CTL_LINE_INTS), zeroed before each launch
   int perQueue;         // items per queue (band), claimed once per frame of the launch
@@ -390,6 +400,8 @@ hipError_t renderBlocksPerCU(int integrator, bool cull, bool count, bool wide, i
 // the camera-ray pass: one wave per 8x8 tile of the rank's tiles, results in p.primHit
 constexpr int PRIM_MISS = -1, PRIM_RETRACE = -2, PRIM_TILE = -3;
 hipError_t launchPrimary(const RenderParams& p, hipStream_t s);
+// the live items of every work queue from the pass's tile masks (p.liveItems), for the regen kernels
+hipError_t launchLiveList(const RenderParams& p, hipStream_t s);
 // the path-regeneration kernel (pt_regen.hip): the variant and launch shape of a frame
 struct RegenShape {
   bool wide = false;      // the large-scene variant (WIDE_REGEN_WAVES, 4-wide walk, dynamic ray fetch)
@@ -403,6 +415,7 @@ struct RegenShape {
 // smallScene: the scene's records fit the L2s (not a PT_WIDE_SCENE_MB scene)
 hipError_t regenShape(int integrator, bool cull, bool wide, int f4nDev, bool smallScene, RegenShape* out);
 hipError_t launchRegen(const RenderParams& p, int integrator, int grid, hipStream_t s, bool cull, const RegenShape& r);
+bool regenTakesLists(int integrator, const RegenShape& r);  // the variant claims from live-item lists after a pass
 int regenLdsStack();
 int regenTop4(const RegenShape& r, int integrator);  // 4-wide nodes the wide regen kernel stages in LDS (PT_REGEN_TOP4[_3])
 hipError_t launchTrace(const TraceParams& p, int grid, hipStream_t s, bool cull);

@@ -71,6 +71,12 @@ constexpr int regenTop4W(int waves) { return waves == 3 ? PT_REGEN_TOP4_3 : PT_R
 // hand-out's state; materials staged in LDS per block measured c2 -0.6 %, within noise. Both knobs
 // were deleted in round 6, git history keeps them.)
 
+// live-item lists (pt_kernels.hip liveListKernel) for every regen variant but the MIS one of the scenes
+// that outgrow the L2s, whose launches fill the machine for milliseconds: a list kernel between the
+// pass and the frame kernel waits there for room as long as the pass itself (c5 4.07 -> 4.49 ms per frame)
+constexpr bool regenLists(int integ, int waves) {
+  return !(integ == 2 && waves == PT_WIDE_REGEN_WAVES && PT_WIDE_REGEN_WAVES_SMALL != PT_WIDE_REGEN_WAVES);
+}
 enum : int { K_NONE = 0, K_PRIMARY = 1, K_BOUNCE = 2, K_SHADOW = 3 };
 
 struct PathState {
@@ -300,6 +306,9 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
   static_assert(!FULL || W4, "the LDS tree is the 4-wide one");
   static_assert(!FULL || PT_REGEN_YIELD > 0, "the whole LDS tree is walked by walk4Run (loadNode4Lds) only");
   constexpr bool TILE_PRIM = PT_TILE_PRIM && INTEG != 2;
+  // the large scenes' MIS variant takes no live lists (regenLists): it compiles the claim
+  // it had, next() and the pass's mask array
+  constexpr bool LISTS = regenLists(INTEG, WAVES);
   __shared__ int s_stack[REGEN_LDS_STACK * BS];
   StackT<REGEN_LDS_STACK, BS> st;
   st.init(s_stack, p.ovf, p.ovfDepth);
@@ -414,22 +423,22 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
             // next tile ahead, c2 0.1807 -> 0.1841 ms, c5 4.25 -> 4.29; 2 / 4 consecutive items per
             // atomic, c2 0.2106 -> 0.2160 / 0.2390 at 4 hardware queues; claiming once the tile has
             // 8 / 16 / 32 slots left, c2 0.1783 -> 0.1786 / 0.1792 / 0.1793)
-            const int item = cur.next(p.queue, p.perQueue, p.numItems, home, tileFr, p.nFrames);
-            if (item < 0) {
+            // (round 7: after a camera-ray pass the claim comes from the queue's list of live items, which
+            // holds the tile's mask too -- an all-sky tile is no longer an item)
+            uint32_t lo = 0, hi = 0;  // the tile's camera-ray mask
+            static_assert(LISTS, "the tile hand-out's variants all take live lists");
+            if (!cur.nextLive(p.queue, p.primHit ? p.liveItems : nullptr, p.perQueue, p.numItems, p.nFrames, home, tile,
+                              tileFr, lo, hi)) {
               drained = true;
               break;  // no tiles left for this wave
             }
-            tile = item;
 #if PT_WAVE_TRACE
             wTiles++;
             wLastClaim = wall_clock64();
 #endif
             if (p.primHit) {
-              // the camera-ray pass's compacted results: the tile's mask (scalar), then its first nValid
+              // the camera-ray pass's compacted results: the tile's mask (scalar, lo / hi), then its first nValid
               // entries (one coalesced read of 8 bytes per path; sky slots cost nothing)
-              const unsigned long long m = primTileMask(p, tileFr, tile);
-              const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)m);
-              const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(m >> 32));
               if ((lane < 32 ? lo >> lane : hi >> (lane - 32)) & 1u)
                 s_slot[__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u))] = (unsigned char)lane;
               nValid = __popc(lo) + __popc(hi);
@@ -502,15 +511,21 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
         const unsigned long long idle = __ballot(!active);
         if (idle == 0) break;
         if (cursor >= 64) {
-          const int item = cur.next(p.queue, p.perQueue, p.numItems, home, tileFr, p.nFrames);
-          if (item < 0) break;  // no tiles left for this wave
-          tile = item;
-          cursor = 0;
-          if (p.primHit) {  // the tile's mask of the camera-ray pass's compacted results (wave-uniform)
-            const unsigned long long m = primTileMask(p, tileFr, tile);
-            tmaskLo = __builtin_amdgcn_readfirstlane((uint32_t)m);
-            tmaskHi = __builtin_amdgcn_readfirstlane((uint32_t)(m >> 32));
+          if constexpr (LISTS) {  // after a pass a live item: the tile, its frame and its camera-ray mask (wave-uniform)
+            if (!cur.nextLive(p.queue, p.primHit ? p.liveItems : nullptr, p.perQueue, p.numItems, p.nFrames, home, tile,
+                              tileFr, tmaskLo, tmaskHi))
+              break;  // no tiles left for this wave
+          } else {
+            const int item = cur.next(p.queue, p.perQueue, p.numItems, home, tileFr, p.nFrames);
+            if (item < 0) break;  // no tiles left for this wave
+            tile = item;
+            if (p.primHit) {  // the tile's mask of the camera-ray pass's compacted results (wave-uniform)
+              const unsigned long long m = primTileMask(p, tileFr, tile);
+              tmaskLo = __builtin_amdgcn_readfirstlane((uint32_t)m);
+              tmaskHi = __builtin_amdgcn_readfirstlane((uint32_t)(m >> 32));
+            }
           }
+          cursor = 0;
 #if PT_WAVE_TRACE
           wTiles++;
           wLastClaim = wall_clock64();
@@ -727,6 +742,9 @@ hipError_t launchRegen(const RenderParams& p, int integrator, int grid, hipStrea
   }
 }
 
+bool regenTakesLists(int integrator, const RegenShape& r) {
+  return regenLists(integrator, r.wide ? (r.small ? PT_WIDE_REGEN_WAVES_SMALL : wideRegenWaves(integrator)) : 0);
+}
 int regenLdsStack() { return REGEN_LDS_STACK; }
 int regenTop4(const RegenShape& r, int integrator) {
   return regenTop4W(r.small ? PT_WIDE_REGEN_WAVES_SMALL : wideRegenWaves(integrator));

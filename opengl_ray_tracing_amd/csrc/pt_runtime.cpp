@@ -178,6 +178,7 @@ struct pt_ctx {
   int batchCap = 1;
   int colCap[COLS] = {};                    // frames each colour buffer holds
   int primCap[PIPE] = {};                   // frames each slot's camera-ray results hold
+  int liveCap[PIPE] = {};                   // ... and each slot's live-item lists (regen kernels)
   // the large-scene path (regen kernel at 4 waves/SIMD, 4-wide walk with dynamic ray fetch,
   // camera-ray pass) on scenes of any size: -1 = for the Lambert integrator (c2 0.342 ->
   // 0.251 ms/frame) and the MIS integrator at 2 bounces (round 5: c3 0.1443 -> 0.1331; c4's 8
@@ -196,6 +197,7 @@ struct pt_ctx {
   unsigned binGen = 0, binGenSeen[MAX_SLOTS] = {};
   float* d_col[COLS] = {};                  // per-colour-buffer sample colours (COL_F floats per slot)
   int2* d_prim[PIPE] = {};                  // per-slot camera-ray results (primaryKernel)
+  uint4* d_live[PIPE] = {};                 // per-slot live-item lists and their counts (liveListKernel)
   int lastSlot = -1;                        // slot of the last pipelined frame
   int lastCol = -1;                         // colour buffer of the last pipelined frame
   bool mixPending = false;                  // a pipelined frame's update may still be running
@@ -566,6 +568,7 @@ void pt_destroy(pt_ctx* ctx) {
   for (int k = 0; k < PIPE; k++) {
     if (ctx->slotStream[k]) (void)hipStreamSynchronize(ctx->slotStream[k]);
     dfree(ctx->d_prim[k]);
+    dfree(ctx->d_live[k]);
     if (ctx->kernelDone[k]) (void)hipEventDestroy(ctx->kernelDone[k]);
     if (ctx->slotStream[k]) (void)hipStreamDestroy(ctx->slotStream[k]);
   }
@@ -1979,6 +1982,29 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
       }
       p.primHit = ctx->d_prim[slot];
       p.primMask = reinterpret_cast<unsigned long long*>(ctx->d_prim[slot] + (size_t)ctx->primCap[slot] * shareN);
+      // the regen kernels claim from per-queue lists of the tiles the pass left paths in (all variants
+      // but the large scenes' MIS one, pt_regen.hip regenLists)
+      if (regen && regenTakesLists(c.integrator, rs)) {
+        // per slot, like the results: every queue's segment of live items (liveStride records of 16 bytes)
+        auto liveBytes = [&](int cap) { return (size_t)NUM_QUEUES * liveStride(ctx->perQueue, cap) * sizeof(uint4); };
+        if (piped)
+          for (int k = 0; k < D; k++)
+            if (!ctx->d_live[k]) {
+              const int cap = std::max(nF, ctx->batchCap);
+              CK(hipMalloc(&ctx->d_live[k], liveBytes(cap)));
+              ctx->liveCap[k] = cap;
+            }
+        if (ctx->liveCap[slot] < nF) {  // the slot's previous launch (on S) may still read the old lists
+          if (ctx->d_live[slot]) {
+            CK(hipStreamSynchronize(S));
+            dfree(ctx->d_live[slot]);
+          }
+          const int cap = std::max(nF, piped ? ctx->batchCap : 1);
+          CK(hipMalloc(&ctx->d_live[slot], liveBytes(cap)));
+          ctx->liveCap[slot] = cap;
+        }
+        p.liveItems = p.primHit ? ctx->d_live[slot] : nullptr;  // (a share that owns no tile has no results and no lists)
+      }
     }
   }
   // a frame in band order (probePolicy) records no costs and launches no reorder; the
@@ -2015,6 +2041,7 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
   if (!p.primHit) CK(hipMemsetAsync(queue, 0, (size_t)NUM_QUEUES * CTL_LINE_INTS * sizeof(int), S));
   CK(hipEventRecord(evb, S));
   if (p.primHit) CK(launchPrimary(p, S));
+  if (p.liveItems) CK(launchLiveList(p, S));  // the frame kernel claims only tiles the pass left paths in
   if (regen) CK(launchRegen(p, c.integrator, grid, S, cull, rs));
   else CK(launchRender(p, c.integrator, grid, S, cull, count, wide));
 #if PT_WAVE_TRACE

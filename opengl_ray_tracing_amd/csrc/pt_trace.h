@@ -913,6 +913,7 @@ struct TileCursor {
   // the first claim past a queue's end, read once when the home queue drains): c2 per call -1.4 %,
   // its batched frames +1.2 %, c3 / c4 unchanged
   unsigned* drained = nullptr;
+  // (order / orderCap: the megakernel's lists only; the regen kernels pass none)
   __device__ __forceinline__ int next(int* queue, int perQueue, int numItems, int home, int& frame, int nFrames = 1,
                                       const int* order = nullptr, int orderCap = 0) {
     while (qi < NUM_QUEUES) {
@@ -942,6 +943,49 @@ struct TileCursor {
       qi++;
     }
     return -1;
+  }
+  // The claim of the regen variants that take live lists (pt_regen.hip regenLists). After a camera-ray
+  // pass (live != null) claim c of queue q is record c of the queue's live list
+  // (RenderParams::liveItems, liveListKernel) -- next()'s items in next()'s order without those the
+  // pass finished -- one wave-uniform 16-byte scalar read that holds the tile, its frame and its
+  // camera-ray mask (the lists are the previous kernel's output: constant here); the list's length is
+  // read beside the atomic. Without a pass (live == null) every item is
+  // claimed, the tile and frame next() gives, the masks untouched. False when every queue is
+  // drained; the drained mask is used as in next(). (Why one function, and what else was tried:
+  // DESIGN.md 3d.)
+  __device__ __forceinline__ bool nextLive(int* queue, const uint4* live, int perQueue, int numItems, int nFrames,
+                                           int home, int& tile, int& frame, uint32_t& maskLo, uint32_t& maskHi) {
+    typedef const __attribute__((address_space(4))) uint32_t* ConstU32;  // a uniform address: scalar loads
+    while (qi < NUM_QUEUES) {
+      const int q = (home + qi) & (NUM_QUEUES - 1);
+      const bool gone = drained && qi > 0 && ((__builtin_amdgcn_readfirstlane(*(volatile unsigned*)drained) >> q) & 1u);
+      if (!gone) {
+        const uint4* seg = live + (size_t)q * liveStride(perQueue, nFrames);
+        int n = 0;
+        if (live) n = (int)*(ConstU32)seg;  // in flight with the atomic
+        int it = 0;
+        if ((threadIdx.x & 63) == 0) it = atomicAdd(queue + q * CTL_LINE_INTS, 1);
+        it = __builtin_amdgcn_readfirstlane(it);  // lane 0's claim, as a scalar
+        n = live ? __builtin_amdgcn_readfirstlane(n) : min(perQueue, numItems - q * perQueue) * nFrames;
+        if (it < n) {
+          if (live) {
+            ConstU32 r = (ConstU32)(seg + LIVE_HEAD + it);
+            tile = (int)r[0];
+            frame = (int)r[1];
+            maskLo = r[2];
+            maskHi = r[3];
+          } else {
+            const int k = it / nFrames;
+            tile = q * perQueue + k;
+            frame = it - k * nFrames;
+          }
+          return true;
+        }
+        if (drained && (threadIdx.x & 63) == 0) atomicOr(drained, 1u << q);
+      }
+      qi++;
+    }
+    return false;
   }
 };
 

@@ -1,0 +1,256 @@
+"""The regen kernels' live-item lists (pt_kernels.hip liveListKernel, pt_trace.h TileCursor::nextLive):
+after the camera-ray pass each work queue hands out only the tiles the pass left paths in. The
+shapes are the smallest at which a list can go wrong -- no live tile at all, one live tile near the
+end of the queues, fewer tiles than queues, tiles live in some frames of a batch only, screen-tile
+shares that own nothing or only sky, and lists rebuilt after a camera move and a scene upload --
+and every image is compared with the oracle bit for bit (tests/parity.py, exact == 1.0).
+
+The regen kernel with the camera-ray pass runs by default for a streamed batch of Lambert or
+2-bounce MIS frames (render_frames, as tests/test_gpu_tiny.py) and is pinned with FLAG_REGEN |
+FLAG_PRIMARY_PASS wherever frames are issued one at a time (as test_frame_kernels_agree pins the
+kernel: a single frame issued into an idle pipeline would run the megakernel). Disney and MIS beyond
+2 bounces run the regen kernels' narrow variants under the same flags.
+
+Ray counts: a Lambert (and a uniform Disney) path traces exactly the oracle's rays, so the counts are
+equal. The MIS regen kernel does not trace a BRDF ray whose pdf is 0 (IS:816 traces and discards it,
+and the oracle counts it), so its counts are held to the exact figures the regen kernel gave on the
+commit before the lists, when every tile was claimed (tests/golden/live_tiles/mis_rays.json, written
+by tests/golden/make_live_tiles_fixture.py), and stay below the oracle's.
+
+Reference: IS main.cpp:659-709 (the frame loop), IS pass1.fsh:846-871 (camera ray, sky, running mean).
+"""
+import json
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import oracle
+import parity
+from opengl_ray_tracing_amd import FLAG_PRIMARY_PASS, FLAG_REGEN, FLAG_SERIAL_FRAMES, Renderer, orbit_camera, scenes
+from opengl_ray_tracing_amd.scene import Material, Scene
+
+pytestmark = pytest.mark.gpu
+
+FORCED = FLAG_REGEN | FLAG_PRIMARY_PASS
+
+
+@pytest.fixture(scope="module")
+def env():
+    return scenes.synthetic_env(64, 32)
+
+
+def image_point(eye, rot, w, h, fx, fy, depth):
+    """The world point at `depth` along the camera ray through pixel coordinates (fx, fy) (IS:846-850)."""
+    m = np.asarray(rot, np.float64).reshape(4, 4)  # column-major: row k is column k
+    x, y = (2.0 * fx + 1.0) / w - 1.0, (2.0 * fy + 1.0) / h - 1.0
+    return np.asarray(eye, np.float64) + depth * (m[0, :3] * x + m[1, :3] * y - 1.5 * m[2, :3])
+
+
+def triangle_scene(verts):
+    """One triangle at the given world positions, as the reference uploads it: the scene encoder's
+    records of a one-triangle mesh (its material; one leaf under the dummy node 0) with the
+    positions, the face normal and the leaf's box put in place (readObj itself rescales a mesh)."""
+    s = Scene()
+    s.add_mesh(np.eye(3, dtype=np.float32), np.array([[0, 1, 2]], np.int32), Material(baseColor=(0.8, 0.6, 0.4)))
+    s.build_bvh("sah", 8)
+    tris, nodes = s.encode()
+    tris = np.array(tris, np.float32).reshape(1, 36)
+    nodes = np.array(nodes, np.float32).reshape(2, 12)
+    v = np.asarray(verts, np.float32).reshape(3, 3)
+    n = np.cross((v[1] - v[0]).astype(np.float64), (v[2] - v[0]).astype(np.float64))
+    tris[0, 0:9] = v.reshape(9)
+    tris[0, 9:18] = np.tile((n / np.linalg.norm(n)).astype(np.float32), 3)
+    nodes[1, 6:9] = v.min(0)
+    nodes[1, 9:12] = v.max(0)
+    return tris, nodes
+
+
+def pixel_triangle(eye, rot, w, h, x0, y0, x1, y1, depth=3.0):
+    """A triangle whose image is the lower-left half of the pixel rectangle [x0, x1] x [y0, y1]."""
+    return triangle_scene([image_point(eye, rot, w, h, x0, y0, depth), image_point(eye, rot, w, h, x1, y0, depth),
+                           image_point(eye, rot, w, h, x0, y1, depth)])
+
+
+def behind_camera(eye, rot, w, h):
+    return triangle_scene([image_point(eye, rot, w, h, fx, fy, -5.0) for fx, fy in ((0, 0), (w, 0), (0, h))])
+
+
+def oracle_frames(tris, nodes, hdr, w, h, integrator, eye, rot, frames, mb=2):
+    """-> (running mean after `frames` frames from a restart, rays, pixels whose camera ray hit in any frame)"""
+    o = oracle.Oracle(tris, nodes, hdr)
+    sky = oracle.Oracle(*behind_camera(eye, rot, w, h), hdr)
+    acc = np.zeros((h, w, 4), np.float32)
+    hit = np.zeros((h, w), bool)
+    rays = 0
+    for f in range(frames):
+        acc, cnt = o.render(w, h, integrator, f, eye, rot, accum=acc, max_bounce=mb)
+        rays += cnt.rays
+        one, _ = o.render(w, h, integrator, f, eye, rot, max_bounce=mb)
+        none, cs = sky.render(w, h, integrator, f, eye, rot, max_bounce=mb)
+        assert cs.rays == w * h
+        hit |= np.any(one[..., :3] != none[..., :3], axis=-1)
+    return acc, rays, hit
+
+
+def live_tiles(hit):
+    h, w = hit.shape
+    return {(ty, tx) for ty in range((h + 7) // 8) for tx in range((w + 7) // 8) if hit[8 * ty:8 * ty + 8, 8 * tx:8 * tx + 8].any()}
+
+
+def gpu_frames(tris, nodes, hdr, w, h, integrator, eye, rot, frames, mode, mb=2, **kw):
+    """mode: "stream" (one render_frames call, the default kernels), "forced" (the same, pinned), "call"
+    (display() calls), "serial" (PT_FLAG_SERIAL_FRAMES), or a tuple of batch sizes"""
+    flags = 0 if mode == "stream" else FORCED | (FLAG_SERIAL_FRAMES if mode == "serial" else 0)
+    with Renderer(w, h, integrator, max_bounce=mb, flags=flags, **kw) as r:
+        r.upload_scene(tris, nodes)
+        r.upload_env(hdr)
+        if mode == "call":
+            for f in range(frames):
+                r.render_frame(eye, rot, f)
+        elif mode == "serial":
+            for f in range(frames):
+                r.render_frame(eye, rot, f, sync=False)
+        else:
+            f = 0
+            for n in ((frames,) if mode in ("stream", "forced") else mode):
+                r.render_frames(eye, rot, f, n)
+                f += n
+            assert f == frames
+        r.synchronize()
+        st = r.stats()
+        assert st.regen == 1, (mode, st)
+        return r.accum().copy(), st.rays
+
+
+MIS_RAYS_FILE = Path(__file__).parent / "golden" / "live_tiles" / "mis_rays.json"
+RECORD = None  # make_live_tiles_fixture.py: a dict that takes the MIS counts instead of checking them
+
+
+def check_rays(integrator, gpu, orc, key):
+    if integrator != "mis":
+        assert gpu == orc, (key, gpu, orc)
+    elif RECORD is not None:
+        RECORD[key] = int(gpu)
+    else:
+        want = json.loads(MIS_RAYS_FILE.read_text())[key]
+        assert gpu == want and gpu <= orc, (key, gpu, want, orc)
+
+
+@pytest.mark.parametrize("integrator", ["lambert", "mis"])
+def test_no_live_tile(env, integrator):
+    """A triangle behind the camera: every queue's list is empty, the image is the sky and each
+    frame traces one ray per pixel."""
+    w, h, frames = 64, 40, 5
+    eye, rot = orbit_camera(20.0, 10.0, 4.0)
+    tris, nodes = behind_camera(eye, rot, w, h)
+    ref, rays, hit = oracle_frames(tris, nodes, env, w, h, integrator, eye, rot, frames)
+    assert not hit.any() and rays == frames * w * h
+    for mode in ("stream", "call"):
+        g, n = gpu_frames(tris, nodes, env, w, h, integrator, eye, rot, frames, mode)
+        parity.assert_parity(g.reshape(-1, 4), ref.reshape(-1, 4), f"no live tile/{integrator}/{mode}")
+        assert n == frames * w * h, (mode, n)
+
+
+@pytest.mark.parametrize("w,h", [(70, 45), (16, 16), (160, 32)])
+@pytest.mark.parametrize("integrator", ["lambert", "mis"])
+def test_one_live_tile(env, integrator, w, h):
+    """A few pixels of the bottom-right tile only, which a late queue owns: 70 x 45 has partial tiles and
+    tiles of its last screen tiles outside the image (96 tiles, 3 per queue); 16 x 16 has fewer tiles
+    than queues, so most queues own no tile; 160 x 32 has 80 tiles, 3 per queue, so queue 26 is only
+    partly inside the tile count and queues 27-31 own none."""
+    frames = 3
+    eye, rot = orbit_camera(20.0, 10.0, 4.0)
+    tris, nodes = pixel_triangle(eye, rot, w, h, w - 4.0, h - 4.0, w - 1.2, h - 1.2)
+    ref, rays, hit = oracle_frames(tris, nodes, env, w, h, integrator, eye, rot, frames)
+    assert live_tiles(hit) == {((h - 1) // 8, (w - 1) // 8)}
+    for mode in ("stream", "call"):
+        g, n = gpu_frames(tris, nodes, env, w, h, integrator, eye, rot, frames, mode)
+        parity.assert_parity(g.reshape(-1, 4), ref.reshape(-1, 4), f"one live tile/{integrator}/{mode}/{w}x{h}")
+        check_rays(integrator, n, rays, f"one live tile/{w}x{h}/{mode}")
+
+
+@pytest.mark.parametrize("integrator,mb", [("disney", 2), ("mis", 3)])
+def test_narrow_kernels(env, integrator, mb):
+    """The regen kernels that are not the large-scene variants (Disney: the tile hand-out; MIS at 3
+    bounces: the per-lane hand-out) claim from the lists too: the 70 x 45 image with a triangle over
+    its lower right, batched and per call."""
+    w, h, frames = 70, 45, 3
+    eye, rot = orbit_camera(20.0, 10.0, 4.0)
+    tris, nodes = pixel_triangle(eye, rot, w, h, 30.0, 12.0, w - 1.2, h - 1.2)
+    ref, rays, hit = oracle_frames(tris, nodes, env, w, h, integrator, eye, rot, frames, mb)
+    assert 1 < len(live_tiles(hit)) < 54
+    for mode in ("forced", "call"):
+        g, n = gpu_frames(tris, nodes, env, w, h, integrator, eye, rot, frames, mode, mb)
+        parity.assert_parity(g.reshape(-1, 4), ref.reshape(-1, 4), f"narrow/{integrator}/{mode}")
+        check_rays(integrator, n, rays, f"narrow/{integrator}{mb}/{mode}")
+
+
+@pytest.mark.parametrize("integrator", ["lambert", "mis"])
+def test_items_live_in_some_frames_only(env, integrator):
+    """c2's mesh at 96 x 54, 7 frames as batches of 3 + 3 + 1, one frame at a time and with
+    PT_FLAG_SERIAL_FRAMES: the silhouette tiles' masks differ from frame to frame (the jitter), so a
+    tile is an item of some frames of a batch only."""
+    w, h, frames = 96, 54, 7
+    cfg, tris, nodes, _ = scenes.build_config("c2")
+    eye, rot = orbit_camera(*cfg.camera)
+    ref, rays, hit = oracle_frames(tris, nodes, env, w, h, integrator, eye, rot, frames)
+    assert 0 < len(live_tiles(hit)) < (w // 8) * ((h + 7) // 8)
+    out = [gpu_frames(tris, nodes, env, w, h, integrator, eye, rot, frames, m) for m in ((3, 3, 1), (1,) * 7, "serial")]
+    for g, n in out:
+        parity.assert_parity(g.reshape(-1, 4), ref.reshape(-1, 4), f"some frames/{integrator}")
+        assert np.array_equal(g, out[0][0]) and n == out[0][1]
+        check_rays(integrator, n, rays, "some frames")  # (the three ways' counts are equal, above)
+
+
+@pytest.mark.parametrize("world", [3, 8])
+def test_screen_tile_shares(env, world):
+    """40 x 40 (2 x 2 screen tiles of 32 x 32) split 3 and 8 ways: some ranks own nothing, some own
+    only sky; each rank's pixels equal the one-rank render's, and the ray counts sum to its count."""
+    w = h = 40
+    frames = 3
+    eye, rot = orbit_camera(20.0, 10.0, 4.0)
+    tris, nodes = pixel_triangle(eye, rot, w, h, 3.0, 2.0, 20.0, 14.0)  # inside screen tile 0
+    ref, rays, hit = oracle_frames(tris, nodes, env, w, h, "lambert", eye, rot, frames)
+    assert hit.any() and not hit[32:].any() and not hit[:, 32:].any()
+    whole, n1 = gpu_frames(tris, nodes, env, w, h, "lambert", eye, rot, frames, "stream")
+    parity.assert_parity(whole.reshape(-1, 4), ref.reshape(-1, 4), "one rank")
+    assert n1 == rays
+    total = 0
+    for rank in range(world):
+        a, n = gpu_frames(tris, nodes, env, w, h, "lambert", eye, rot, frames, "stream", tile_rank=rank, tile_world=world)
+        mine = np.zeros((h, w), bool)
+        for t in range(rank, 4, world):  # screen tiles t (row-major, 2 x 2 of them)
+            ty, tx = divmod(t, 2)
+            mine[32 * ty:32 * ty + 32, 32 * tx:32 * tx + 32] = True
+        assert np.array_equal(a[mine], whole[mine]) and not a[~mine].any(), rank
+        total += n
+    assert total == n1
+
+
+@pytest.mark.parametrize("integrator", ["lambert", "mis"])
+def test_camera_move_and_scene_upload(env, integrator):
+    """Two frames, a camera move that makes empty tiles live and live tiles empty, two more, another
+    scene, two more: each segment equals the oracle for the same restarted running mean."""
+    w, h = 64, 40
+    eye, rot = orbit_camera(20.0, 10.0, 4.0)
+    eye2, rot2 = orbit_camera(20.0, 10.0, 6.0)
+    tris, nodes = pixel_triangle(eye, rot, w, h, 4.0, 3.0, 22.0, 15.0, depth=1.5)
+    tris2, nodes2 = pixel_triangle(eye2, rot2, w, h, 40.0, 20.0, 62.0, 38.0, depth=2.0)
+    segs = [(tris, nodes, eye, rot), (tris, nodes, eye2, rot2), (tris2, nodes2, eye2, rot2)]
+    refs = [oracle_frames(t, n, env, w, h, integrator, e, m, 2) for t, n, e, m in segs]
+    la, lb, lc = (live_tiles(r[2]) for r in refs)
+    assert la - lb and lb - la and lc and lc != lb
+    with Renderer(w, h, integrator, max_bounce=2, flags=FORCED) as r:  # a segment's second frame is a launch of one
+        r.upload_env(env)
+        seen = 0
+        for k, ((t, n, e, m), (ref, rays, _)) in enumerate(zip(segs, refs)):
+            if k != 1:
+                r.upload_scene(t, n)
+            r.render_frames(e, m, 0, 2)
+            r.synchronize()
+            parity.assert_parity(r.accum().reshape(-1, 4), ref.reshape(-1, 4), f"segment {k}/{integrator}")
+            st = r.stats()
+            assert st.regen == 1
+            check_rays(integrator, st.rays - seen, rays, f"camera move/segment {k}")
+            seen = st.rays

@@ -12,7 +12,7 @@ Reads gpurun_out/prof_<tag>_<cfg>/ and writes, under profiles/<tag>/:
   counters.json                 {cfg: per-kernel and per-frame counter work, time bases}
 
 A frame (bench.py step at N = 1) runs these kernels, each once (FRAME_KERNELS): the camera-ray
-pass primaryKernel (the regen path), the frame kernel (renderKernel<I, true, false[, W]> or
+pass primaryKernel and the live-item lists liveListKernel (the regen path), the frame kernel (renderKernel<I, true, false[, W]> or
 regenKernel<I, true[, W, true]>), the tile reorder reorderKernel (megakernel frames in
 longest-first order) and the running-mean update mixKernel. The profiled bench runs end with its
 timed frames (--no-reset --no-serial --no-psnr), so each kernel's last K dispatches are the timed
@@ -48,6 +48,7 @@ TRACE_STEPS = 96  # divisible by every frames-per-launch the bench uses (12 for 
 COUNTER_STEPS = 96
 FRAME_KERNELS = {
     "primary": re.compile(r"primaryKernel"),
+    "live": re.compile(r"liveListKernel"),  # the regen kernels' live-item lists, after the pass
     "frame": re.compile(r"renderKernel<\d+, true, false(, \d+)?>|regenKernel<\d+, true[^>]*>"),
     "reorder": re.compile(r"reorderKernel"),
     "mix": re.compile(r"mixKernel"),
