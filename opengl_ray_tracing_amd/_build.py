@@ -49,12 +49,17 @@ SOURCES = {
     "pt_build.o": ("hip", CSRC / "pt_build.hip", [CSRC / "pt_kernels.h"]),
     "pt_guides.o": ("hip", CSRC / "pt_guides.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", CSRC / "pt_trace.h",
                                                      INCLUDE / "pt_fmath.h"]),
-    "pt_denoise.o": ("hip", CSRC / "pt_denoise.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]),
+    "pt_denoise.o": ("hip", CSRC / "pt_denoise.hip", [CSRC / "pt_atrous.h", CSRC / "pt_device.h", CSRC / "pt_kernels.h",
+                                                       INCLUDE / "pt_fmath.h"]),
     "pt_temporal.o": ("hip", CSRC / "pt_temporal.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]),
     "pt_moments.o": ("hip", CSRC / "pt_moments.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]),
-    "pt_variance.o": ("hip", CSRC / "pt_variance.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]),
-    "pt_runtime.o": ("cxx", CSRC / "pt_runtime.cpp", [CSRC / "pt_kernels.h", INCLUDE / "pt_abi.h", INCLUDE / "pt_scene.h",
-                                                       INCLUDE / "pt_fmath.h", CSRC / "pt_rccl.h"]),
+    "pt_variance.o": ("hip", CSRC / "pt_variance.hip", [CSRC / "pt_atrous.h", CSRC / "pt_device.h", CSRC / "pt_kernels.h",
+                                                         INCLUDE / "pt_fmath.h"]),
+    "pt_runtime.o": ("cxx", CSRC / "pt_runtime.cpp", [CSRC / "pt_runtime.h", CSRC / "pt_kernels.h", CSRC / "pt_accel.h",
+                                                       INCLUDE / "pt_abi.h", INCLUDE / "pt_scene.h", INCLUDE / "pt_fmath.h",
+                                                       CSRC / "pt_rccl.h"]),
+    "pt_post.o": ("cxx", CSRC / "pt_post.cpp", [CSRC / "pt_runtime.h", CSRC / "pt_kernels.h", INCLUDE / "pt_abi.h",
+                                                 CSRC / "pt_rccl.h"]),
     "pt_rccl.o": ("cxx", CSRC / "pt_rccl.cpp", [CSRC / "pt_rccl.h"]),
     "scene.o": ("cxx", CSRC / "scene.cpp", [INCLUDE / "pt_scene.h"]),
 }

@@ -433,25 +433,30 @@ struct GuideParams {
   int ovfDepth;
 };
 hipError_t launchGuides(const GuideParams& p, int grid, hipStream_t s, bool cull);
+// One pass of an a-trous filter (pt_atrous.h): what the two filters' passes share
+struct AtrousCommon {
+  int width, height;
+  int stride;                // 2^pass
+  const float4* in;
+  float4* out;
+  const float4* posT;
+  const float4* nrmTri;
+  const float4* albedo;
+  float sigmaZ;              // <= 0: term off
+  float albDen;              // sigma_a^2
+  int albOn;
+  int normalLog2;            // -1: term off
+  float limit;
+};
 // The edge-avoiding a-trous filter (pt_denoise.hip), one launch per pass. Every pass reads its
 // input colour `in` and that colour tone-mapped `tmIn` (both float4 planes), and writes `out` and,
 // for the next pass, tm(out) to `tmOut` (null on the last pass); launchAtrousTm writes the first
 // pass's tm plane from the accumulation.
-struct AtrousParams {
-  int width, height;
-  int stride;                // 2^pass
-  const float4* in;
+struct AtrousParams : AtrousCommon {
   const float4* tmIn;
-  const float4* posT;
-  const float4* nrmTri;
-  const float4* albedo;
-  float4* out;
   float4* tmOut;
-  float sigmaZ;              // <= 0: term off
-  float colDen, albDen;      // sigma_c_i^2, sigma_a^2
-  int colOn, albOn;
-  int normalLog2;            // -1: term off
-  float limit;
+  float colDen;              // sigma_c_i^2
+  int colOn;
 };
 constexpr int ATROUS_TILE = 16;     // a block's 16 x 16 output pixels
 constexpr int ATROUS_LDS_STRIDE = 2;  // passes of stride <= this stage their tile + halo in LDS
@@ -473,22 +478,10 @@ struct VarInitParams {
 };
 // One launch per pass: reads the colour `in` and its (l, v) plane `lvIn`, writes `out` and, for the
 // next pass, (lum(tm(out)), v_out) to `lvOut` (null on the last pass).
-struct AtrousVarParams {
-  int width, height;
-  int stride;                // 2^pass
-  const float4* in;
+struct AtrousVarParams : AtrousCommon {
   const float2* lvIn;
-  const float4* posT;
-  const float4* nrmTri;
-  const float4* albedo;
-  float4* out;
   float2* lvOut;
   float sigmaL;              // <= 0: term off
-  float sigmaZ;              // <= 0: term off
-  float albDen;              // sigma_a^2
-  int albOn;
-  int normalLog2;            // -1: term off
-  float limit;
 };
 hipError_t launchVarLum(const float4* in, float* lum, int n, float limit, hipStream_t s);
 hipError_t launchVarInit(const VarInitParams& p, hipStream_t s);

@@ -1,6 +1,7 @@
 // pt_runtime.cpp -- host implementation of the C-ABI in include/pt_abi.h:
 // device selection, scene/env upload with the MI355X re-layout, frame
 // launches, batch queries, accumulation access and multi-GPU tile pack.
+// (The display post-processing -- guides, denoisers, temporal resolve -- is pt_post.cpp.)
 //
 // Compiled with -ffp-contract=off so the per-triangle unit normal and plane
 // offset precomputed here round exactly like the reference computes them
@@ -23,50 +24,17 @@
 #include "pt_fmath.h"
 #include "pt_kernels.h"
 #include "pt_rccl.h"
+#include "pt_runtime.h"
 #include "pt_scene.h"
 
 using namespace pt;
 
-static constexpr int EV_RING = 64;
-// Frames in flight: the default megakernel's (or regen kernel's) launch g (its pipeline
-// sequence number) runs on slot stream g % depth (8 by default) with its own work queues,
-// overflow stack, tile order and camera-ray results, and writes its sample colours to colour
-// buffer g % (2 * depth + 1). While k other launches are in flight its persistent grid is 1.5 /
-// (k + 1) of residency (renderOne), so the frames in flight share the GPU by space: their waves
-// are resident together, and a frame whose last long paths keep a few waves busy leaves the
-// rest of the machine to the others. Its running-mean update (mixKernel) runs on the caller's
-// stream, in frame order, once the launch's kernel has ended: the accumulation is updated in
-// frame order, the image is bit for bit the one of serial frames, and whatever the caller
-// queues behind a frame (pack, download, tonemap) follows its update with no further
-// cross-queue wait. No launch waits for a mix except the one of the launch 2 * depth + 1 back,
-// whose colour buffer it reuses.
-//
-// A launch may render a batch of consecutive frames of one camera (pt_render_frames_async,
-// RenderParams::nFrames): every frame's colours in its own part of the colour buffer, and one
-// mixKernel folds them into the running mean pixel by pixel in frame order. A small screen-tile
-// share (1/8 of the image) gives one frame too little work to fill the machine; a batch of
-// tile_world frames per launch is about one whole image's work, and the chain of running-mean
-// updates on the caller's stream -- one cross-queue wait and one launch per update, which set
-// an 8-way share's frame period before -- has one link per batch.
-// (Measured alternatives, DESIGN.md 4: a separate mix stream is twice as slow at small
-// shares -- each mix waited on two ~25 us cross-queue signals in a chain from mix to mix; and
-// with full-residency grids a mix waits for a CU slot behind the next frame's persistent
-// kernel, ~250 us on c2, which made deeper pipelines slower, not faster.)
-#ifndef PT_PIPE
-#define PT_PIPE 8  // frames in flight (PT_PIPE_DEPTH overrides; capped by the hardware queues)
-#endif
-static constexpr int PIPE = MAX_SLOTS;      // most frames in flight
 // 32: c2's 1/8 share in the 20-frame bench window at 4 hardware queues 0.0417 -> 0.0351 ms per
 // frame (its 20 frames one launch instead of 16 + 4), 1/4 share 0.0593 -> 0.0569, c4 0.2736 -> 0.2701
 #ifndef PT_MAX_BATCH
 #define PT_MAX_BATCH 32
 #endif
 static constexpr int MAX_BATCH = PT_MAX_BATCH;  // most frames per launch (pt_render_frames_async)
-// colour buffers: a launch reuses the buffer of the launch 2 * depth + 1 back, whose running-mean
-// update is then long done -- with depth + 1 the wait made a slot's next frame follow the
-// running-mean update of the previous frame on another slot (two cross-queue hops), and an N = 8
-// share of c2 kept only ~3 of its 8 frames in flight
-static constexpr int COLS = 2 * MAX_SLOTS + 1;
 // a launch of one frame while nothing else is in flight mixes its samples into the running mean in
 // its own kernels (renderOne: no colour buffer, no mixKernel launch)
 #ifndef PT_DIRECT_SOLO
@@ -83,234 +51,7 @@ static_assert(PIPE * NUM_QUEUES * CTL_LINE_INTS * 4 <= (int)CTL_STATS, "queue co
 #define PT_TILE_GROUP 1  // tiles ordered by cost in groups of this many consecutive tiles (1 measured best)
 #endif
 
-
-struct pt_ctx {
-  pt_config cfg{};
-  std::string err;
-  hipStream_t own = nullptr, stream = nullptr;
-  // Launch timing: a fixed ring of begin/end event pairs. Launch number i (since
-  // pt_create) records into pair i % EV_RING; a launch's elapsed time is folded
-  // into the running totals once its end event has completed (non-blocking on
-  // every new launch, blocking only when the ring is full or stats are read), so
-  // the cost per frame stays constant however long a caller renders.
-  hipEvent_t ev[2 * EV_RING] = {};
-  int evProbe[EV_RING] = {};    // probe slot of the launch in each ring position (-1 none)
-  int evGen[EV_RING] = {};      // probe generation it was tagged in
-  long long issued = 0, folded = 0;
-  double msTotal = 0.0;         // summed device time of the folded launches since the reset
-  float msLast = 0.0f;          // device time of the last folded launch
-  int launches = 0;             // render launches since the reset
-  long long frames = 0;         // frames those launches rendered (a batch launch renders several)
-  int tagSlot = -1;             // probe slot for the launch being issued (probePolicy)
-  int numCU = 0;
-  // scene
-  float4* d_geo = nullptr;
-  float4* d_pairs = nullptr;  // triangles i and i+1 component-interleaved (SceneView::pairs)
-  float4* d_hit = nullptr;   // per triangle: normals + material id (SceneView::hitRec)
-  float4* d_mats = nullptr;  // the distinct materials (SceneView::mats)
-  int nMats = 0;
-  float4* d_bvh = nullptr;
-  int nDevNodes = 0;  // internal nodes in d_bvh (device ids 0..nDevNodes-1)
-  // the runtime's own tree (uploadAccel; SceneView::fast) and the reference
-  // facts its results are checked against
-  bool fastReady = false;
-  float4* d_fbvh = nullptr;
-  float4* d_fpairs = nullptr;
-  int* d_fastTri = nullptr;
-  int* d_refParent = nullptr;
-  float4* d_refBox = nullptr;
-  float4* d_leafBox = nullptr;
-  int fRoot = REF_NONE, fnDev = 0, fDepth = 0;
-  // the same tree collapsed to 4-wide nodes (encodeWide4; the large-scene regen kernel)
-  float4* d_fbvh4 = nullptr;
-  bool fast4Ready = false;
-  int f4Root = REF_NONE, f4nDev = 0, f4Depth = 0;
-  // the last pt_upload_scene (pt_frame_stats upload_ms, accel_*)
-  float uploadMs = 0.0f, accelMs = 0.0f;
-  int accelDevice = -1, accelNodes = 0, accelDepth = 0;
-  int rootRef = REF_NONE;
-  int nTri = 0, nNodes = 0, depth = 0, maxStack = 0;
-  // env
-  float4* d_hdr = nullptr;
-  float2* d_cache = nullptr;  // sample table (x, y); the pdf lives in d_hdr[k].w
-  uint2* d_hdr8 = nullptr;    // the same texels compacted (pt_kernels.h Env), null = not exact
-  uint32_t* d_cache4 = nullptr;
-  uint32_t* d_cacheRow = nullptr;           // the sample table by rows (pt_kernels.h Env::cacheRow)
-  unsigned short* d_cacheY = nullptr;
-  float2* d_trig = nullptr;                  // SampleHdr's sines and cosines (Env::trig)
-  uint2* d_light = nullptr;                  // each sample-table entry's light-sample color and pdf (Env::light)
-  int hdrW = 0, hdrH = 0;
-  // BASIC shapes, the double image, the replayed random stream
-  double* d_shapes = nullptr;
-  int nShapes = 0;
-  double* d_basicImg = nullptr;
-  double* d_stream = nullptr;
-  long long* d_offsets = nullptr;
-  long long streamN = 0, nOffsets = 0;
-  unsigned long long* d_overruns = nullptr;
-  // frame state
-  float4* d_accum = nullptr;
-  // control block (pt_kernels.h CTL_*): padded queue counters (zeroed per
-  // launch), cumulative fetch stats, padded sharded cumulative ray counters
-  unsigned char* d_ctl = nullptr;
-  int* d_ovf = nullptr;
-  int* d_cost = nullptr;   // per slot: per-tile cost of its last frame, longest item, split state, estimate
-  int* d_order = nullptr;  // per slot: per-band work items for its next frame
-  bool lastFast = false;    // the last megakernel frame traversed the runtime's tree
-  bool lastRegen = false;   // the last frame ran the path-regeneration kernel
-  int lastWaves = 0;        // waves per SIMD of the last megakernel launch (occupancy query)
-  // tree / tile-split policy probe (probePolicy): frames since the probe (re)started,
-  // the summed frame times of each policy, the decision
-  int probeFrame = 0;
-  // camera-ray bins (pt_primary.hip) of the camera and scene they were built for
-  PrimaryBins bins;
-  bool binsValid = false;
-  float binEye[3] = {}, binCam[16] = {};
-  unsigned sceneVersion = 0, binVersion = 0;
-  // frames in flight (PIPE slots; see PIPE above)
-  bool pipe = false;                        // this context pipelines its megakernel frames
-  int pipeDepth = PT_PIPE;                  // frames in flight (slot streams in use), 1..PIPE
-  int pipeDepthBase = PT_PIPE;              // ... as chosen at creation (uploadScene may lower it for large scenes)
-  bool pipeDepthFixed = false;              // PT_PIPE_DEPTH set: no scene-dependent choice
-  // Frames of one pt_render_frames_async call rendered per launch (RenderParams::nFrames), at most:
-  // pt_config.frame_batch, else as many as make one launch about a whole image's work (tile_world
-  // frames of a screen-tile share, up to MAX_BATCH). Probe frames and frameCounter 0 run alone.
-  int batchCap = 1;
-  int colCap[COLS] = {};                    // frames each colour buffer holds
-  int primCap[PIPE] = {};                   // frames each slot's camera-ray results hold
-  int liveCap[PIPE] = {};                   // ... and each slot's live-item lists (regen kernels)
-  // the large-scene path (regen kernel at 4 waves/SIMD, 4-wide walk with dynamic ray fetch,
-  // camera-ray pass) on scenes of any size: -1 = for the Lambert integrator (c2 0.342 ->
-  // 0.251 ms/frame) and the MIS integrator at 2 bounces (round 5: c3 0.1443 -> 0.1331; c4's 8
-  // bounces keep the megakernel); PT_FLAG_REGEN / PT_FLAG_MEGAKERNEL choose per context,
-  // PT_REGEN_WIDE = 1 / 0 (environment) for every / no scene
-  int regenWide = -1;
-  bool solo = true;                         // PT_SOLO = 0 (environment): every pipelined launch on a slot stream
-  hipStream_t slotStream[PIPE] = {};
-  hipEvent_t kernelDone[PIPE] = {};         // slot's last frame kernel (+ reorder) ended
-  bool slotBusy[PIPE] = {};                 // kernelDone[k] has been recorded since the last sync
-  hipEvent_t mixDone[COLS] = {};            // colour buffer's last running-mean update
-  hipStream_t lastMixStream = nullptr;      // the stream the last update ran on (pt_set_stream may change it)
-  // camera-ray bins built on one slot's stream: binsBuilt is recorded after the build, and
-  // every other slot waits for it once before its first frame with those bins (binGen)
-  hipEvent_t binsBuilt = nullptr;
-  unsigned binGen = 0, binGenSeen[MAX_SLOTS] = {};
-  float* d_col[COLS] = {};                  // per-colour-buffer sample colours (COL_F floats per slot)
-  int2* d_prim[PIPE] = {};                  // per-slot camera-ray results (primaryKernel)
-  uint4* d_live[PIPE] = {};                 // per-slot live-item lists and their counts (liveListKernel)
-  int lastSlot = -1;                        // slot of the last pipelined frame
-  int lastCol = -1;                         // colour buffer of the last pipelined frame
-  bool mixPending = false;                  // a pipelined frame's update may still be running
-  unsigned long long frameNo = 0;           // pipelined frames issued
-  int probeN[4] = {0, 0, 0, 0};        // timed frames: runtime tree, uploaded tree (both unsplit), split
-  double probeMs[4] = {0.0, 0.0, 0.0, 0.0};
-  long long probeLast[4] = {-1, -1, -1, -1};  // launch number of each slot's last timed frame
-  int probeGen = 0;
-  int treeDecided = -1, splitDecided = -1;  // -1 probing, 0 off, 1 on
-  unsigned policyKey = 0, probedKey = ~0u;  // bumped by every scene / env upload; the key the decisions were made for
-  int orderCap = 0;        // work items per band in d_order
-  bool orderValid[PIPE] = {};
-  bool orderSplit[PIPE] = {};               // the slot's order list holds split items (a one-frame launch built it)
-  size_t ovfInts = 0;
-  // shards
-  int shardSize = 32, shardsX = 0, shardsY = 0, numItems = 0, perQueue = 0;
-  // scratch for queries / tonemap / pack
-  float* d_rays = nullptr;
-  float* d_t = nullptr;
-  int* d_tri = nullptr;
-  size_t traceCap = 0;
-  float* d_rgb = nullptr;
-  // guide buffers of the last pt_render_guides (valid for the scene version they were traced in) and
-  // the denoiser's images: two ping-pong colour planes, their tone-mapped planes, and the
-  // image the last pt_denoise wrote (one of the two, or the caller's)
-  float4* d_guide[3] = {};   // pos_t, nrm_tri, albedo of the current set (guideSet)
-  // pos_t / nrm_tri exist twice: pt_temporal_commit marks the current set as the history's, and
-  // pt_render_guides then writes the other one (albedo is not part of the history: one plane)
-  float4* d_guidePN[2][2] = {};
-  int guideSet = 0;
-  float guideEye[3] = {}, guideCam[16] = {};  // the camera of the current guides
-  bool guidesValid = false;
-  unsigned guideVersion = 0;
-  int* d_guideOvf = nullptr;  // the guide kernel's own stack overflow area (frames in flight use d_ovf)
-  size_t guideOvfInts = 0;
-  float4* d_dn[2] = {};
-  float4* d_dnTm[2] = {};
-  const float4* denoised = nullptr;
-  // the temporal resolve: two resolved planes (the one the last resolve wrote and, after a commit,
-  // the history's), the image the last resolve wrote (one of the two, or the caller's), the history
-  float4* d_res[2] = {};
-  int resCur = 0;                  // the plane the next context-owned resolve writes
-  const float4* resolved = nullptr;
-  bool resolvedFresh = false;      // a resolve since the last commit / reset / pt_render_guides
-  bool histValid = false;
-  int histSet = 0, histRes = 0;    // the history's guide set and resolved plane
-  float histEye[3] = {}, histCam[16] = {};
-  // PT_FLAG_MOMENTS: the running means (m1, m2) of the sample luminance beside the running mean of
-  // the colour (mixMomentsKernel), and the frames they hold (0: not valid, see noteMoments)
-  float2* d_mom = nullptr;
-  uint32_t momFrames = 0;
-  // pt_denoise_var: l = lum(tm(input)), step A's variance, the passes' two (l, v) planes
-  float* d_lum = nullptr;
-  float* d_var0 = nullptr;
-  float2* d_lv[2] = {};
-  bool varianceValid = false;  // d_var0 holds the last pt_denoise_var's step A
-  // in-process multi-GPU (pt_config.n_devices > 1): this context renders as
-  // screen-tile rank 0 on device_ids[0] and owns the other ranks' contexts and
-  // the per-frame gather of their tiles into its accumulation
-  std::vector<pt_ctx*> peers;  // ranks 1 .. n_devices-1
-  struct GroupGather* gather = nullptr;
-};
-
-// The per-frame gather of an in-process device group. Rank k >= 1 packs its
-// tiles (packKernel) on its render stream into one of two send buffers; the
-// packed tiles travel to rank 0's device -- an RCCL send/recv group over the
-// communicator of all the devices, or hipMemcpyPeerAsync -- and are unpacked
-// into rank 0's accumulation on rank 0's communication stream. Rank 0's next
-// frame renders meanwhile (its own tiles only); a send buffer is packed again
-// only after its previous transfer completed.
-struct GroupGather {
-  int mode = PT_GATHER_COPY;
-  int n = 0;
-  hipStream_t cstream = nullptr;  // rank 0's device: receives, copies, unpacks
-  hipEvent_t done = nullptr;      // rank 0's device: the last frame's unpacks
-  bool pending = false;
-  unsigned frame = 0;
-  struct Peer {
-    int dev = 0;
-    size_t count = 0;                       // packed pixels (float4) of this rank
-    float* send[2] = {nullptr, nullptr};    // on the rank's device, PACK_F floats per slot
-    float* recv = nullptr;                  // on rank 0's device
-    hipStream_t mstream = nullptr;          // the rank's device: RCCL sends
-    hipEvent_t packed[2] = {nullptr, nullptr};
-    hipEvent_t sent[2] = {nullptr, nullptr};  // the buffer's transfer completed
-    bool sentValid[2] = {false, false};
-  };
-  std::vector<Peer> peer;  // ranks 1 .. n-1
-  ncclComm_t comms[PT_MAX_DEVICES] = {};
-  bool commsReady = false;
-};
-
 static std::string g_create_err;
-
-#define CK(expr)                                                                     \
-  do {                                                                               \
-    hipError_t e_ = (expr);                                                          \
-    if (e_ != hipSuccess) {                                                          \
-      ctx->err = std::string(#expr) + ": " + hipGetErrorString(e_);                  \
-      return PT_E_HIP;                                                               \
-    }                                                                                \
-  } while (0)
-
-static int fail(pt_ctx* ctx, int code, const std::string& msg) {
-  if (ctx) ctx->err = msg;
-  return code;
-}
-
-template <class T>
-static void dfree(T*& p) {
-  if (p) (void)hipFree((void*)p);
-  p = nullptr;
-}
 
 template <class T>
 static int upload(pt_ctx* ctx, T** dst, const std::vector<T>& src) {
@@ -1005,7 +746,7 @@ static int syncStreams(pt_ctx* ctx);
 static int ensureBasicImage(pt_ctx* ctx);
 
 // the temporal history shows another scene or another light after an upload
-static void dropHistory(pt_ctx* ctx) {
+extern "C++" void dropHistory(pt_ctx* ctx) {
   ctx->histValid = false;
   ctx->resolvedFresh = false;
 }
@@ -1499,7 +1240,7 @@ static uint32_t sampleIndex(const pt_config& c, uint32_t frameCounter) {
   return frameCounter * w + (uint32_t)c.sample_rank;
 }
 
-static SceneView sceneView(const pt_ctx* ctx) {
+extern "C++" SceneView sceneView(const pt_ctx* ctx) {
   SceneView s;
   s.geo = ctx->d_geo;
   s.pairs = ctx->d_pairs;
@@ -1634,7 +1375,6 @@ static int probePolicy(pt_ctx* ctx, uint32_t frameCounter, bool ordered, bool fa
   return f >= 6 && f < 15 ? PT_SPLIT_PCT : 0;
 }
 
-static PackParams packParams(const pt_ctx* ctx, int rank, int world);
 
 // the slot streams (and their events) of depth D
 static int ensureSlots(pt_ctx* ctx, int D) {
@@ -2096,7 +1836,7 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
 }
 
 // the caller's stream waits for the last pipelined frame's running-mean update
-static int joinPipe(pt_ctx* ctx) {
+extern "C++" int joinPipe(pt_ctx* ctx) {
   if (!ctx->mixPending) return PT_OK;
   CK(hipSetDevice(ctx->cfg.device_id));
   CK(hipStreamWaitEvent(ctx->stream, ctx->mixDone[ctx->lastCol], 0));
@@ -2187,7 +1927,7 @@ int pt_trace_closest(pt_ctx* ctx, const float* rays, int n, float* t_out, int* t
 }
 
 // a device group's rank-0 stream waits for the last gather (the whole image is in its accumulation)
-static int joinGather(pt_ctx* ctx) {
+extern "C++" int joinGather(pt_ctx* ctx) {
   GroupGather* g = ctx->gather;
   if (!g || !g->pending) return PT_OK;
   CK(hipSetDevice(ctx->cfg.device_id));
@@ -2294,7 +2034,7 @@ int pt_tonemap(pt_ctx* ctx, float limit, float gamma, float* rgb_out) {
   return PT_OK;
 }
 
-static PackParams packParams(const pt_ctx* ctx, int rank, int world) {
+extern "C++" PackParams packParams(const pt_ctx* ctx, int rank, int world) {
   PackParams p;
   p.width = ctx->cfg.width;
   p.height = ctx->cfg.height;
@@ -2357,421 +2097,6 @@ int pt_display_unpack(pt_ctx* ctx, int world, const void* const* dpacked, void* 
     d.count[k] = packParams(ctx, k, world).count;
   }
   CK(launchDisplayUnpack(d, world, reinterpret_cast<uchar4*>(dimage), ctx->stream));
-  return PT_OK;
-}
-
-// ------------------------------------------------------------ guide buffers and the denoised display
-static_assert(sizeof(pt_denoise_params) == PT_DENOISE_PARAMS_SIZE, "pt_denoise_params layout");
-
-void pt_denoise_defaults(pt_denoise_params* prm) {
-  if (!prm) return;
-  prm->passes = 5;
-  prm->sigma_c = 2.0f;
-  prm->sigma_z = 0.02f;
-  prm->sigma_a = 0.2f;
-  prm->normal_log2 = 6;
-  prm->limit = 1.5f;
-}
-
-int pt_denoise_params_size(void) { return (int)sizeof(pt_denoise_params); }
-
-// a context that can hold guides: a GL integrator with a scene
-static int guideContext(pt_ctx* ctx, const char* what) {
-  if (ctx->cfg.integrator == PT_BASIC_CPU_COMPAT)
-    return fail(ctx, PT_E_INVALID, std::string(what) + ": not for PT_BASIC_CPU_COMPAT contexts");
-  if (!ctx->d_bvh) return fail(ctx, PT_E_NOSCENE, std::string(what) + ": no scene");
-  return PT_OK;
-}
-static int guidesReady(pt_ctx* ctx, const char* what) {
-  if (int rc = guideContext(ctx, what)) return rc;
-  if (!ctx->guidesValid || ctx->guideVersion != ctx->sceneVersion)
-    return fail(ctx, PT_E_INVALID, std::string(what) + ": no guides of this scene (pt_render_guides first)");
-  return PT_OK;
-}
-
-int pt_render_guides(pt_ctx* ctx, const float eye[3], const float cameraRotate[16]) {
-  if (!ctx || !eye || !cameraRotate) return PT_E_INVALID;
-  if (int rc = guideContext(ctx, "pt_render_guides")) return rc;
-  CK(hipSetDevice(ctx->cfg.device_id));
-  const int W = ctx->cfg.width, H = ctx->cfg.height;
-  const size_t npix = (size_t)W * H;
-  // the set that is not the history's
-  const int set = ctx->histValid ? 1 - ctx->histSet : ctx->guideSet;
-  for (auto& g : ctx->d_guidePN[set])
-    if (!g) CK(hipMalloc(&g, npix * sizeof(float4)));
-  if (!ctx->d_guide[2]) CK(hipMalloc(&ctx->d_guide[2], npix * sizeof(float4)));
-  ctx->guideSet = set;
-  ctx->d_guide[0] = ctx->d_guidePN[set][0];
-  ctx->d_guide[1] = ctx->d_guidePN[set][1];
-  ctx->resolvedFresh = false;  // a resolve of the previous guides is not committed with these
-  const long tiles = (long)((W + 7) / 8) * ((H + 7) / 8);
-  const int grid = (int)std::min<long>((tiles + BLOCK / 64 - 1) / (BLOCK / 64), (long)ctx->numCU * 8);
-  // the kernel's own overflow area: frames in flight keep using d_ovf meanwhile
-  const int ovfDepth = ctx->maxStack > LDS_STACK ? ctx->maxStack - LDS_STACK / 2 : 0;
-  const size_t need = (size_t)grid * BLOCK * (size_t)ovfDepth;
-  if (need > ctx->guideOvfInts) {
-    CK(hipStreamSynchronize(ctx->stream));  // an earlier guide launch may still use the old area
-    dfree(ctx->d_guideOvf);
-    ctx->guideOvfInts = 0;
-    CK(hipMalloc(&ctx->d_guideOvf, need * sizeof(int)));
-    ctx->guideOvfInts = need;
-  }
-  GuideParams p;
-  p.scene = sceneView(ctx);
-  // the hit search of pt_trace_closest: the runtime's own tree, results reference-exact
-  p.scene.fast = ctx->fastReady && !(ctx->cfg.flags & (PT_FLAG_REFERENCE_TREE | PT_FLAG_COUNT_FETCHES)) ? 1 : 0;
-  p.width = W;
-  p.height = H;
-  std::memcpy(p.eye, eye, sizeof(p.eye));
-  std::memcpy(p.cam, cameraRotate, sizeof(p.cam));
-  p.posT = ctx->d_guide[0];
-  p.nrmTri = ctx->d_guide[1];
-  p.albedo = ctx->d_guide[2];
-  p.ovf = ovfDepth ? ctx->d_guideOvf : nullptr;
-  p.ovfDepth = ovfDepth;
-  const bool cull = !(ctx->cfg.flags & (PT_FLAG_NO_CULL | PT_FLAG_COUNT_FETCHES));
-  CK(launchGuides(p, grid, ctx->stream, cull));
-  ctx->guidesValid = true;
-  ctx->guideVersion = ctx->sceneVersion;
-  std::memcpy(ctx->guideEye, eye, sizeof(ctx->guideEye));
-  std::memcpy(ctx->guideCam, cameraRotate, sizeof(ctx->guideCam));
-  return PT_OK;
-}
-
-int pt_download_guides(pt_ctx* ctx, float* pos_t, float* nrm_tri, float* albedo) {
-  if (!ctx) return PT_E_INVALID;
-  if (int rc = guidesReady(ctx, "pt_download_guides")) return rc;
-  CK(hipSetDevice(ctx->cfg.device_id));
-  const size_t bytes = (size_t)ctx->cfg.width * ctx->cfg.height * sizeof(float4);
-  float* dst[3] = {pos_t, nrm_tri, albedo};
-  for (int k = 0; k < 3; k++)
-    if (dst[k]) CK(hipMemcpyAsync(dst[k], ctx->d_guide[k], bytes, hipMemcpyDefault, ctx->stream));  // host or device
-  CK(hipStreamSynchronize(ctx->stream));
-  return PT_OK;
-}
-
-int pt_guides_device_ptr(pt_ctx* ctx, void** pos_t, void** nrm_tri, void** albedo) {
-  if (!ctx) return PT_E_INVALID;
-  if (int rc = guidesReady(ctx, "pt_guides_device_ptr")) return rc;
-  if (pos_t) *pos_t = ctx->d_guide[0];
-  if (nrm_tri) *nrm_tri = ctx->d_guide[1];
-  if (albedo) *albedo = ctx->d_guide[2];
-  return PT_OK;
-}
-
-int pt_denoise(pt_ctx* ctx, const pt_denoise_params* prm, void* d_out_rgba) {
-  return pt_denoise_from(ctx, prm, nullptr, d_out_rgba);
-}
-
-int pt_denoise_from(pt_ctx* ctx, const pt_denoise_params* prm, const void* d_in_rgba, void* d_out_rgba) {
-  if (!ctx) return PT_E_INVALID;
-  if (int rc = guidesReady(ctx, "pt_denoise")) return rc;
-  pt_denoise_params P;
-  pt_denoise_defaults(&P);
-  if (prm) P = *prm;
-  if (P.passes < 1 || P.passes > 8) return fail(ctx, PT_E_INVALID, "pt_denoise: passes must be 1..8");
-  if (P.normal_log2 < -1 || P.normal_log2 > 10) return fail(ctx, PT_E_INVALID, "pt_denoise: normal_log2 must be -1..10");
-  if (!(P.limit > 0.0f)) return fail(ctx, PT_E_INVALID, "pt_denoise: limit must be > 0");
-  // the passes ping-pong through the context's two planes: an input that is one of them, or the
-  // output, would be overwritten while it is read
-  if (d_in_rgba && (d_in_rgba == d_out_rgba || d_in_rgba == ctx->d_dn[0] || d_in_rgba == ctx->d_dn[1]))
-    return fail(ctx, PT_E_INVALID, "pt_denoise_from: the input must not be the output or the context's denoised buffer");
-  // the accumulation as the frames rendered so far leave it
-  if (int rc = joinGather(ctx)) return rc;
-  if (int rc = joinPipe(ctx)) return rc;
-  CK(hipSetDevice(ctx->cfg.device_id));
-  const int W = ctx->cfg.width, H = ctx->cfg.height;
-  const size_t npix = (size_t)W * H;
-  for (int k = 0; k < 2; k++) {
-    if (!ctx->d_dn[k]) CK(hipMalloc(&ctx->d_dn[k], npix * sizeof(float4)));
-    if (!ctx->d_dnTm[k]) CK(hipMalloc(&ctx->d_dnTm[k], npix * sizeof(float4)));
-  }
-  const float4* in = d_in_rgba ? reinterpret_cast<const float4*>(d_in_rgba) : ctx->d_accum;
-  CK(launchAtrousTm(in, ctx->d_dnTm[0], (int)npix, P.limit, ctx->stream));
-  AtrousParams a;
-  a.width = W;
-  a.height = H;
-  a.posT = ctx->d_guide[0];
-  a.nrmTri = ctx->d_guide[1];
-  a.albedo = ctx->d_guide[2];
-  a.sigmaZ = P.sigma_z;
-  a.albDen = P.sigma_a * P.sigma_a;
-  a.albOn = P.sigma_a > 0.0f;
-  a.normalLog2 = P.normal_log2;
-  a.limit = P.limit;
-  for (int i = 0; i < P.passes; i++) {
-    const bool last = i == P.passes - 1;
-    const float sc = P.sigma_c * (1.0f / (float)(1 << i));  // halved every pass
-    a.stride = 1 << i;
-    a.colDen = sc * sc;
-    a.colOn = sc > 0.0f;
-    a.in = in;
-    a.tmIn = ctx->d_dnTm[i & 1];
-    a.out = last && d_out_rgba ? reinterpret_cast<float4*>(d_out_rgba) : ctx->d_dn[i & 1];
-    a.tmOut = last ? nullptr : ctx->d_dnTm[(i + 1) & 1];
-    CK(launchAtrous(a, ctx->stream));
-    in = a.out;
-  }
-  ctx->denoised = in;
-  return PT_OK;
-}
-
-int pt_denoised_device_ptr(pt_ctx* ctx, void** dptr) {
-  if (!ctx || !dptr) return PT_E_INVALID;
-  if (!ctx->denoised) return fail(ctx, PT_E_INVALID, "pt_denoised_device_ptr: no pt_denoise yet");
-  *dptr = const_cast<float4*>(ctx->denoised);
-  return PT_OK;
-}
-
-int pt_download_denoised(pt_ctx* ctx, float* rgba) {
-  if (!ctx || !rgba) return PT_E_INVALID;
-  if (!ctx->denoised) return fail(ctx, PT_E_INVALID, "pt_download_denoised: no pt_denoise yet");
-  CK(hipSetDevice(ctx->cfg.device_id));
-  const size_t bytes = (size_t)ctx->cfg.width * ctx->cfg.height * sizeof(float4);
-  CK(hipMemcpyAsync(rgba, ctx->denoised, bytes, hipMemcpyDefault, ctx->stream));  // host or device
-  CK(hipStreamSynchronize(ctx->stream));
-  return PT_OK;
-}
-
-int pt_display_denoised(pt_ctx* ctx, float limit, float gamma, void* dimage) {
-  if (!ctx || !dimage || !(limit > 0.0f)) return PT_E_INVALID;
-  if (!ctx->denoised) return fail(ctx, PT_E_INVALID, "pt_display_denoised: no pt_denoise yet");
-  CK(hipSetDevice(ctx->cfg.device_id));
-  PackParams p = packParams(ctx, 0, 1);  // every pixel: the denoised image is the whole frame
-  CK(launchDisplayOwn(p, ctx->denoised, limit, gamma, reinterpret_cast<uchar4*>(dimage), ctx->stream));
-  return PT_OK;
-}
-
-// ------------------------------------------------------------ sample moments and the variance-guided filter
-static_assert(sizeof(pt_denoise_var_params) == PT_DENOISE_VAR_PARAMS_SIZE, "pt_denoise_var_params layout");
-
-int pt_moments_frames(pt_ctx* ctx, uint32_t* frames) {
-  if (!ctx || !frames) return PT_E_INVALID;
-  *frames = ctx->d_mom ? ctx->momFrames : 0u;
-  return PT_OK;
-}
-
-int pt_download_moments(pt_ctx* ctx, float* m) {
-  if (!ctx || !m) return PT_E_INVALID;
-  if (!ctx->d_mom) return fail(ctx, PT_E_INVALID, "pt_download_moments: not a PT_FLAG_MOMENTS context");
-  if (int rc = joinPipe(ctx)) return rc;
-  CK(hipSetDevice(ctx->cfg.device_id));
-  const size_t bytes = (size_t)ctx->cfg.width * ctx->cfg.height * sizeof(float2);
-  CK(hipMemcpyAsync(m, ctx->d_mom, bytes, hipMemcpyDefault, ctx->stream));  // host or device
-  CK(hipStreamSynchronize(ctx->stream));
-  return PT_OK;
-}
-
-int pt_moments_device_ptr(pt_ctx* ctx, void** dptr) {
-  if (!ctx || !dptr) return PT_E_INVALID;
-  if (!ctx->d_mom) return fail(ctx, PT_E_INVALID, "pt_moments_device_ptr: not a PT_FLAG_MOMENTS context");
-  *dptr = ctx->d_mom;
-  return PT_OK;
-}
-
-void pt_denoise_var_defaults(pt_denoise_var_params* prm) {
-  if (!prm) return;
-  prm->passes = 5;
-  prm->sigma_l = 4.0f;
-  prm->sigma_z = 0.02f;
-  prm->sigma_a = 0.2f;
-  prm->normal_log2 = 6;
-  prm->limit = 1.5f;
-  prm->min_temporal = 8;
-}
-
-int pt_denoise_var_params_size(void) { return (int)sizeof(pt_denoise_var_params); }
-
-int pt_denoise_var(pt_ctx* ctx, const pt_denoise_var_params* prm, const void* d_in_rgba, void* d_out_rgba) {
-  if (!ctx) return PT_E_INVALID;
-  if (int rc = guidesReady(ctx, "pt_denoise_var")) return rc;
-  pt_denoise_var_params P;
-  pt_denoise_var_defaults(&P);
-  if (prm) P = *prm;
-  if (P.passes < 1 || P.passes > 8) return fail(ctx, PT_E_INVALID, "pt_denoise_var: passes must be 1..8");
-  if (P.normal_log2 < -1 || P.normal_log2 > 10)
-    return fail(ctx, PT_E_INVALID, "pt_denoise_var: normal_log2 must be -1..10");
-  if (!(P.limit > 0.0f)) return fail(ctx, PT_E_INVALID, "pt_denoise_var: limit must be > 0");
-  if (P.min_temporal < 2) return fail(ctx, PT_E_INVALID, "pt_denoise_var: min_temporal must be >= 2");
-  // the passes ping-pong through the context's two planes, as pt_denoise_from's
-  if (d_in_rgba && (d_in_rgba == d_out_rgba || d_in_rgba == ctx->d_dn[0] || d_in_rgba == ctx->d_dn[1]))
-    return fail(ctx, PT_E_INVALID, "pt_denoise_var: the input must not be the output or the context's denoised buffer");
-  // the accumulation and the moments as the frames rendered so far leave them
-  if (int rc = joinGather(ctx)) return rc;
-  if (int rc = joinPipe(ctx)) return rc;
-  CK(hipSetDevice(ctx->cfg.device_id));
-  const int W = ctx->cfg.width, H = ctx->cfg.height;
-  const size_t npix = (size_t)W * H;
-  for (int k = 0; k < 2; k++) {
-    if (!ctx->d_dn[k]) CK(hipMalloc(&ctx->d_dn[k], npix * sizeof(float4)));
-    if (!ctx->d_lv[k]) CK(hipMalloc(&ctx->d_lv[k], npix * sizeof(float2)));
-  }
-  if (!ctx->d_lum) CK(hipMalloc(&ctx->d_lum, npix * sizeof(float)));
-  if (!ctx->d_var0) CK(hipMalloc(&ctx->d_var0, npix * sizeof(float)));
-  const float4* in = d_in_rgba ? reinterpret_cast<const float4*>(d_in_rgba) : ctx->d_accum;
-  CK(launchVarLum(in, ctx->d_lum, (int)npix, P.limit, ctx->stream));
-  // step A: from the moments once they hold min_temporal frames, else (or without them) spatial
-  const float kf = ctx->d_mom ? (float)ctx->momFrames : 0.0f;
-  VarInitParams v;
-  v.width = W;
-  v.height = H;
-  v.in = in;
-  v.nrmTri = ctx->d_guide[1];
-  v.moments = ctx->d_mom && kf >= (float)P.min_temporal ? ctx->d_mom : nullptr;
-  v.lum = ctx->d_lum;
-  v.var0 = ctx->d_var0;
-  v.lv = ctx->d_lv[0];
-  v.kf = kf;
-  v.limit = P.limit;
-  CK(launchVarInit(v, ctx->stream));
-  ctx->varianceValid = true;
-  AtrousVarParams a;
-  a.width = W;
-  a.height = H;
-  a.posT = ctx->d_guide[0];
-  a.nrmTri = ctx->d_guide[1];
-  a.albedo = ctx->d_guide[2];
-  a.sigmaL = P.sigma_l;
-  a.sigmaZ = P.sigma_z;
-  a.albDen = P.sigma_a * P.sigma_a;
-  a.albOn = P.sigma_a > 0.0f;
-  a.normalLog2 = P.normal_log2;
-  a.limit = P.limit;
-  for (int i = 0; i < P.passes; i++) {
-    const bool last = i == P.passes - 1;
-    a.stride = 1 << i;
-    a.in = in;
-    a.lvIn = ctx->d_lv[i & 1];
-    a.out = last && d_out_rgba ? reinterpret_cast<float4*>(d_out_rgba) : ctx->d_dn[i & 1];
-    a.lvOut = last ? nullptr : ctx->d_lv[(i + 1) & 1];
-    CK(launchAtrousVar(a, ctx->stream));
-    in = a.out;
-  }
-  ctx->denoised = in;
-  return PT_OK;
-}
-
-int pt_download_variance(pt_ctx* ctx, float* v) {
-  if (!ctx || !v) return PT_E_INVALID;
-  if (!ctx->varianceValid) return fail(ctx, PT_E_INVALID, "pt_download_variance: no pt_denoise_var yet");
-  CK(hipSetDevice(ctx->cfg.device_id));
-  const size_t bytes = (size_t)ctx->cfg.width * ctx->cfg.height * sizeof(float);
-  CK(hipMemcpyAsync(v, ctx->d_var0, bytes, hipMemcpyDefault, ctx->stream));  // host or device
-  CK(hipStreamSynchronize(ctx->stream));
-  return PT_OK;
-}
-
-// ------------------------------------------------------------ the temporal resolve
-static_assert(sizeof(pt_temporal_params) == PT_TEMPORAL_PARAMS_SIZE, "pt_temporal_params layout");
-
-void pt_temporal_defaults(pt_temporal_params* prm) {
-  if (!prm) return;
-  prm->sigma_z = 0.02f;
-  prm->normal_cos = 0.9f;
-  prm->max_history = 32.0f;
-}
-
-int pt_temporal_params_size(void) { return (int)sizeof(pt_temporal_params); }
-
-int pt_temporal_resolve(pt_ctx* ctx, const pt_temporal_params* prm, uint32_t frames, void* d_out_rgba) {
-  if (!ctx) return PT_E_INVALID;
-  if (int rc = guidesReady(ctx, "pt_temporal_resolve")) return rc;
-  pt_temporal_params P;
-  pt_temporal_defaults(&P);
-  if (prm) P = *prm;
-  if (frames == 0) return fail(ctx, PT_E_INVALID, "pt_temporal_resolve: frames must be >= 1 (frameCounter + 1)");
-  if (!(P.sigma_z >= 0.0f)) return fail(ctx, PT_E_INVALID, "pt_temporal_resolve: sigma_z must be >= 0");
-  if (!(P.normal_cos >= -1.0f && P.normal_cos <= 1.0f))
-    return fail(ctx, PT_E_INVALID, "pt_temporal_resolve: normal_cos must be in [-1, 1]");
-  if (!(P.max_history >= 1.0f)) return fail(ctx, PT_E_INVALID, "pt_temporal_resolve: max_history must be >= 1");
-  // the accumulation as the frames rendered so far leave it
-  if (int rc = joinGather(ctx)) return rc;
-  if (int rc = joinPipe(ctx)) return rc;
-  CK(hipSetDevice(ctx->cfg.device_id));
-  const int W = ctx->cfg.width, H = ctx->cfg.height;
-  const size_t npix = (size_t)W * H;
-  float4* out = reinterpret_cast<float4*>(d_out_rgba);
-  if (!out) {
-    // never the history's plane: a second resolve recomputes from the same history
-    const int k = ctx->histValid ? 1 - ctx->histRes : ctx->resCur;
-    if (!ctx->d_res[k]) CK(hipMalloc(&ctx->d_res[k], npix * sizeof(float4)));
-    ctx->resCur = k;
-    out = ctx->d_res[k];
-  }
-  TemporalParams t;
-  t.width = W;
-  t.height = H;
-  t.accum = ctx->d_accum;
-  t.posT = ctx->d_guide[0];
-  t.nrmTri = ctx->d_guide[1];
-  t.hist = t.histPosT = t.histNrmTri = nullptr;
-  if (ctx->histValid) {
-    t.hist = ctx->d_res[ctx->histRes];
-    t.histPosT = ctx->d_guidePN[ctx->histSet][0];
-    t.histNrmTri = ctx->d_guidePN[ctx->histSet][1];
-  }
-  t.out = out;
-  for (int k = 0; k < 3; k++) {
-    t.eye[k] = ctx->histEye[k];
-    t.c0[k] = ctx->histCam[k];
-    t.c1[k] = ctx->histCam[4 + k];
-    t.c2[k] = ctx->histCam[8 + k];
-  }
-  t.sigmaZ = P.sigma_z;
-  t.normalCos = P.normal_cos;
-  t.maxHistory = P.max_history;
-  t.frames = (float)frames;
-  CK(launchTemporal(t, ctx->stream));
-  ctx->resolved = out;
-  ctx->resolvedFresh = true;
-  return PT_OK;
-}
-
-int pt_temporal_commit(pt_ctx* ctx) {
-  if (!ctx) return PT_E_INVALID;
-  if (int rc = guidesReady(ctx, "pt_temporal_commit")) return rc;
-  if (!ctx->resolvedFresh)
-    return fail(ctx, PT_E_INVALID, "pt_temporal_commit: no pt_temporal_resolve since the last commit, reset or pt_render_guides");
-  if (ctx->resolved != ctx->d_res[ctx->resCur])
-    return fail(ctx, PT_E_INVALID, "pt_temporal_commit: the last resolve went to a caller's buffer (resolve with NULL to commit)");
-  ctx->histRes = ctx->resCur;
-  ctx->histSet = ctx->guideSet;
-  std::memcpy(ctx->histEye, ctx->guideEye, sizeof(ctx->histEye));
-  std::memcpy(ctx->histCam, ctx->guideCam, sizeof(ctx->histCam));
-  ctx->histValid = true;
-  ctx->resolvedFresh = false;
-  return PT_OK;
-}
-
-int pt_temporal_reset(pt_ctx* ctx) {
-  if (!ctx) return PT_E_INVALID;
-  dropHistory(ctx);
-  return PT_OK;
-}
-
-int pt_resolved_device_ptr(pt_ctx* ctx, void** dptr) {
-  if (!ctx || !dptr) return PT_E_INVALID;
-  if (!ctx->resolved) return fail(ctx, PT_E_INVALID, "pt_resolved_device_ptr: no pt_temporal_resolve yet");
-  *dptr = const_cast<float4*>(ctx->resolved);
-  return PT_OK;
-}
-
-int pt_download_resolved(pt_ctx* ctx, float* rgba) {
-  if (!ctx || !rgba) return PT_E_INVALID;
-  if (!ctx->resolved) return fail(ctx, PT_E_INVALID, "pt_download_resolved: no pt_temporal_resolve yet");
-  CK(hipSetDevice(ctx->cfg.device_id));
-  const size_t bytes = (size_t)ctx->cfg.width * ctx->cfg.height * sizeof(float4);
-  CK(hipMemcpyAsync(rgba, ctx->resolved, bytes, hipMemcpyDefault, ctx->stream));  // host or device
-  CK(hipStreamSynchronize(ctx->stream));
-  return PT_OK;
-}
-
-int pt_display_resolved(pt_ctx* ctx, float limit, float gamma, void* dimage) {
-  if (!ctx || !dimage || !(limit > 0.0f)) return PT_E_INVALID;
-  if (!ctx->resolved) return fail(ctx, PT_E_INVALID, "pt_display_resolved: no pt_temporal_resolve yet");
-  CK(hipSetDevice(ctx->cfg.device_id));
-  PackParams p = packParams(ctx, 0, 1);  // every pixel: the resolved image is the whole frame
-  CK(launchDisplayOwn(p, ctx->resolved, limit, gamma, reinterpret_cast<uchar4*>(dimage), ctx->stream));
   return PT_OK;
 }
 

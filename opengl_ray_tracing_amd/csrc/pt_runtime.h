@@ -1,0 +1,284 @@
+// pt_runtime.h -- what the host files of the C-ABI share (pt_runtime.cpp: contexts, uploads, the
+// frame path, gather, stats; pt_post.cpp: the display post-processing): the context, the error
+// helpers, and the few functions of pt_runtime.cpp the post-processing calls. Internal: not installed.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "pt_abi.h"
+#include "pt_kernels.h"
+#include "pt_rccl.h"
+
+using namespace pt;
+
+static constexpr int EV_RING = 64;
+// Frames in flight: the default megakernel's (or regen kernel's) launch g (its pipeline
+// sequence number) runs on slot stream g % depth (8 by default) with its own work queues,
+// overflow stack, tile order and camera-ray results, and writes its sample colours to colour
+// buffer g % (2 * depth + 1). While k other launches are in flight its persistent grid is 1.5 /
+// (k + 1) of residency (renderOne), so the frames in flight share the GPU by space: their waves
+// are resident together, and a frame whose last long paths keep a few waves busy leaves the
+// rest of the machine to the others. Its running-mean update (mixKernel) runs on the caller's
+// stream, in frame order, once the launch's kernel has ended: the accumulation is updated in
+// frame order, the image is bit for bit the one of serial frames, and whatever the caller
+// queues behind a frame (pack, download, tonemap) follows its update with no further
+// cross-queue wait. No launch waits for a mix except the one of the launch 2 * depth + 1 back,
+// whose colour buffer it reuses.
+//
+// A launch may render a batch of consecutive frames of one camera (pt_render_frames_async,
+// RenderParams::nFrames): every frame's colours in its own part of the colour buffer, and one
+// mixKernel folds them into the running mean pixel by pixel in frame order. A small screen-tile
+// share (1/8 of the image) gives one frame too little work to fill the machine; a batch of
+// tile_world frames per launch is about one whole image's work, and the chain of running-mean
+// updates on the caller's stream -- one cross-queue wait and one launch per update, which set
+// an 8-way share's frame period before -- has one link per batch.
+// (Measured alternatives, DESIGN.md 4: a separate mix stream is twice as slow at small
+// shares -- each mix waited on two ~25 us cross-queue signals in a chain from mix to mix; and
+// with full-residency grids a mix waits for a CU slot behind the next frame's persistent
+// kernel, ~250 us on c2, which made deeper pipelines slower, not faster.)
+#ifndef PT_PIPE
+#define PT_PIPE 8  // frames in flight (PT_PIPE_DEPTH overrides; capped by the hardware queues)
+#endif
+static constexpr int PIPE = MAX_SLOTS;      // most frames in flight
+// colour buffers: a launch reuses the buffer of the launch 2 * depth + 1 back, whose running-mean
+// update is then long done -- with depth + 1 the wait made a slot's next frame follow the
+// running-mean update of the previous frame on another slot (two cross-queue hops), and an N = 8
+// share of c2 kept only ~3 of its 8 frames in flight
+static constexpr int COLS = 2 * MAX_SLOTS + 1;
+
+struct pt_ctx {
+  pt_config cfg{};
+  std::string err;
+  hipStream_t own = nullptr, stream = nullptr;
+  // Launch timing: a fixed ring of begin/end event pairs. Launch number i (since
+  // pt_create) records into pair i % EV_RING; a launch's elapsed time is folded
+  // into the running totals once its end event has completed (non-blocking on
+  // every new launch, blocking only when the ring is full or stats are read), so
+  // the cost per frame stays constant however long a caller renders.
+  hipEvent_t ev[2 * EV_RING] = {};
+  int evProbe[EV_RING] = {};    // probe slot of the launch in each ring position (-1 none)
+  int evGen[EV_RING] = {};      // probe generation it was tagged in
+  long long issued = 0, folded = 0;
+  double msTotal = 0.0;         // summed device time of the folded launches since the reset
+  float msLast = 0.0f;          // device time of the last folded launch
+  int launches = 0;             // render launches since the reset
+  long long frames = 0;         // frames those launches rendered (a batch launch renders several)
+  int tagSlot = -1;             // probe slot for the launch being issued (probePolicy)
+  int numCU = 0;
+  // scene
+  float4* d_geo = nullptr;
+  float4* d_pairs = nullptr;  // triangles i and i+1 component-interleaved (SceneView::pairs)
+  float4* d_hit = nullptr;   // per triangle: normals + material id (SceneView::hitRec)
+  float4* d_mats = nullptr;  // the distinct materials (SceneView::mats)
+  int nMats = 0;
+  float4* d_bvh = nullptr;
+  int nDevNodes = 0;  // internal nodes in d_bvh (device ids 0..nDevNodes-1)
+  // the runtime's own tree (uploadAccel; SceneView::fast) and the reference
+  // facts its results are checked against
+  bool fastReady = false;
+  float4* d_fbvh = nullptr;
+  float4* d_fpairs = nullptr;
+  int* d_fastTri = nullptr;
+  int* d_refParent = nullptr;
+  float4* d_refBox = nullptr;
+  float4* d_leafBox = nullptr;
+  int fRoot = REF_NONE, fnDev = 0, fDepth = 0;
+  // the same tree collapsed to 4-wide nodes (encodeWide4; the large-scene regen kernel)
+  float4* d_fbvh4 = nullptr;
+  bool fast4Ready = false;
+  int f4Root = REF_NONE, f4nDev = 0, f4Depth = 0;
+  // the last pt_upload_scene (pt_frame_stats upload_ms, accel_*)
+  float uploadMs = 0.0f, accelMs = 0.0f;
+  int accelDevice = -1, accelNodes = 0, accelDepth = 0;
+  int rootRef = REF_NONE;
+  int nTri = 0, nNodes = 0, depth = 0, maxStack = 0;
+  // env
+  float4* d_hdr = nullptr;
+  float2* d_cache = nullptr;  // sample table (x, y); the pdf lives in d_hdr[k].w
+  uint2* d_hdr8 = nullptr;    // the same texels compacted (pt_kernels.h Env), null = not exact
+  uint32_t* d_cache4 = nullptr;
+  uint32_t* d_cacheRow = nullptr;           // the sample table by rows (pt_kernels.h Env::cacheRow)
+  unsigned short* d_cacheY = nullptr;
+  float2* d_trig = nullptr;                  // SampleHdr's sines and cosines (Env::trig)
+  uint2* d_light = nullptr;                  // each sample-table entry's light-sample color and pdf (Env::light)
+  int hdrW = 0, hdrH = 0;
+  // BASIC shapes, the double image, the replayed random stream
+  double* d_shapes = nullptr;
+  int nShapes = 0;
+  double* d_basicImg = nullptr;
+  double* d_stream = nullptr;
+  long long* d_offsets = nullptr;
+  long long streamN = 0, nOffsets = 0;
+  unsigned long long* d_overruns = nullptr;
+  // frame state
+  float4* d_accum = nullptr;
+  // control block (pt_kernels.h CTL_*): padded queue counters (zeroed per
+  // launch), cumulative fetch stats, padded sharded cumulative ray counters
+  unsigned char* d_ctl = nullptr;
+  int* d_ovf = nullptr;
+  int* d_cost = nullptr;   // per slot: per-tile cost of its last frame, longest item, split state, estimate
+  int* d_order = nullptr;  // per slot: per-band work items for its next frame
+  bool lastFast = false;    // the last megakernel frame traversed the runtime's tree
+  bool lastRegen = false;   // the last frame ran the path-regeneration kernel
+  int lastWaves = 0;        // waves per SIMD of the last megakernel launch (occupancy query)
+  // tree / tile-split policy probe (probePolicy): frames since the probe (re)started,
+  // the summed frame times of each policy, the decision
+  int probeFrame = 0;
+  // camera-ray bins (pt_primary.hip) of the camera and scene they were built for
+  PrimaryBins bins;
+  bool binsValid = false;
+  float binEye[3] = {}, binCam[16] = {};
+  unsigned sceneVersion = 0, binVersion = 0;
+  // frames in flight (PIPE slots; see PIPE above)
+  bool pipe = false;                        // this context pipelines its megakernel frames
+  int pipeDepth = PT_PIPE;                  // frames in flight (slot streams in use), 1..PIPE
+  int pipeDepthBase = PT_PIPE;              // ... as chosen at creation (uploadScene may lower it for large scenes)
+  bool pipeDepthFixed = false;              // PT_PIPE_DEPTH set: no scene-dependent choice
+  // Frames of one pt_render_frames_async call rendered per launch (RenderParams::nFrames), at most:
+  // pt_config.frame_batch, else as many as make one launch about a whole image's work (tile_world
+  // frames of a screen-tile share, up to MAX_BATCH). Probe frames and frameCounter 0 run alone.
+  int batchCap = 1;
+  int colCap[COLS] = {};                    // frames each colour buffer holds
+  int primCap[PIPE] = {};                   // frames each slot's camera-ray results hold
+  int liveCap[PIPE] = {};                   // ... and each slot's live-item lists (regen kernels)
+  // the large-scene path (regen kernel at 4 waves/SIMD, 4-wide walk with dynamic ray fetch,
+  // camera-ray pass) on scenes of any size: -1 = for the Lambert integrator (c2 0.342 ->
+  // 0.251 ms/frame) and the MIS integrator at 2 bounces (round 5: c3 0.1443 -> 0.1331; c4's 8
+  // bounces keep the megakernel); PT_FLAG_REGEN / PT_FLAG_MEGAKERNEL choose per context,
+  // PT_REGEN_WIDE = 1 / 0 (environment) for every / no scene
+  int regenWide = -1;
+  bool solo = true;                         // PT_SOLO = 0 (environment): every pipelined launch on a slot stream
+  hipStream_t slotStream[PIPE] = {};
+  hipEvent_t kernelDone[PIPE] = {};         // slot's last frame kernel (+ reorder) ended
+  bool slotBusy[PIPE] = {};                 // kernelDone[k] has been recorded since the last sync
+  hipEvent_t mixDone[COLS] = {};            // colour buffer's last running-mean update
+  hipStream_t lastMixStream = nullptr;      // the stream the last update ran on (pt_set_stream may change it)
+  // camera-ray bins built on one slot's stream: binsBuilt is recorded after the build, and
+  // every other slot waits for it once before its first frame with those bins (binGen)
+  hipEvent_t binsBuilt = nullptr;
+  unsigned binGen = 0, binGenSeen[MAX_SLOTS] = {};
+  float* d_col[COLS] = {};                  // per-colour-buffer sample colours (COL_F floats per slot)
+  int2* d_prim[PIPE] = {};                  // per-slot camera-ray results (primaryKernel)
+  uint4* d_live[PIPE] = {};                 // per-slot live-item lists and their counts (liveListKernel)
+  int lastSlot = -1;                        // slot of the last pipelined frame
+  int lastCol = -1;                         // colour buffer of the last pipelined frame
+  bool mixPending = false;                  // a pipelined frame's update may still be running
+  unsigned long long frameNo = 0;           // pipelined frames issued
+  int probeN[4] = {0, 0, 0, 0};        // timed frames: runtime tree, uploaded tree (both unsplit), split
+  double probeMs[4] = {0.0, 0.0, 0.0, 0.0};
+  long long probeLast[4] = {-1, -1, -1, -1};  // launch number of each slot's last timed frame
+  int probeGen = 0;
+  int treeDecided = -1, splitDecided = -1;  // -1 probing, 0 off, 1 on
+  unsigned policyKey = 0, probedKey = ~0u;  // bumped by every scene / env upload; the key the decisions were made for
+  int orderCap = 0;        // work items per band in d_order
+  bool orderValid[PIPE] = {};
+  bool orderSplit[PIPE] = {};               // the slot's order list holds split items (a one-frame launch built it)
+  size_t ovfInts = 0;
+  // shards
+  int shardSize = 32, shardsX = 0, shardsY = 0, numItems = 0, perQueue = 0;
+  // scratch for queries / tonemap / pack
+  float* d_rays = nullptr;
+  float* d_t = nullptr;
+  int* d_tri = nullptr;
+  size_t traceCap = 0;
+  float* d_rgb = nullptr;
+  // guide buffers of the last pt_render_guides (valid for the scene version they were traced in) and
+  // the denoiser's images: two ping-pong colour planes, their tone-mapped planes, and the
+  // image the last pt_denoise wrote (one of the two, or the caller's)
+  float4* d_guide[3] = {};   // pos_t, nrm_tri, albedo of the current set (guideSet)
+  // pos_t / nrm_tri exist twice: pt_temporal_commit marks the current set as the history's, and
+  // pt_render_guides then writes the other one (albedo is not part of the history: one plane)
+  float4* d_guidePN[2][2] = {};
+  int guideSet = 0;
+  float guideEye[3] = {}, guideCam[16] = {};  // the camera of the current guides
+  bool guidesValid = false;
+  unsigned guideVersion = 0;
+  int* d_guideOvf = nullptr;  // the guide kernel's own stack overflow area (frames in flight use d_ovf)
+  size_t guideOvfInts = 0;
+  float4* d_dn[2] = {};
+  float4* d_dnTm[2] = {};
+  const float4* denoised = nullptr;
+  // the temporal resolve: two resolved planes (the one the last resolve wrote and, after a commit,
+  // the history's), the image the last resolve wrote (one of the two, or the caller's), the history
+  float4* d_res[2] = {};
+  int resCur = 0;                  // the plane the next context-owned resolve writes
+  const float4* resolved = nullptr;
+  bool resolvedFresh = false;      // a resolve since the last commit / reset / pt_render_guides
+  bool histValid = false;
+  int histSet = 0, histRes = 0;    // the history's guide set and resolved plane
+  float histEye[3] = {}, histCam[16] = {};
+  // PT_FLAG_MOMENTS: the running means (m1, m2) of the sample luminance beside the running mean of
+  // the colour (mixMomentsKernel), and the frames they hold (0: not valid, see noteMoments)
+  float2* d_mom = nullptr;
+  uint32_t momFrames = 0;
+  // pt_denoise_var: l = lum(tm(input)), step A's variance, the passes' two (l, v) planes
+  float* d_lum = nullptr;
+  float* d_var0 = nullptr;
+  float2* d_lv[2] = {};
+  bool varianceValid = false;  // d_var0 holds the last pt_denoise_var's step A
+  // in-process multi-GPU (pt_config.n_devices > 1): this context renders as
+  // screen-tile rank 0 on device_ids[0] and owns the other ranks' contexts and
+  // the per-frame gather of their tiles into its accumulation
+  std::vector<pt_ctx*> peers;  // ranks 1 .. n_devices-1
+  struct GroupGather* gather = nullptr;
+};
+
+// The per-frame gather of an in-process device group. Rank k >= 1 packs its
+// tiles (packKernel) on its render stream into one of two send buffers; the
+// packed tiles travel to rank 0's device -- an RCCL send/recv group over the
+// communicator of all the devices, or hipMemcpyPeerAsync -- and are unpacked
+// into rank 0's accumulation on rank 0's communication stream. Rank 0's next
+// frame renders meanwhile (its own tiles only); a send buffer is packed again
+// only after its previous transfer completed.
+struct GroupGather {
+  int mode = PT_GATHER_COPY;
+  int n = 0;
+  hipStream_t cstream = nullptr;  // rank 0's device: receives, copies, unpacks
+  hipEvent_t done = nullptr;      // rank 0's device: the last frame's unpacks
+  bool pending = false;
+  unsigned frame = 0;
+  struct Peer {
+    int dev = 0;
+    size_t count = 0;                       // packed pixels (float4) of this rank
+    float* send[2] = {nullptr, nullptr};    // on the rank's device, PACK_F floats per slot
+    float* recv = nullptr;                  // on rank 0's device
+    hipStream_t mstream = nullptr;          // the rank's device: RCCL sends
+    hipEvent_t packed[2] = {nullptr, nullptr};
+    hipEvent_t sent[2] = {nullptr, nullptr};  // the buffer's transfer completed
+    bool sentValid[2] = {false, false};
+  };
+  std::vector<Peer> peer;  // ranks 1 .. n-1
+  ncclComm_t comms[PT_MAX_DEVICES] = {};
+  bool commsReady = false;
+};
+
+#define CK(expr)                                                                     \
+  do {                                                                               \
+    hipError_t e_ = (expr);                                                          \
+    if (e_ != hipSuccess) {                                                          \
+      ctx->err = std::string(#expr) + ": " + hipGetErrorString(e_);                  \
+      return PT_E_HIP;                                                               \
+    }                                                                                \
+  } while (0)
+
+static inline int fail(pt_ctx* ctx, int code, const std::string& msg) {
+  if (ctx) ctx->err = msg;
+  return code;
+}
+
+template <class T>
+static void dfree(T*& p) {
+  if (p) (void)hipFree((void*)p);
+  p = nullptr;
+}
+
+// defined in pt_runtime.cpp; the library exports only pt_abi.h's names
+#pragma GCC visibility push(hidden)
+int joinGather(pt_ctx* ctx);  // the device group's gather of the last frame has landed in the accumulation
+int joinPipe(pt_ctx* ctx);    // the caller's stream waits for the last pipelined frame's running-mean update
+SceneView sceneView(const pt_ctx* ctx);
+PackParams packParams(const pt_ctx* ctx, int rank, int world);
+void dropHistory(pt_ctx* ctx);  // the temporal history shows another scene or another light after an upload
+#pragma GCC visibility pop

@@ -319,6 +319,22 @@ class Renderer:
         self._ck(self._lib.pt_guides_device_ptr(self._h, *[C.byref(x) for x in p]), "pt_guides_device_ptr")
         return tuple(x.value for x in p)
 
+    def _params(self, what, prm, defaults, params, names, ints=()):
+        """prm set by its *_defaults function, then from a method's **params: `names` are the
+        parameters it has, `ints` those of them that are integers."""
+        defaults(C.byref(prm))
+        for k, v in params.items():
+            if k not in names:
+                raise TypeError(f"{what}() has no parameter {k!r}")
+            setattr(prm, k, int(v) if k in ints else float(v))
+        return prm
+
+    def _image(self, download: str) -> np.ndarray:
+        """An (h, w, 4) f32 image through the ABI's download function of that name."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._ck(getattr(self._lib, download)(self._h, _fp(out)), download)
+        return out
+
     def denoise(self, out_dptr: int | None = None, download: bool = True, src_dptr: int | None = None, **params):
         """The edge-avoiding a-trous filter of the accumulation (pt_denoise) -- or, with src_dptr, of
         an H x W x 4 f32 device image such as resolved_device_ptr() (pt_denoise_from) -- steered by
@@ -326,12 +342,9 @@ class Renderer:
         pt_denoise_defaults). With out_dptr (H x W x 4 f32 device memory) asynchronous, returns
         None; without, returns the denoised image (h, w, 4) -- or, with download False, leaves it
         in the context's buffer (denoised_device_ptr, display_denoised) without synchronising."""
-        prm = _native.PtDenoiseParams()
-        self._lib.pt_denoise_defaults(C.byref(prm))
-        for k, v in params.items():
-            if k not in ("passes", "sigma_c", "sigma_z", "sigma_a", "normal_log2", "limit"):
-                raise TypeError(f"denoise() has no parameter {k!r}")
-            setattr(prm, k, int(v) if k in ("passes", "normal_log2") else float(v))
+        prm = self._params("denoise", _native.PtDenoiseParams(), self._lib.pt_denoise_defaults, params,
+                           ("passes", "sigma_c", "sigma_z", "sigma_a", "normal_log2", "limit"),
+                           ("passes", "normal_log2"))
         out_p = C.c_void_p(out_dptr) if out_dptr else None
         if src_dptr:
             self._ck(self._lib.pt_denoise_from(self._h, C.byref(prm), C.c_void_p(src_dptr), out_p), "pt_denoise_from")
@@ -339,9 +352,7 @@ class Renderer:
             self._ck(self._lib.pt_denoise(self._h, C.byref(prm), out_p), "pt_denoise")
         if out_dptr or not download:
             return None
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self._lib.pt_download_denoised(self._h, _fp(out)), "pt_download_denoised")
-        return out
+        return self._image("pt_download_denoised")
 
     def denoised_device_ptr(self) -> int:
         p = C.c_void_p()
@@ -379,20 +390,15 @@ class Renderer:
         sigma_a, normal_log2, limit, min_temporal (defaults: pt_denoise_var_defaults). Returns as
         denoise() does; the image is the context's denoised image (denoised_device_ptr,
         display_denoised)."""
-        prm = _native.PtDenoiseVarParams()
-        self._lib.pt_denoise_var_defaults(C.byref(prm))
-        for k, v in params.items():
-            if k not in ("passes", "sigma_l", "sigma_z", "sigma_a", "normal_log2", "limit", "min_temporal"):
-                raise TypeError(f"denoise_var() has no parameter {k!r}")
-            setattr(prm, k, int(v) if k in ("passes", "normal_log2", "min_temporal") else float(v))
+        prm = self._params("denoise_var", _native.PtDenoiseVarParams(), self._lib.pt_denoise_var_defaults, params,
+                           ("passes", "sigma_l", "sigma_z", "sigma_a", "normal_log2", "limit", "min_temporal"),
+                           ("passes", "normal_log2", "min_temporal"))
         out_p = C.c_void_p(out_dptr) if out_dptr else None
         self._ck(self._lib.pt_denoise_var(self._h, C.byref(prm), C.c_void_p(src_dptr) if src_dptr else None, out_p),
                  "pt_denoise_var")
         if out_dptr or not download:
             return None
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self._lib.pt_download_denoised(self._h, _fp(out)), "pt_download_denoised")
-        return out
+        return self._image("pt_download_denoised")
 
     def variance(self) -> np.ndarray:
         """The initial variance plane (h, w) of the last denoise_var (pt_download_variance)."""
@@ -408,19 +414,13 @@ class Renderer:
         committed; without, returns the resolved image (h, w, 4), .w = the sample count -- or, with
         download False, leaves it in the context's buffer (resolved_device_ptr, display_resolved,
         denoise(src_dptr=...)) without synchronising."""
-        prm = _native.PtTemporalParams()
-        self._lib.pt_temporal_defaults(C.byref(prm))
-        for k, v in params.items():
-            if k not in ("sigma_z", "normal_cos", "max_history"):
-                raise TypeError(f"temporal_resolve() has no parameter {k!r}")
-            setattr(prm, k, float(v))
+        prm = self._params("temporal_resolve", _native.PtTemporalParams(), self._lib.pt_temporal_defaults, params,
+                           ("sigma_z", "normal_cos", "max_history"))
         self._ck(self._lib.pt_temporal_resolve(self._h, C.byref(prm), int(frames) & 0xFFFFFFFF,
                                                C.c_void_p(out_dptr) if out_dptr else None), "pt_temporal_resolve")
         if out_dptr or not download:
             return None
-        out = np.empty((self.height, self.width, 4), np.float32)
-        self._ck(self._lib.pt_download_resolved(self._h, _fp(out)), "pt_download_resolved")
-        return out
+        return self._image("pt_download_resolved")
 
     def temporal_commit(self):
         """The last temporal_resolve's image and the current guides become the history (before the

@@ -7,33 +7,19 @@ a screen-tile split, the 8-bit display, the quality gate and the error paths.
 Reference: IS pass1.fsh:846-850 (the camera ray), :335-382 (hitBVH), :63-71 / :251-300 (the hit
 record); Dammertz et al., HPG 2010 (the filter); pass3.fsh:14-24 (tonemap and display).
 """
-import functools
-import re
-
 import numpy as np
 import pytest
 
 import denoise_ref as dr
 import oracle
+from post_common import INVALID, NOSCENE, _unorm8, bits, config, rc_of
 from opengl_ray_tracing_amd import Renderer, orbit_camera, scenes
-from opengl_ray_tracing_amd._native import PtError
 from opengl_ray_tracing_amd.scene import Material, Scene
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 TERMS_OFF = [dict(sigma_c=0.0), dict(sigma_z=0.0), dict(sigma_a=0.0), dict(normal_log2=-1)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-@functools.lru_cache(maxsize=None)
-def config(name):
-    cfg, tris, nodes, hdr = scenes.build_config(name)
-    eye, rot = orbit_camera(*cfg.camera)
-    return cfg, tris, nodes, hdr, eye, rot
 
 
 def triangle_scene():
@@ -181,13 +167,6 @@ def test_screen_tile_split_rank0_denoises_the_gathered_mean():
 
 
 # ------------------------------------------------------------------ display
-def _unorm8(x):
-    """round(clamp(x, 0, 1) * 255) as the display kernels compute it: one fused multiply-add
-    (exact in f64, then one rounding to f32), truncated."""
-    c = np.clip(np.nan_to_num(x.astype(F), nan=0.0), 0, 1).astype(np.float64)
-    return np.floor((c * 255.0 + 0.5).astype(F)).astype(np.uint8)
-
-
 @pytest.mark.parametrize("gamma", [0.0, 2.2])
 def test_display_denoised_is_pass3_of_the_denoised_image(gamma):
     """Every pixel's pass3 tonemap of the denoised image (the GPU's own f32 tonemap, pt_tonemap
@@ -233,16 +212,6 @@ def test_defaults_gain_at_least_2_db_on_the_gpu(name):
 
 
 # ------------------------------------------------------------------ errors
-def rc_of(fn, *a, **kw):
-    with pytest.raises(PtError) as e:
-        fn(*a, **kw)
-    assert str(e.value).split(": ", 1)[1], "pt_last_error text"
-    return int(re.search(r"failed with (-?\d+)", str(e.value)).group(1))
-
-
-INVALID, NOSCENE = -1, -3
-
-
 def test_error_paths():
     import torch
     cfg, tris, nodes, hdr, eye, rot = config("c2")

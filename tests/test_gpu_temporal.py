@@ -9,13 +9,13 @@ move); IS pass1.fsh:846-850 (the camera ray the projection inverts); pass3.fsh:1
 """
 import ctypes as C
 import functools
-import re
 
 import numpy as np
 import pytest
 
 import denoise_ref as dr
 import temporal_ref as tr
+from post_common import INVALID, NOSCENE, _unorm8, bits, device_plane, rc_of
 from opengl_ray_tracing_amd import Renderer, _native, orbit_camera, scenes
 from opengl_ray_tracing_amd._native import PtError
 
@@ -24,10 +24,6 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 FRAMES = 2
 PARAMS = [dict(), dict(sigma_z=0.001), dict(normal_cos=0.999), dict(max_history=1.0)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
 
 
 @functools.lru_cache(maxsize=None)
@@ -55,13 +51,6 @@ def render_camera(r, eye, rot, frames=FRAMES):
         r.render_frame(eye, rot, f)
     r.render_guides(eye, rot)
     return r.accum(), r.guides()
-
-
-def device_plane(h, w, dtype="float32"):
-    import torch
-    t = torch.zeros((h, w, 4), dtype=getattr(torch, dtype), device="cuda:0")
-    torch.cuda.synchronize()  # the fill (torch's stream) before the renderer's stream writes it
-    return t
 
 
 # ------------------------------------------------------------------ bit-exact against the restatement
@@ -237,13 +226,6 @@ def test_screen_tile_split_rank0_resolves_the_gathered_mean():
 
 
 # ------------------------------------------------------------------ display
-def _unorm8(x):
-    """round(clamp(x, 0, 1) * 255) as the display kernels compute it: one fused multiply-add
-    (exact in f64, then one rounding to f32), truncated."""
-    c = np.clip(np.nan_to_num(x.astype(F), nan=0.0), 0, 1).astype(np.float64)
-    return np.floor((c * 255.0 + 0.5).astype(F)).astype(np.uint8)
-
-
 @pytest.mark.parametrize("gamma", [0.0, 2.2])
 def test_display_resolved_is_pass3_of_the_resolved_image(gamma):
     """Every pixel's pass3 tonemap of the resolved image (the GPU's own f32 tonemap, pt_tonemap of
@@ -284,16 +266,6 @@ def test_uploads_and_reset_drop_the_history():
 
 
 # ------------------------------------------------------------------ errors
-def rc_of(fn, *a, **kw):
-    with pytest.raises(PtError) as e:
-        fn(*a, **kw)
-    assert str(e.value).split(": ", 1)[1], "pt_last_error text"
-    return int(re.search(r"failed with (-?\d+)", str(e.value)).group(1))
-
-
-INVALID, NOSCENE = -1, -3
-
-
 def test_error_paths():
     cfg, tris, nodes, hdr = config("c2")
     eye, rot = camera("c2")

@@ -10,7 +10,6 @@ Reference: Schied et al., "Spatiotemporal Variance-Guided Filtering" (HPG 2017);
 (the running mean whose weights the moments share); pass3.fsh:14-24 (tonemap and display).
 """
 import functools
-import re
 
 import numpy as np
 import pytest
@@ -18,8 +17,8 @@ import pytest
 import denoise_ref as dr
 import oracle
 import variance_ref as vr
-from opengl_ray_tracing_amd import Renderer, orbit_camera, scenes
-from opengl_ray_tracing_amd._native import PtError
+from post_common import INVALID, NOSCENE, _unorm8, bits, config, device_plane, rc_of
+from opengl_ray_tracing_amd import Renderer, scenes
 from opengl_ray_tracing_amd.renderer import FLAG_COUNT_FETCHES, FLAG_MEGAKERNEL, FLAG_SERIAL_FRAMES
 
 pytestmark = pytest.mark.gpu
@@ -28,17 +27,6 @@ F = np.float32
 SIZES = [(1, 1), (5, 3), (33, 31), (100, 76)]
 N = 7
 TERMS_OFF = [dict(sigma_l=0.0), dict(sigma_z=0.0), dict(sigma_a=0.0), dict(normal_log2=-1)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-@functools.lru_cache(maxsize=None)
-def config(name):
-    cfg, tris, nodes, hdr = scenes.build_config(name)
-    eye, rot = orbit_camera(*cfg.camera)
-    return cfg, tris, nodes, hdr, eye, rot
 
 
 def renderer(name, w, h, **kw):
@@ -65,13 +53,6 @@ def oracle_moments(name, w, h):
     acc.setflags(write=False)
     m.setflags(write=False)
     return acc, m
-
-
-def device_plane(h, w, dtype="float32"):
-    import torch
-    t = torch.zeros((h, w, 4), dtype=getattr(torch, dtype), device="cuda:0")
-    torch.cuda.synchronize()  # the fill (torch's stream) before the renderer's stream writes it
-    return t
 
 
 # ------------------------------------------------------------------ moments
@@ -200,12 +181,6 @@ def test_filter_without_moments_is_spatial(w, h):
         assert np.array_equal(bits(r.accum()), bits(acc))
 
 
-def _unorm8(x):
-    """round(clamp(x, 0, 1) * 255) as the display kernels compute it (test_gpu_denoise.py)."""
-    c = np.clip(np.nan_to_num(x.astype(F), nan=0.0), 0, 1).astype(np.float64)
-    return np.floor((c * 255.0 + 0.5).astype(F)).astype(np.uint8)
-
-
 def test_display_denoised_is_pass3_of_the_filtered_image():
     cfg, tris, nodes, hdr, eye, rot = config("c2")
     w, h = 100, 76
@@ -249,16 +224,6 @@ def test_quality_gates_on_the_gpu(name):
 
 
 # ------------------------------------------------------------------ errors
-def rc_of(fn, *a, **kw):
-    with pytest.raises(PtError) as e:
-        fn(*a, **kw)
-    assert str(e.value).split(": ", 1)[1], "pt_last_error text"
-    return int(re.search(r"failed with (-?\d+)", str(e.value)).group(1))
-
-
-INVALID, NOSCENE = -1, -3
-
-
 def test_create_rejects_the_forbidden_combinations():
     for kw in (dict(integrator="basic"), dict(flags=FLAG_COUNT_FETCHES), dict(flags=FLAG_SERIAL_FRAMES),
                dict(tile_world=2), dict(tile_world=2, tile_rank=1), dict(devices=[0, 0])):
