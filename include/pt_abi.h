@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 10 /* 2: in-process multi-GPU fields at the end of pt_config / pt_frame_stats;
+#define PT_ABI_VERSION 11 /* 2: in-process multi-GPU fields at the end of pt_config / pt_frame_stats;
                              3: scene-upload fields at the end of pt_frame_stats, pt_build_bvh_device;
                              4: BASIC shapes as doubles, its double image, the replayed random stream;
                              5: the displayed frame of a screen-tile split (pt_display_*);
@@ -40,7 +40,9 @@ extern "C" {
                                 pt_temporal_commit, pt_display_resolved) and pt_denoise_from; no existing
                                 struct changes;
                              10: per-pixel sample moments (PT_FLAG_MOMENTS, pt_download_moments) and the
-                                variance-guided filter (pt_denoise_var); no existing struct changes */
+                                variance-guided filter (pt_denoise_var); no existing struct changes;
+                             11: diagnostics only: pt_fmath_* ids 7-10 (the float approximations and
+                                ptm_sincosf) and pt_sph_texel_device; no existing struct changes */
 
 /* error codes */
 #define PT_OK 0
@@ -498,10 +500,16 @@ int pt_get_stats(pt_ctx* ctx, pt_frame_stats* stats);   /* synchronises the stre
 int pt_reset_stats(pt_ctx* ctx);
 
 /* Diagnostics: evaluate one include/pt_fmath.h function (0 sin, 1 cos, 2 atan2(x,y),
- * 3 asin, 4 log, 5 exp, 6 pow(x,y)) over n inputs on the host CPU or on the
+ * 3 asin, 4 log, 5 exp, 6 pow(x,y), 7 ptm_atan2f_fast(x,y), 8 ptm_asinf_fast, 9 / 10 the sine / the
+ * cosine that ptm_sincosf returns) over n inputs on the host CPU or on the
  * context's GPU; the two must agree bit for bit. */
 int pt_fmath_host(int fn, const float* x, const float* y, int n, float* out);
 int pt_fmath_device(pt_ctx* ctx, int fn, const float* x, const float* y, int n, float* out);
+/* Diagnostics: the sky texel y * W + x that the frame kernels' fast decision (pt_device.h sphTexel)
+ * and its correctly rounded fallback (sphTexelExact) give for each of n directions (dirs: n x 3 f32),
+ * evaluated on the directions exactly as given (not normalised), for a W x H map (W * H < 2^31).
+ * Needs no env upload. The two outputs must be equal for every direction. */
+int pt_sph_texel_device(pt_ctx* ctx, int W, int H, const float* dirs, int n, int* texel, int* texel_exact);
 
 #ifdef __cplusplus
 }

@@ -13,11 +13,11 @@ from . import _build
 
 _lib = None
 
-ABI_VERSION = 10  # include/pt_abi.h PT_ABI_VERSION
+ABI_VERSION = 11  # include/pt_abi.h PT_ABI_VERSION
 # an older tuning build (tools/tune.py A/B against a previous round's library) loads when its structs
 # match: ABI 7 only added pt_unpack_ranks, ABI 8 the guide buffers and the denoiser, ABI 9 the
-# temporal resolve and ABI 10 the sample moments and the variance-guided filter, which such a build
-# does not have
+# temporal resolve, ABI 10 the sample moments and the variance-guided filter and ABI 11 the
+# diagnostics of the sky texel decision, which such a build does not have
 ABI_STRUCTS_SINCE = 6
 c_float_p = C.POINTER(C.c_float)
 c_double_p = C.POINTER(C.c_double)
@@ -143,6 +143,7 @@ SIGNATURES = {
     "pt_reset_stats": (C.c_int, [C.c_void_p]),
     "pt_fmath_host": (C.c_int, [C.c_int, c_float_p, c_float_p, C.c_int, c_float_p]),
     "pt_fmath_device": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, C.c_int, c_float_p]),
+    "pt_sph_texel_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_int, c_int_p, c_int_p]),
     # pt_scene.h
     "pt_material_default": (None, [C.POINTER(PtMaterial)]),
     "pt_scene_create": (C.c_int, [C.POINTER(C.c_void_p)]),

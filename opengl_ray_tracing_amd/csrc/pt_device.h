@@ -276,8 +276,9 @@ __device__ __forceinline__ void toSpherical(V3 v, float& u, float& w) {
 // correctly rounded atan2 / asin -- decided by their float approximations (include/pt_fmath.h
 // ptm_*_fast, at most 4 / 3 ulp) whenever the approximate texel coordinates lie farther from a
 // texel edge than the approximation can move them (4e-7 of the map's size: the bound from those ulps
-// through toSpherical's float operations is 3e-7, the largest difference measured over 4e6 random
-// directions 1.2e-7), else by the correctly rounded functions themselves. The same texel either way;
+// through toSpherical's float operations is 3e-7, the largest difference measured 1.8e-7 over
+// directions aimed at texel edges, poles and the seam of eight map sizes: tests/test_gpu_env.py,
+// tests/sph_texel_ref.py), else by the correctly rounded functions themselves. The same texel either way;
 // c2's sky lookups (every camera ray and bounce ray that escapes) at the float functions' cost
 // (c2 0.189 -> ~0.174 ms per frame)
 // (the correctly rounded fallback: a call, so its double-precision registers are not the caller's)

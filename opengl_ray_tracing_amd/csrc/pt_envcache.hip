@@ -163,7 +163,9 @@ __global__ void envCompactKernel(const float4* hdr, const float2* cache, int w, 
   hdr8[k] = t;
   const float2 q = cache[k];
   const float fx = rintf(q.x * (float)w), fy = rintf(q.y * (float)h);
-  bool okc = fx >= 0.0f && fx <= 65535.0f && fy >= 0.0f && fy <= 65535.0f;
+  // (entries 0 .. w and 0 .. h only: Env::trig holds w + h + 2 angles and Env::light (w + 1)(h + 1)
+  // entries, which sampleHdrDir indexes with them; a caller's table may hold an x or y above 1)
+  bool okc = fx >= 0.0f && fx <= (float)w && fy >= 0.0f && fy <= (float)h;
   const uint32_t v = okc ? ((uint32_t)fx | (uint32_t)fy << 16) : 0u;
   const float2 e = decodeCache4(v, w, h);
   okc = okc && __float_as_uint(e.x) == __float_as_uint(q.x) && __float_as_uint(e.y) == __float_as_uint(q.y);

@@ -514,6 +514,7 @@ hipError_t launchTonemap(const float4* accum, float* rgb, int n, float limit, fl
 constexpr int PACK_F = 3;
 hipError_t launchPack(const PackParams& p, const float4* accum, float* packed, hipStream_t s);
 hipError_t launchFmath(int fn, const float* x, const float* y, int n, float* out, hipStream_t s);
+hipError_t launchSphTexel(int W, int H, const float* dirs, int n, int* texel, int* texelExact, hipStream_t s);
 hipError_t launchDisplayPack(const PackParams& p, const float4* accum, float limit, float gamma, uint8_t* packed,
                              hipStream_t s);
 hipError_t launchDisplayOwn(const PackParams& p, const float4* accum, float limit, float gamma, uchar4* image,

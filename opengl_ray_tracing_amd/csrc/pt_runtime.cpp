@@ -2241,18 +2241,25 @@ static float fmathHost(int fn, float x, float y) {
     case 3: return ptm_asinf(x);
     case 4: return ptm_logf(x);
     case 5: return ptm_expf(x);
-    default: return ptm_powf(x, y);
+    case 6: return ptm_powf(x, y);
+    case 7: return ptm_atan2f_fast(x, y);
+    case 8: return ptm_asinf_fast(x);
+    default: {  // 9, 10: the sine and the cosine of ptm_sincosf
+      float s, c;
+      ptm_sincosf(x, &s, &c);
+      return fn == 9 ? s : c;
+    }
   }
 }
 
 int pt_fmath_host(int fn, const float* x, const float* y, int n, float* out) {
-  if (fn < 0 || fn > 6 || n < 0 || (n > 0 && (!x || !out))) return PT_E_INVALID;
+  if (fn < 0 || fn > 10 || n < 0 || (n > 0 && (!x || !out))) return PT_E_INVALID;
   for (int i = 0; i < n; i++) out[i] = fmathHost(fn, x[i], y ? y[i] : 0.0f);
   return PT_OK;
 }
 
 int pt_fmath_device(pt_ctx* ctx, int fn, const float* x, const float* y, int n, float* out) {
-  if (!ctx || fn < 0 || fn > 6 || n < 0 || (n > 0 && (!x || !out))) return PT_E_INVALID;
+  if (!ctx || fn < 0 || fn > 10 || n < 0 || (n > 0 && (!x || !out))) return PT_E_INVALID;
   if (n == 0) return PT_OK;
   CK(hipSetDevice(ctx->cfg.device_id));
   float *dx = nullptr, *dy = nullptr, *dout = nullptr;
@@ -2269,6 +2276,26 @@ int pt_fmath_device(pt_ctx* ctx, int fn, const float* x, const float* y, int n, 
   CK(hipFree(dx));
   CK(hipFree(dy));
   CK(hipFree(dout));
+  return PT_OK;
+}
+
+int pt_sph_texel_device(pt_ctx* ctx, int W, int H, const float* dirs, int n, int* texel, int* texel_exact) {
+  if (!ctx || W < 1 || H < 1 || (int64_t)W * H > INT32_MAX || n < 0 || (n > 0 && (!dirs || !texel || !texel_exact)))
+    return PT_E_INVALID;
+  if (n == 0) return PT_OK;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  float* dd = nullptr;
+  int* dt = nullptr;  // texel, then texel_exact
+  const size_t bt = (size_t)n * sizeof(int);
+  CK(hipMalloc(&dd, (size_t)n * 3 * sizeof(float)));
+  CK(hipMalloc(&dt, 2 * bt));
+  CK(hipMemcpy(dd, dirs, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
+  CK(launchSphTexel(W, H, dd, n, dt, dt + n, ctx->stream));
+  CK(hipStreamSynchronize(ctx->stream));
+  CK(hipMemcpy(texel, dt, bt, hipMemcpyDeviceToHost));
+  CK(hipMemcpy(texel_exact, dt + n, bt, hipMemcpyDeviceToHost));
+  CK(hipFree(dd));
+  CK(hipFree(dt));
   return PT_OK;
 }
 

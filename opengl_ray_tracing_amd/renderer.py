@@ -456,5 +456,27 @@ class Renderer:
                           s.accel_build_ms, s.accel_device, s.accel_nodes, s.accel_depth, s.regen, s.frames,
                           s.frame_batch, s.env_compact, s.tree4_nodes)
 
+    def fmath_device(self, fn: int, x, y=None) -> np.ndarray:
+        """Diagnostics: include/pt_fmath.h function `fn` (pt_fmath_device's ids 0..10) of x (and y)
+        on this context's GPU; pt_fmath_host gives the same bits on the CPU."""
+        x = np.ascontiguousarray(x, np.float32)
+        y = None if y is None else np.ascontiguousarray(y, np.float32)
+        out = np.empty_like(x)
+        self._ck(self._lib.pt_fmath_device(self._h, int(fn), _fp(x), None if y is None else _fp(y), x.size, _fp(out)),
+                 "pt_fmath_device")
+        return out
+
+    def sph_texel(self, w: int, h: int, dirs):
+        """Diagnostics (pt_sph_texel_device): the sky texel y * w + x of each direction (n x 3, used
+        as given, not normalised) in a w x h map, by the kernels' fast decision and by its correctly
+        rounded fallback: (texel, texel_exact), int32 each."""
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        n = d.shape[0]
+        t = np.empty(n, np.int32)
+        te = np.empty(n, np.int32)
+        self._ck(self._lib.pt_sph_texel_device(self._h, int(w), int(h), _fp(d), n, t.ctypes.data_as(_native.c_int_p),
+                                               te.ctypes.data_as(_native.c_int_p)), "pt_sph_texel_device")
+        return t, te
+
     def reset_stats(self):
         self._ck(self._lib.pt_reset_stats(self._h), "pt_reset_stats")

@@ -101,3 +101,37 @@ def test_hdr_cache_properties():
     hist = np.bincount(np.clip(xs, 0, hdr.shape[1] - 1), minlength=hdr.shape[1]).astype(np.float64)
     marg = lum.sum(0) / lum.sum()
     assert np.corrcoef(hist / hist.sum(), marg)[0, 1] > 0.9
+
+
+# ---- the maps at the edges of the env-map path (tests/env_maps.py)
+import env_maps  # noqa: E402
+
+
+def test_rgbe_quantise_is_what_a_radiance_texel_decodes_to():
+    """rgbe_quantise's texels are m * 2^(E - 136) with integer m < 256, the largest in [128, 256) --
+    and a decoded Radiance file is its own quantisation."""
+    img = env_maps.random_map(37, 19, 3)
+    mx = img.max(-1)
+    _, ex = np.frexp(mx)
+    m = img * np.ldexp(np.float32(1), 8 - ex)[..., None]
+    assert np.array_equal(m, np.floor(m)) and m.max() <= 255 and (m.max(-1)[mx > 0] >= 128).all()
+    assert len(np.unique(ex)) >= 8  # several exponent bytes
+    hdr = load_hdr(scenes.HDR_FILES["peppermint"])
+    assert np.array_equal(env_maps.rgbe_quantise(hdr), hdr)
+
+
+@pytest.mark.parametrize("name", env_maps.CACHE_MAP_NAMES)
+def test_hdr_cache_matches_oracle_on_degenerate_maps(name):
+    """calculate_hdr_cache equals the oracle's restatement bit for bit, NaN as NaN, on maps with one
+    texel, odd sizes, black rows, black columns (zero marginals, whose conditional CDFs are NaN: a
+    search in one ends at entry 0) and no light at all (every pdf NaN). (None of these maps has a
+    table entry x = w or y = h -- a CDF would have to end below the last xi -- so the GPU tests put
+    such entries into a caller's table.)"""
+    hdr = env_maps.cache_maps()[name]
+    a = calculate_hdr_cache(hdr)
+    b = oracle.hdr_cache(hdr)
+    assert a.shape == hdr.shape and env_maps.same_bits_or_nan(a, b)
+    if name == "black 8x4":
+        assert np.isnan(a[..., 2]).all()
+    else:
+        assert np.isfinite(a).all() and 0 <= a[..., :2].min() and a[..., 0].max() <= 1 and a[..., 1].max() <= 1
