@@ -55,7 +55,7 @@ SOURCES = {
     "pt_moments.o": ("hip", CSRC / "pt_moments.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]),
     "pt_variance.o": ("hip", CSRC / "pt_variance.hip", [CSRC / "pt_atrous.h", CSRC / "pt_device.h", CSRC / "pt_kernels.h",
                                                          INCLUDE / "pt_fmath.h"]),
-    "pt_runtime.o": ("cxx", CSRC / "pt_runtime.cpp", [CSRC / "pt_runtime.h", CSRC / "pt_kernels.h", CSRC / "pt_accel.h",
+    "pt_runtime.o": ("cxx", CSRC / "pt_runtime.cpp", [CSRC / "pt_runtime.h", CSRC / "pt_plan.h", CSRC / "pt_kernels.h", CSRC / "pt_accel.h",
                                                        INCLUDE / "pt_abi.h", INCLUDE / "pt_scene.h", INCLUDE / "pt_fmath.h",
                                                        CSRC / "pt_rccl.h"]),
     "pt_post.o": ("cxx", CSRC / "pt_post.cpp", [CSRC / "pt_runtime.h", CSRC / "pt_kernels.h", INCLUDE / "pt_abi.h",
@@ -147,6 +147,21 @@ def build_abi_caller(force: bool = False) -> Path:
     return ABI_CALLER
 
 
+PLAN_TABLE_SRC = ROOT / "tests" / "native" / "plan_table.cpp"
+PLAN_TABLE = ROOT / "tests" / "native" / "plan_table"
+
+
+def build_plan_table(force: bool = False) -> Path:
+    """Test infrastructure: the frame path's launch policy (csrc/pt_plan.h) on contexts filled by hand
+    (tests/native/plan_table.cpp), host-only: the HIP headers for the types, no HIP library."""
+    deps = [PLAN_TABLE_SRC, CSRC / "pt_plan.h", CSRC / "pt_runtime.h", CSRC / "pt_kernels.h", CSRC / "pt_rccl.h",
+            INCLUDE / "pt_abi.h"]
+    if force or _stale(PLAN_TABLE, deps):
+        _run(["g++", "-std=c++17", "-O1", "-Wall", "-Wno-unused-function", "-D__HIP_PLATFORM_AMD__", f"-I{ROCM}/include",
+              f"-I{INCLUDE}", f"-I{CSRC}", str(PLAN_TABLE_SRC), "-o", str(PLAN_TABLE)])
+    return PLAN_TABLE
+
+
 def build_oracle(force: bool = False) -> Path:
     """Test infrastructure only (see oracle/pt_oracle.h)."""
     src = [ORACLE_DIR / "pt_oracle.c", ORACLE_DIR / "pt_oracle.h", ORACLE_DIR / "Makefile", INCLUDE / "pt_fmath.h"]
@@ -159,5 +174,6 @@ if __name__ == "__main__":
     build_native(force="--force" in sys.argv, verbose=True)
     build_oracle(force="--force" in sys.argv)
     build_abi_caller(force="--force" in sys.argv)
+    build_plan_table(force="--force" in sys.argv)
     print(LIB)
     print(ORACLE_LIB)

@@ -23,33 +23,20 @@
 #include "pt_accel.h"
 #include "pt_fmath.h"
 #include "pt_kernels.h"
+#include "pt_plan.h"
 #include "pt_rccl.h"
 #include "pt_runtime.h"
 #include "pt_scene.h"
 
 using namespace pt;
 
-// 32: c2's 1/8 share in the 20-frame bench window at 4 hardware queues 0.0417 -> 0.0351 ms per
-// frame (its 20 frames one launch instead of 16 + 4), 1/4 share 0.0593 -> 0.0569, c4 0.2736 -> 0.2701
-#ifndef PT_MAX_BATCH
-#define PT_MAX_BATCH 32
-#endif
-static constexpr int MAX_BATCH = PT_MAX_BATCH;  // most frames per launch (pt_render_frames_async)
 // a launch of one frame while nothing else is in flight mixes its samples into the running mean in
 // its own kernels (renderOne: no colour buffer, no mixKernel launch)
 #ifndef PT_DIRECT_SOLO
 #define PT_DIRECT_SOLO 1
 #endif
-// a single frame launched while nothing else is in flight (a display() call) runs on the megakernel
-#ifndef PT_CALL_MEGAKERNEL
-#define PT_CALL_MEGAKERNEL 1
-#endif
 static_assert(PT_PIPE >= 1 && PT_PIPE <= PIPE, "PT_PIPE: 1..MAX_SLOTS");
 static_assert(PIPE * NUM_QUEUES * CTL_LINE_INTS * 4 <= (int)CTL_STATS, "queue counters of every slot fit the control block");
-
-#ifndef PT_TILE_GROUP
-#define PT_TILE_GROUP 1  // tiles ordered by cost in groups of this many consecutive tiles (1 measured best)
-#endif
 
 static std::string g_create_err;
 
@@ -60,6 +47,30 @@ static int upload(pt_ctx* ctx, T** dst, const std::vector<T>& src) {
   CK(hipMalloc(dst, src.size() * sizeof(T)));
   CK(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
   return PT_OK;
+}
+
+// One family of per-frame buffers -- the colour buffers, the slots' camera-ray results or their
+// live-item lists -- with room in bufs[idx] for the launch's `frames` frames. Every buffer of the n a
+// pipelined context uses (n = 0: unpiped, bufs[idx] alone) is allocated at the first launch that uses
+// any, so no later launch -- a timed one -- waits for an allocation (c2's 1/8 share: a 19 us hipMalloc
+// before the sixth launch's first kernel). A buffer too small is freed after wait() -- its last
+// reader -- and allocated again (each buffer grows once, to batchCap). bytes(cap): of cap frames.
+template <class T, class Bytes, class Wait>
+static int frameBuffer(pt_ctx* ctx, T** bufs, int* caps, int n, int idx, int frames, int cap, Bytes bytes, Wait wait) {
+  auto alloc = [&](int k) -> int {
+    CK(hipMalloc(&bufs[k], bytes(cap)));
+    caps[k] = cap;
+    return PT_OK;
+  };
+  for (int k = 0; k < n; k++)
+    if (!bufs[k])
+      if (int rc = alloc(k)) return rc;
+  if (caps[idx] >= frames) return PT_OK;
+  if (bufs[idx]) {
+    CK(wait());
+    dfree(bufs[idx]);
+  }
+  return alloc(idx);
 }
 
 extern "C" {
@@ -74,45 +85,6 @@ int pt_device_count(int* n) {
 }
 
 const char* pt_last_error(pt_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
-
-// Frames per launch of pt_render_frames_async: pt_config.frame_batch, else whole images' work per
-// launch in multiples of tile_world frames, at most MAX_BATCH:
-//  * 2 x for the Lambert regen kernel -- one image's is enough to fill the machine, the second
-//    halves the launches and running-mean updates per frame: c2 0.244 -> 0.231 ms per frame at
-//    N = 1, c2's 1/8 share 0.0354 -> 0.0344 (profiles/r4); 3 and 4 measured no better;
-//  * 4 x for the megakernel (Disney/MIS on small scenes), whose longest-first launches end in their
-//    longest tiles: c4 at N = 1 0.2566 -> 0.2531 ms per frame over 200 frames and 0.3288 -> 0.2860
-//    over 20 from an idle GPU, N = 2 0.139 -> 0.131, N = 4 / 8 equal (profiles/r4/batch_c4/);
-//  * 1 x on large Disney/MIS scenes, whose frames are long already (c5 5.66 ms at 1, 5.86 at 2).
-// With few hardware queues (GPU_MAX_HW_QUEUES 4, HIP's default and the GPU box's: 2 frames in flight)
-// a launch takes more frames, so that about as much work is in flight: Lambert 8 x, Disney/MIS 16 x,
-// large scenes 2 x (round 5, 4 queues, the driver's 20-frame bench window from an idle GPU: c2 at
-// 2 / 4 / 6 / 8 / 12 / 16 frames per launch 0.218 / 0.196 / 0.187 / 0.184 / 0.178 / 0.184 ms per
-// frame; c4 at 4 / 8 / 16 0.342 / 0.302 / 0.271; c5 at 1 / 2 4.59 / 4.34; c2's shares at 20 frames,
-// N = 2 / 4 / 8, at 2 x N 0.116 / 0.066 / 0.041 and 4 x N 0.107 / 0.060 / 0.041 ms).
-static int defaultBounce(int integ);
-
-static int batchFor(const pt_ctx* ctx, bool wideScene) {
-  const pt_config& c = ctx->cfg;
-  if (c.frame_batch > 0) return std::min(c.frame_batch, MAX_BATCH);
-  const bool fewQueues = ctx->pipeDepth <= 3;
-#ifndef PT_BATCH_LAMBERT
-#define PT_BATCH_LAMBERT 12  // c2, 20 frames: 8 + 8 + 4 -> 12 + 8, 0.1789-0.1802 -> 0.1707-0.1729 ms (10: 0.1949); 200 frames equal
-#endif
-#ifndef PT_BATCH_MIS
-#define PT_BATCH_MIS 16
-#endif
-#ifndef PT_BATCH_MIS_MK
-// MIS beyond its shader's 2 bounces renders on the megakernel (c4): 32 frames per launch, c4 0.2599
-// -> 0.2327 ms over 20 frames (one launch instead of 16 + 4), 0.2389 -> 0.2303 over 100; the MIS
-// regen kernel (c3) keeps 16 (24 / 32: 0.1107 -> 0.1122 / 0.1148)
-#define PT_BATCH_MIS_MK 32
-#endif
-  const int mb = c.max_bounce >= 0 ? c.max_bounce : defaultBounce(c.integrator);
-  const int mis = c.integrator == 2 && mb > 2 ? PT_BATCH_MIS_MK : PT_BATCH_MIS;
-  const int m = wideScene ? (fewQueues ? 2 : 1) : c.integrator == 0 ? (fewQueues ? PT_BATCH_LAMBERT : 2) : (fewQueues ? mis : 4);
-  return std::max(1, std::min(m * std::max(1, c.tile_world), MAX_BATCH));
-}
 
 static int createOne(pt_ctx** out, const pt_config* cfg) {
   if (!out || !cfg) return PT_E_INVALID;
@@ -183,30 +155,21 @@ static int createOne(pt_ctx** out, const pt_config* cfg) {
   const int owned = (numShards - cfg->tile_rank + cfg->tile_world - 1) / cfg->tile_world;
   ctx->numItems = owned * (ss / 8) * (ss / 8);
   ctx->perQueue = (ctx->numItems + NUM_QUEUES - 1) / NUM_QUEUES;
-  // the default megakernel and the regen kernel pipeline their frames (not BASIC, the fetch
-  // counter or PT_FLAG_SERIAL_FRAMES)
   // the path-regeneration kernel with the 4-wide walk for every integrator on any scene
   // (PT_REGEN_WIDE = 1; 0: never; unset: Lambert frames and large Disney/MIS scenes)
   if (const char* e = std::getenv("PT_REGEN_WIDE")) ctx->regenWide = std::atoi(e) != 0 ? 1 : 0;
   if (const char* e = std::getenv("PT_SOLO")) ctx->solo = std::atoi(e) != 0;
-  ctx->pipe = cfg->integrator != PT_BASIC_CPU_COMPAT &&
-              !(cfg->flags & (PT_FLAG_COUNT_FETCHES | PT_FLAG_SERIAL_FRAMES));
+  ctx->pipe = pipelines(*cfg);
   if (ctx->pipe) {
-    // a process has the hardware queues its HIP runtime was initialised with (GPU_MAX_HW_QUEUES,
-    // HIP's default 4; the Python package asks for 12 when it is unset and HIP not yet initialised,
-    // and passes what is in effect as pt_config.hw_queues): streams beyond them share queues and
-    // serialise, so the slot streams, the context's own stream and the caller's (torch's) must fit
+    // the hardware queues of the process (GPU_MAX_HW_QUEUES, HIP's default 4; the Python package asks
+    // for 12 when it is unset and HIP not yet initialised, and passes what is in effect as
+    // pt_config.hw_queues)
     int hwq = cfg->hw_queues;
     if (hwq <= 0) {
       const char* q = std::getenv("GPU_MAX_HW_QUEUES");
       hwq = q && std::atoi(q) > 0 ? std::atoi(q) : 4;
     }
-    ctx->pipeDepth = std::min(ctx->pipeDepth, std::max(2, hwq - 2));
-    // Whole Lambert frames (the regen kernel on every scene): 6 in flight. c2's bench line (20 frames
-    // from an idle GPU) 0.254-0.257 ms per frame at 6 vs 0.259-0.277 at 8 and 0.259 at 4, 100 frames
-    // 0.232 either way; the MIS megakernel keeps 8 (c4 0.366 at 8 vs 0.373-0.397 at 6, 0.41 at 4),
-    // and so do screen-tile shares (c2's 1/8 share 0.061 at 8 vs 0.074 at 6)
-    if (cfg->integrator == 0 && ctx->regenWide != 0 && cfg->tile_world <= 1) ctx->pipeDepth = std::min(ctx->pipeDepth, 6);
+    ctx->pipeDepth = pipeDepthFor(*cfg, ctx->regenWide, hwq);
     if (const char* e = std::getenv("PT_PIPE_DEPTH")) {
       ctx->pipeDepth = std::min(PIPE, std::max(1, std::atoi(e)));
       ctx->pipeDepthFixed = true;
@@ -770,19 +733,13 @@ static int uploadScene(pt_ctx* ctx, const float* tris, const SceneHost& h) {
   ctx->nTri = h.nTri;
   ctx->nNodes = h.nNodes;
   ctx->nDevNodes = h.ref.nDev;
-  // Large Disney/MIS scenes (the regen kernel's, renderOne wideScene) run 4 frames in flight:
+  ctx->sceneBytes = sceneBytes(ctx->nTri, ctx->nDevNodes);
+  // Large Disney/MIS scenes (the regen kernel's, pt_plan.h wideScene) run 4 frames in flight:
   // c5's frames last ~6 ms, and 8 in flight spend more on the pipeline's fill and drain than
   // they gain (bench line, 20 frames from idle: 5.60-5.66 ms per frame at 4 vs 5.88 at 8, 6.00 at 6)
-  if (ctx->pipe && !ctx->pipeDepthFixed) {
-    const size_t sceneBytes = (size_t)ctx->nTri * (PAIR_F4 * 16 + 64 + HIT_F4 * 16) + (size_t)ctx->nDevNodes * 64;
-    const bool wideScene = ctx->cfg.integrator != 0 && !(ctx->cfg.flags & PT_FLAG_NO_CULL) &&
-                           sceneBytes > ((size_t)PT_WIDE_SCENE_MB << 20);
-    ctx->pipeDepth = wideScene ? std::min(ctx->pipeDepthBase, 4) : ctx->pipeDepthBase;
-  }
-  if (ctx->pipe) {
-    const size_t sceneBytes = (size_t)ctx->nTri * (PAIR_F4 * 16 + 64 + HIT_F4 * 16) + (size_t)ctx->nDevNodes * 64;
-    ctx->batchCap = batchFor(ctx, ctx->cfg.integrator != 0 && sceneBytes > ((size_t)PT_WIDE_SCENE_MB << 20));
-  }
+  if (ctx->pipe && !ctx->pipeDepthFixed) ctx->pipeDepth = wideScene(ctx) ? std::min(ctx->pipeDepthBase, 4) : ctx->pipeDepthBase;
+  // (the batch's large-scene guard, unlike wideScene, holds under PT_FLAG_NO_CULL too)
+  if (ctx->pipe) ctx->batchCap = batchFor(ctx, ctx->cfg.integrator != 0 && largeScene(ctx));
   ctx->rootRef = h.ref.rootRef;
   ctx->depth = h.ref.depth;
   ctx->maxStack = h.ref.depth + 1;
@@ -1172,15 +1129,6 @@ int pt_basic_replay_overruns(pt_ctx* ctx, int64_t* count) {
   return PT_OK;
 }
 
-static int defaultBounce(int integ) {
-  switch (integ) {
-    case PT_LAMBERT_O: return 2;           // O:385
-    case PT_DISNEY_UNIFORM_D: return 5;    // D:502
-    case PT_DISNEY_MIS_SOBOL_IS: return 2; // IS:861
-    default: return 8;                     // BasicRayTracingWithC++/main.cpp:254
-  }
-}
-
 // Fold the oldest unfolded launch's device time into the totals (and into its
 // probe slot). blocking = false returns false instead of waiting for it.
 static bool foldOne(pt_ctx* ctx, bool blocking) {
@@ -1385,123 +1333,94 @@ static int ensureSlots(pt_ctx* ctx, int D) {
   return PT_OK;
 }
 
-// One launch: frame frameCounter, or -- pipelined, with no policy probe running and the batch
-// not starting a running mean -- up to `want` consecutive frames of the same camera
-// (RenderParams::nFrames, at most ctx->batchCap). *done = the frames rendered.
-static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[16], uint32_t frameCounter,
-                     int want = 1, int* done = nullptr) {
-  if (!ctx) return PT_E_INVALID;
-  if (done) *done = 1;
-  CK(hipSetDevice(ctx->cfg.device_id));
+// the BASIC integrator's frame (BasicRayTracingWithC++): one kernel on the context's stream
+static int renderBasic(pt_ctx* ctx, uint32_t frameCounter) {
   const pt_config& c = ctx->cfg;
-  unsigned long long* stats = reinterpret_cast<unsigned long long*>(ctx->d_ctl + CTL_STATS);
+  if (!ctx->d_shapes) return fail(ctx, PT_E_NOSCENE, "no BASIC shapes uploaded");
+  const int maxDepth = maxBounce(c);  // B:254
+  if (maxDepth > BASIC_MAX_DEPTH) return fail(ctx, PT_E_INVALID, "BASIC max_bounce > 31");
+  if (int rc = ensureBasicImage(ctx)) return rc;
+  if (!ctx->d_overruns) {
+    CK(hipMalloc(&ctx->d_overruns, sizeof(unsigned long long)));
+    CK(hipMemsetAsync(ctx->d_overruns, 0, sizeof(unsigned long long), ctx->stream));
+  }
   hipEvent_t evb, eve;
-  if (c.integrator == PT_BASIC_CPU_COMPAT) {
-    if (!ctx->d_shapes) return fail(ctx, PT_E_NOSCENE, "no BASIC shapes uploaded");
-    const int maxDepth = c.max_bounce >= 0 ? c.max_bounce : 8;  // B:254
-    if (maxDepth > BASIC_MAX_DEPTH) return fail(ctx, PT_E_INVALID, "BASIC max_bounce > 31");
-    if (int rc = ensureBasicImage(ctx)) return rc;
-    if (!ctx->d_overruns) {
-      CK(hipMalloc(&ctx->d_overruns, sizeof(unsigned long long)));
-      CK(hipMemsetAsync(ctx->d_overruns, 0, sizeof(unsigned long long), ctx->stream));
-    }
-    int erc = launchEvents(ctx, &evb, &eve);
-    if (erc) return erc;
-    BasicParams p;
-    p.shapes = ctx->d_shapes;
-    p.nShapes = ctx->nShapes;
-    p.width = c.width;
-    p.height = c.height;
-    p.sample = sampleIndex(c, frameCounter);
-    p.seed = c.basic_seed;
-    p.maxDepth = maxDepth;
-    p.reset = frameCounter == 0;
-    p.brightness = (float)((double)(2.0f * 3.1415926f) * (1.0 / (double)c.basic_samples));  // B:20
-    p.accum = ctx->d_accum;
-    p.image = ctx->d_basicImg;
-    p.stream = ctx->d_stream;
-    p.offsets = ctx->d_offsets;
-    p.streamN = ctx->streamN;
-    p.nOffsets = ctx->nOffsets;
-    p.stats = stats;
-    p.overruns = ctx->d_overruns;
-    CK(hipEventRecord(evb, ctx->stream));
-    CK(launchBasic(p, ctx->stream));
-    CK(hipEventRecord(eve, ctx->stream));
-    commitLaunch(ctx);
-    return PT_OK;
-  }
-  if (!ctx->d_bvh || !eye || !cameraRotate) return fail(ctx, ctx->d_bvh ? PT_E_INVALID : PT_E_NOSCENE, "no scene");
-  const bool count = (c.flags & PT_FLAG_COUNT_FETCHES) != 0;
-  const bool cull = !count && !(c.flags & PT_FLAG_NO_CULL);
-  // default: the lock-step persistent megakernel (also the fetch-counting
-  // variant); the path-regeneration kernel on request, and by default for the
-  // Disney/MIS integrators on large scenes (pt_kernels.h PT_WIDE_SCENE_MB,
-  // WIDE_REGEN_WAVES), whose walks are memory-latency bound and whose long paths
-  // leave a lock-step wave's lanes idle
-  const size_t sceneBytes = (size_t)ctx->nTri * (PAIR_F4 * 16 + 64 + HIT_F4 * 16) + (size_t)ctx->nDevNodes * 64;
-  const bool wideScene = !count && cull && c.integrator != 0 && sceneBytes > ((size_t)PT_WIDE_SCENE_MB << 20);
-  // ... and the MIS integrator at its shader's own 2 bounces (IS:861): c3 at 4 hardware queues 0.1443 ->
-  // 0.1331 ms per frame on the regen kernel (round 5); deeper MIS paths keep the megakernel (c4, 8
-  // bounces: 0.270 vs 0.370)
-  const int mbounce = c.max_bounce >= 0 ? c.max_bounce : defaultBounce(c.integrator);
-  const bool regenAll = !count && cull &&
-                        (ctx->regenWide > 0 ||
-                         (ctx->regenWide < 0 && (c.integrator == 0 || (c.integrator == 2 && mbounce <= 2))));
-  // this frame's stream and per-frame buffers: slot frameNo % depth, colour buffer
-  // frameNo % (depth + 1) when pipelined
-  const bool piped = ctx->pipe && !count;
-  if (piped) {
-    if (int e = ensureSlots(ctx, ctx->pipeDepth)) return e;
-  }
-  const int D = piped ? ctx->pipeDepth : 1;
-  const int slot = piped ? (int)(ctx->frameNo % (unsigned)D) : 0;
-  const int nCol = 2 * D + 1;
-  const int colIdx = piped ? (int)(ctx->frameNo % (unsigned)nCol) : 0;
+  int erc = launchEvents(ctx, &evb, &eve);
+  if (erc) return erc;
+  BasicParams p;
+  p.shapes = ctx->d_shapes;
+  p.nShapes = ctx->nShapes;
+  p.width = c.width;
+  p.height = c.height;
+  p.sample = sampleIndex(c, frameCounter);
+  p.seed = c.basic_seed;
+  p.maxDepth = maxDepth;
+  p.reset = frameCounter == 0;
+  p.brightness = (float)((double)(2.0f * 3.1415926f) * (1.0 / (double)c.basic_samples));  // B:20
+  p.accum = ctx->d_accum;
+  p.image = ctx->d_basicImg;
+  p.stream = ctx->d_stream;
+  p.offsets = ctx->d_offsets;
+  p.streamN = ctx->streamN;
+  p.nOffsets = ctx->nOffsets;
+  p.stats = reinterpret_cast<unsigned long long*>(ctx->d_ctl + CTL_STATS);
+  p.overruns = ctx->d_overruns;
+  CK(hipEventRecord(evb, ctx->stream));
+  CK(launchBasic(p, ctx->stream));
+  CK(hipEventRecord(eve, ctx->stream));
+  commitLaunch(ctx);
+  return PT_OK;
+}
+
+// Where a launch runs. Pipelined, launch frameNo takes slot frameNo % depth (its stream, work-queue
+// counters, overflow stack, tile order, camera-ray results and lists) and colour buffer
+// frameNo % (2 * depth + 1); an unpiped context has one of each and runs on the context's stream.
+struct FrameSlot {
+  int D = 1, slot = 0, nCol = 3, colIdx = 0;
   // A launch issued while no other is in flight runs on the caller's stream itself: its camera-ray
   // pass, frame kernel and running-mean update -- and the caller's next work (the gather's pack) --
   // then follow one another in one queue instead of across queues (an event wait between hardware
   // queues costs ~15-18 us per hop; c2's 1/8 share of a 20-frame window is one launch)
-  bool solo = piped && ctx->solo;
-  if (solo) {
-    for (int k = 0; k < D; k++)
-      if (ctx->slotBusy[k] && hipEventQuery(ctx->kernelDone[k]) == hipErrorNotReady) solo = false;
-    (void)hipGetLastError();  // hipEventQuery's not-ready status is not an error
-  }
-  // The frame kernel. A single frame issued while nothing else is in flight -- a synchronous
-  // display() call (pt_render_frame), SURVEY 8(d)'s per-call time -- runs on the lock-step megakernel,
-  // which splits its long tiles and orders its work longest first, where the regen kernel's launch
-  // ends in its waves' last paths at falling lane counts: per call c3 0.585 -> 0.373 ms, c2 0.449 ->
-  // 0.439 (c4 is on the megakernel already: 0.78; its regen kernel 1.32). Streams of frames keep
-  // the regen kernel (c2's batches 0.17 ms per frame). PT_FLAG_REGEN pins the regen kernel.
-  const bool oneCall = piped && solo && want == 1 && sceneBytes <= ((size_t)PT_WIDE_SCENE_MB << 20) &&
-                       ctx->regenWide <= 0 && PT_CALL_MEGAKERNEL;
-  const bool regen = !count && ((c.flags & PT_FLAG_REGEN) ||
-                                ((wideScene || (regenAll && !oneCall)) && !(c.flags & PT_FLAG_MEGAKERNEL)));
-  hipStream_t S = piped && !solo ? ctx->slotStream[slot] : ctx->stream;
-  // every other slot's frame in flight has ended on S (the frames that read buffers
-  // rebuilt below)
-  auto waitOthers = [&]() -> int {
-    for (int k = 0; k < D; k++)
-      if (k != slot && ctx->slotBusy[k]) CK(hipStreamWaitEvent(S, ctx->kernelDone[k], 0));
-    return PT_OK;
-  };
-  int nb = 0;
-  // the more-waves variant of either kernel (the regen kernel's with its 4-wide walk, dynamic ray
-  // fetch and camera-ray pass; on small trees with the whole tree in LDS)
-  const bool wide = wideScene || (regen && regenAll);
-  const bool walk4 = wide && ctx->fast4Ready && !(c.flags & PT_FLAG_REFERENCE_TREE);
+  bool solo = false;
+  hipStream_t S = nullptr;
+};
+
+// no slot's last launch is still running
+static bool pipeIdle(pt_ctx* ctx, int D) {
+  bool idle = true;
+  for (int k = 0; k < D; k++)
+    if (ctx->slotBusy[k] && hipEventQuery(ctx->kernelDone[k]) == hipErrorNotReady) idle = false;
+  (void)hipGetLastError();  // hipEventQuery's not-ready status is not an error
+  return idle;
+}
+
+// every other slot's frame in flight has ended on S (the frames that read buffers the launch rebuilds)
+static int waitOthers(pt_ctx* ctx, const FrameSlot& at) {
+  for (int k = 0; k < at.D; k++)
+    if (k != at.slot && ctx->slotBusy[k]) CK(hipStreamWaitEvent(at.S, ctx->kernelDone[k], 0));
+  return PT_OK;
+}
+
+// The launch shape: the kernel variant's block and blocks per CU (occupancy queries), and the grid.
+struct LaunchShape {
   RegenShape rs;
-  if (regen) {
-    CK(regenShape(c.integrator, cull, wide, walk4 ? ctx->f4nDev : 0, !wideScene, &rs));
-    nb = rs.blocksPerCU;
+  int bs = BLOCK;  // threads per block
+  int fullGrid = 0, grid = 0;
+};
+
+static int gridFor(pt_ctx* ctx, const FramePlan& pl, const FrameSlot& at, LaunchShape* g) {
+  const pt_config& c = ctx->cfg;
+  int nb = 0;
+  if (pl.regen) {
+    CK(regenShape(c.integrator, pl.cull, pl.wide, pl.walk4 ? ctx->f4nDev : 0, !pl.wideScene, &g->rs));
+    nb = g->rs.blocksPerCU;
   } else {
-    CK(renderBlocksPerCU(c.integrator, cull, count, wide, &nb));
+    CK(renderBlocksPerCU(c.integrator, pl.cull, pl.count, pl.wide, &nb));
   }
   if (nb < 1) nb = 1;
-  const int bs = regen ? rs.block : BLOCK;  // threads per block
-  ctx->lastWaves = nb * bs / 64 / 4;  // 4 SIMDs per CU
-  ctx->lastRegen = regen;
+  g->bs = pl.regen ? g->rs.block : BLOCK;
+  ctx->lastWaves = nb * g->bs / 64 / 4;  // 4 SIMDs per CU
+  ctx->lastRegen = pl.regen;
   // Frames in flight share the GPU by space, not by time: a frame's persistent grid is
   // residency / (frames in flight), so the frames' waves are all resident together and a
   // frame whose long paths keep a few waves busy leaves the rest of the machine to the
@@ -1509,8 +1428,8 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
   // keeps the next frame's waves -- and every other launch -- waiting for its tail: c4
   // 0.48 -> 0.34 ms per frame at 8 frames in flight, c2's 1/8 screen share 0.096 -> 0.072.
   // A caller that waits for every frame gets the whole machine for each.
-  const int fullGrid = ctx->numCU * nb;
-  int grid = fullGrid;
+  g->fullGrid = ctx->numCU * nb;
+  g->grid = g->fullGrid;
   // While other frames are in flight, each frame's grid is PT_GRID_PCT % of its equal share: a frame
   // finishing early leaves waves of the others ready to take its place (round 4, against 100 /
   // 200 / 300 % with the bench line as the driver runs it, 20 frames from an idle GPU: c2 0.285 /
@@ -1522,28 +1441,23 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
   // 20 frames from an idle GPU, one rank's share of an N-way split (profiles/r4/shard_time_h20.jsonl,
   // 2 runs each): c2 N = 4 0.129-0.130 -> 0.072 ms per frame, N = 8 0.061 -> 0.046-0.048, c4 N = 4
   // 0.137 -> 0.109-0.113; N = 1, 2 and 200-frame runs within run-to-run spread.
-#ifndef PT_GRID_PCT
-#define PT_GRID_PCT 125  // round 5, final kernels: c4 0.2571 -> 0.2463 ms at 150 -> 125, its 1/8 share 0.0721 -> 0.0688, c2's 0.0332 -> 0.0325; 175: c2 +3 %
-#endif
-#ifndef PT_GRID_PCT_WIDE
-#define PT_GRID_PCT_WIDE 150  // large scenes (c5: two frames per launch, ~8 ms launches): 4.44 ms at 125
-#endif
-  const int GRID_PCT = wideScene ? PT_GRID_PCT_WIDE : PT_GRID_PCT;
-  if (piped && D > 1) {
+  const int GRID_PCT = pl.wideScene ? PT_GRID_PCT_WIDE : PT_GRID_PCT;
+  if (pl.piped && at.D > 1) {
     int others = 0;  // other launches still in flight: the caller streams frames
-    for (int k = 0; k < D; k++)
-      others += k != slot && ctx->slotBusy[k] && hipEventQuery(ctx->kernelDone[k]) == hipErrorNotReady;
+    for (int k = 0; k < at.D; k++)
+      others += k != at.slot && ctx->slotBusy[k] && hipEventQuery(ctx->kernelDone[k]) == hipErrorNotReady;
     (void)hipGetLastError();  // hipEventQuery's not-ready status is not an error
-    if (others > 0) grid = std::min(fullGrid, std::max(NUM_QUEUES, fullGrid * GRID_PCT / (100 * (others + 1))));
+    if (others > 0)
+      g->grid = std::min(g->fullGrid, std::max(NUM_QUEUES, g->fullGrid * GRID_PCT / (100 * (others + 1))));
   }
-  int ovfDepth = 0;
-  int rc = ensureOverflow(ctx, (size_t)fullGrid * bs, &ovfDepth, regen ? regenLdsStack() : LDS_STACK, D);
-  if (rc) return rc;
-  // the colour buffer's previous launch (nCol back) has been mixed (the slot's queue counters,
-  // order list and camera-ray results belong to its previous launch on this same stream)
-  if (piped && ctx->frameNo >= (unsigned long long)nCol && !(S == ctx->stream && ctx->lastMixStream == S))
-    CK(hipStreamWaitEvent(S, ctx->mixDone[colIdx], 0));
-  int* queue = reinterpret_cast<int*>(ctx->d_ctl + CTL_QUEUES) + (size_t)slot * NUM_QUEUES * CTL_LINE_INTS;
+  return PT_OK;
+}
+
+// What the frame's kernels read of the context and the plan (the tree, the frames, the colour buffer,
+// the tile order and the bins follow in renderOne)
+static RenderParams fillParams(const pt_ctx* ctx, const FramePlan& pl, const FrameSlot& at, const LaunchShape& g,
+                               int ovfDepth, const float eye[3], const float cameraRotate[16], uint32_t frameCounter) {
+  const pt_config& c = ctx->cfg;
   RenderParams p;
   std::memset(&p, 0, sizeof(p));
   p.scene = sceneView(ctx);
@@ -1551,31 +1465,24 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
   p.env.cache = ctx->d_cache;
   p.env.hdr8 = ctx->d_hdr8;
   p.env.cache4 = ctx->d_cache4;
-  // the table by rows for the megakernel's frames when the table outgrows an XCD's L2 share: c4's
-  // frame kernel 216 -> 147 MB DRAM-side per frame, time unchanged (0.2914 / 0.2927 ms); its extra
-  // dependent load costs the regen kernels more than their misses (c5 4.20 -> 4.31 ms, c3 0.1083 -> 0.111)
-#ifndef PT_ROW_TABLE
-#define PT_ROW_TABLE 1  // 0: never, 1: the megakernel's frames, 2: every frame (when the table outgrows 4 MB)
-#endif
-  const bool rowTable = PT_ROW_TABLE > 0 && (PT_ROW_TABLE == 2 || !regen) &&
-                        (size_t)ctx->hdrW * ctx->hdrH * sizeof(uint32_t) > ((size_t)4 << 20);
-  p.env.cacheRow = rowTable ? ctx->d_cacheRow : nullptr;
-  p.env.cacheY = rowTable ? ctx->d_cacheY : nullptr;
+  p.env.cacheRow = pl.rowTable ? ctx->d_cacheRow : nullptr;
+  p.env.cacheY = pl.rowTable ? ctx->d_cacheY : nullptr;
   p.env.trig = ctx->d_trig;
   p.env.light = ctx->d_light;  // every scene: c5 too (4.25 vs 4.49 ms without the table, round 6)
   p.env.w = ctx->hdrW;
   p.env.h = ctx->hdrH;
   p.env.res = ctx->hdrW;
-  p.env.nt = sceneBytes > ((size_t)PT_WIDE_SCENE_MB << 20) ? 1 : 0;
+  p.env.nt = pl.envNt;
   p.width = c.width;
   p.height = c.height;
   p.frameCounter = frameCounter;
   p.sampleIndex = sampleIndex(c, frameCounter);
-  p.maxBounce = c.max_bounce >= 0 ? c.max_bounce : defaultBounce(c.integrator);
+  p.sampleStride = c.sample_world > 0 ? (uint32_t)c.sample_world : 1u;
+  p.maxBounce = maxBounce(c);
   std::memcpy(p.eye, eye, sizeof(p.eye));
   std::memcpy(p.cam, cameraRotate, sizeof(p.cam));
   p.accum = ctx->d_accum;
-  p.queue = queue;
+  p.queue = reinterpret_cast<int*>(ctx->d_ctl + CTL_QUEUES) + (size_t)at.slot * NUM_QUEUES * CTL_LINE_INTS;
   p.perQueue = ctx->perQueue;
   p.numItems = ctx->numItems;
   p.shardSize = ctx->shardSize;
@@ -1583,20 +1490,25 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
   p.shardsX = ctx->shardsX;
   p.rank = c.tile_rank;
   p.world = c.tile_world;
-  p.ovf = ovfDepth ? ctx->d_ovf + (size_t)slot * fullGrid * bs * ovfDepth : nullptr;
+  p.ovf = ovfDepth ? ctx->d_ovf + (size_t)at.slot * g.fullGrid * g.bs * ovfDepth : nullptr;
   p.ovfDepth = ovfDepth;
-  p.scene.fast = 0;  // probePolicy below
-
-  p.stats = stats;
+  p.stats = reinterpret_cast<unsigned long long*>(ctx->d_ctl + CTL_STATS);
   p.rayShards = reinterpret_cast<unsigned long long*>(ctx->d_ctl + CTL_RAYS);
-  // longest-tiles-first: each band's tiles in the order of the previous frame's cost
-  const int group = std::max(1, PT_TILE_GROUP);
-  const bool ordered = !regen && !count && !(c.flags & PT_FLAG_NO_TILE_ORDER) &&
-                       (ctx->perQueue + group - 1) / group <= REORDER_MAX && ctx->numItems < (1 << 22);
+  // per-frame buffers indexed by the pixel's slot in this context's share (shareIndex): a 1/N share's
+  // colour and camera-ray buffers are 1/N of a frame (c5 at N = 8, 16 frames per launch: ~2.4 GB of
+  // colour buffers instead of ~19 GB)
+  p.colStride = (size_t)ctx->numItems * 64;
+  return p;
+}
+
+// Longest-tiles-first: the slot's per-tile costs and its order list (both null: a launch in band order
+// records no costs and launches no reorder)
+static int tileOrderLists(pt_ctx* ctx, bool ordered, int slot, int** cost, int** order) {
   const int orderCap = 4 * ctx->perQueue + 64;  // room for the items of split tiles
   const size_t orderInts = (size_t)NUM_QUEUES * orderCap + NUM_QUEUES;
   ctx->orderCap = orderCap;
-  if (ordered && !ctx->d_cost) {
+  if (!ordered) return PT_OK;
+  if (!ctx->d_cost) {
     // per slot and tile: summed item cost, longest item, split state, cost estimate
     // (reorderKernel reads and zeroes the costs)
     const size_t n = (size_t)PIPE * ctx->numItems * 4;
@@ -1606,169 +1518,83 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
     CK(hipMalloc(&ctx->d_order, (size_t)PIPE * orderInts * sizeof(int)));
     for (int k = 0; k < PIPE; k++) ctx->orderValid[k] = false;
   }
-  int* cost = ordered ? ctx->d_cost + (size_t)slot * 4 * ctx->numItems : nullptr;
-  int* order = ordered ? ctx->d_order + (size_t)slot * orderInts : nullptr;
-  // the tree (the runtime's own, checked against the uploaded one, unless asked
-  // not to) and the split policy: probePolicy
-  bool useFast = false;
-  const int splitPct = probePolicy(ctx, frameCounter, ordered,
-                                   !count && !regen && ctx->fastReady && !(c.flags & PT_FLAG_REFERENCE_TREE), &useFast,
-                                   slot, S);
-  // the large-scene regen kernel walks the 4-wide runtime tree (checked against the uploaded one)
-  if (regen && walk4) useFast = true;
-  if (regen && wide)  // its own LDS copy's size: the top of the tree, or all of it
-    p.scene.f4nTop = rs.fullTree ? ctx->f4nDev : std::min(regenTop4(rs, c.integrator), ctx->f4nDev);
-  p.scene.fast = useFast ? 1 : 0;
-  ctx->lastFast = useFast;
-  // While the policy probe times frames (PT_SPLIT_AUTO, 20 frames after a restart) a pipelined
-  // frame starts only after the previous one has ended, and each launch is one frame.
-  const bool probing = ordered && PT_SPLIT_AUTO &&
-                       (ctx->treeDecided < 0 || ctx->splitDecided < 0);
-  const int nF = piped && !probing ? std::max(1, std::min(want, ctx->batchCap)) : 1;
-  if (done) *done = nF;
-  p.nFrames = nF;
-  // One megakernel frame issued while no other launch is in flight (a display() call, SURVEY 8(d)'s
-  // per-call time): the kernel mixes each pixel's sample into the running mean itself (IS:868-871;
-  // one writer per pixel, the previous frame's update is ordered before it on the caller's stream)
-  // -- no colour buffer round trip and no running-mean update launch: c4 per call 0.785 -> 0.772 ms.
-  // The regen kernel keeps the update launch: the read of the running mean at each path's end stalls
-  // its lock-step waves (c2 0.455 either way, c3 0.578 -> 0.587 ms)
-  // A PT_FLAG_MOMENTS context never does: its samples pass through the colour buffer to mixMomentsKernel.
-  const bool direct = piped && solo && nF == 1 && !regen && PT_DIRECT_SOLO && !ctx->d_mom;
-  if (direct && ctx->mixPending && ctx->lastMixStream != S) CK(hipStreamWaitEvent(S, ctx->mixDone[ctx->lastCol], 0));
-  p.sampleStride = c.sample_world > 0 ? (uint32_t)c.sample_world : 1u;
-  // per-frame buffers indexed by the pixel's slot in this context's share (shareIndex): a 1/N share's
-  // colour and camera-ray buffers are 1/N of a frame (c5 at N = 8, 16 frames per launch: ~2.4 GB of
-  // colour buffers instead of ~19 GB)
-  const size_t shareN = (size_t)ctx->numItems * 64;
-  p.colStride = shareN;
-  // every colour buffer (and below, every slot's camera-ray results) allocated at the first launch that
-  // uses any, so no later launch -- a timed one -- waits for an allocation (c2's 1/8 share: a 19 us
-  // hipMalloc before the sixth launch's first kernel)
-  if (piped)
-    for (int k = 0; k < nCol; k++)
-      if (!ctx->d_col[k]) {
-        const int cap = std::max(nF, ctx->batchCap);
-        CK(hipMalloc(&ctx->d_col[k], (size_t)cap * shareN * COL_F * sizeof(float)));
-        ctx->colCap[k] = cap;
-      }
-  if (piped && ctx->colCap[colIdx] < nF) {  // room for the launch's frames (each buffer grows once, to batchCap)
-    if (ctx->d_col[colIdx]) {
-      CK(hipEventSynchronize(ctx->mixDone[colIdx]));  // its last frames' running-mean update has read it
-      dfree(ctx->d_col[colIdx]);
+  *cost = ctx->d_cost + (size_t)slot * 4 * ctx->numItems;
+  *order = ctx->d_order + (size_t)slot * orderInts;
+  return PT_OK;
+}
+
+// Camera-ray bins, rebuilt when the camera or the scene changed (the previous frame has ended
+// first: it may still read the old bins), and with a camera-ray pass the slot's results and lists
+static int bindBins(pt_ctx* ctx, const FramePlan& pl, const FrameSlot& at, const RegenShape& rs, int nF,
+                    const float eye[3], const float cameraRotate[16], RenderParams* p) {
+  const pt_config& c = ctx->cfg;
+  hipStream_t S = at.S;
+  if (!ctx->binsValid || ctx->binVersion != ctx->sceneVersion || std::memcmp(ctx->binEye, eye, sizeof(ctx->binEye)) ||
+      std::memcmp(ctx->binCam, cameraRotate, sizeof(ctx->binCam))) {
+    if (pl.piped) {
+      if (int e = waitOthers(ctx, at)) return e;
     }
-    const int cap = std::max(nF, ctx->batchCap);
-    CK(hipMalloc(&ctx->d_col[colIdx], (size_t)cap * shareN * COL_F * sizeof(float)));
-    ctx->colCap[colIdx] = cap;
-  }
-  p.col = piped && !direct ? ctx->d_col[colIdx] : nullptr;
-  p.packets = PT_PACKETS && (p.scene.fast ? ctx->fDepth : ctx->depth) + 1 <= PKT_DEPTH;
-  // camera-ray bins, rebuilt when the camera or the scene changed (the previous frame
-  // has ended first: it may still read the old bins); they need the reference facts
-  // refReachable checks a bin's winner against
-  // The camera-ray pass (primaryKernel) traces the camera rays ahead of the frame kernel: on
-  // request, and by default for the large-scene regen kernel (c5 7.52 -> 6.86 ms), whose lanes
-  // then start from the camera ray's hit; the megakernel is faster with its camera rays inside
-  // (c2 0.372 vs 0.383 ms with the pass)
-  const bool pass = (c.flags & PT_FLAG_PRIMARY_PASS) || (regen && wide);
-  const bool bins = PT_BINS && !count && ctx->fastReady && !(c.flags & PT_FLAG_NO_BINS) && (!regen || pass);
-  if (bins) {
-    if (!ctx->binsValid || ctx->binVersion != ctx->sceneVersion || std::memcmp(ctx->binEye, eye, sizeof(ctx->binEye)) ||
-        std::memcmp(ctx->binCam, cameraRotate, sizeof(ctx->binCam))) {
-      if (piped) {
-        if (int e = waitOthers()) return e;
-      }
-      ctx->binsValid = false;
-      CK(buildPrimaryBins(eye, cameraRotate, c.width, c.height, ctx->d_geo, ctx->d_leafBox, ctx->nTri, ctx->bins, S));
-      std::memcpy(ctx->binEye, eye, sizeof(ctx->binEye));
-      std::memcpy(ctx->binCam, cameraRotate, sizeof(ctx->binCam));
-      ctx->binVersion = ctx->sceneVersion;
-      ctx->binsValid = true;
-      if (piped) {
-        CK(hipEventRecord(ctx->binsBuilt, S));
-        ctx->binGen++;
-        ctx->binGenSeen[slot] = ctx->binGen;
-      }
-    }
-    // a frame in flight on the other slot's stream must not read bins still being built
-    if (piped && ctx->binGenSeen[slot] != ctx->binGen) {
-      CK(hipStreamWaitEvent(S, ctx->binsBuilt, 0));
-      ctx->binGenSeen[slot] = ctx->binGen;
-    }
-    p.binStart = ctx->bins.binStart;
-    p.binTris = ctx->bins.binTris;
-    p.binGeo = ctx->bins.binGeo;
-    p.binBox = ctx->bins.binBox;
-    p.binTilesX = ctx->bins.tilesX;
-    p.binTilesY = ctx->bins.tilesY;
-    if (pass) {
-      // per frame: the share's entries (shareN int2, compacted per wave tile), then its numItems tile masks
-      const size_t primBytes = shareN * sizeof(int2) + (size_t)ctx->numItems * sizeof(unsigned long long);
-      if (piped)
-        for (int k = 0; k < D; k++)
-          if (!ctx->d_prim[k]) {
-            const int cap = std::max(nF, ctx->batchCap);
-            CK(hipMalloc(&ctx->d_prim[k], (size_t)cap * primBytes));
-            ctx->primCap[k] = cap;
-          }
-      if (ctx->primCap[slot] < nF) {  // the slot's previous launch (on S) may still read the old results
-        if (ctx->d_prim[slot]) {
-          CK(hipStreamSynchronize(S));
-          dfree(ctx->d_prim[slot]);
-        }
-        const int cap = std::max(nF, piped ? ctx->batchCap : 1);
-        CK(hipMalloc(&ctx->d_prim[slot], (size_t)cap * primBytes));
-        ctx->primCap[slot] = cap;
-      }
-      p.primHit = ctx->d_prim[slot];
-      p.primMask = reinterpret_cast<unsigned long long*>(ctx->d_prim[slot] + (size_t)ctx->primCap[slot] * shareN);
-      // the regen kernels claim from per-queue lists of the tiles the pass left paths in (all variants
-      // but the large scenes' MIS one, pt_regen.hip regenLists)
-      if (regen && regenTakesLists(c.integrator, rs)) {
-        // per slot, like the results: every queue's segment of live items (liveStride records of 16 bytes)
-        auto liveBytes = [&](int cap) { return (size_t)NUM_QUEUES * liveStride(ctx->perQueue, cap) * sizeof(uint4); };
-        if (piped)
-          for (int k = 0; k < D; k++)
-            if (!ctx->d_live[k]) {
-              const int cap = std::max(nF, ctx->batchCap);
-              CK(hipMalloc(&ctx->d_live[k], liveBytes(cap)));
-              ctx->liveCap[k] = cap;
-            }
-        if (ctx->liveCap[slot] < nF) {  // the slot's previous launch (on S) may still read the old lists
-          if (ctx->d_live[slot]) {
-            CK(hipStreamSynchronize(S));
-            dfree(ctx->d_live[slot]);
-          }
-          const int cap = std::max(nF, piped ? ctx->batchCap : 1);
-          CK(hipMalloc(&ctx->d_live[slot], liveBytes(cap)));
-          ctx->liveCap[slot] = cap;
-        }
-        p.liveItems = p.primHit ? ctx->d_live[slot] : nullptr;  // (a share that owns no tile has no results and no lists)
-      }
+    ctx->binsValid = false;
+    CK(buildPrimaryBins(eye, cameraRotate, c.width, c.height, ctx->d_geo, ctx->d_leafBox, ctx->nTri, ctx->bins, S));
+    std::memcpy(ctx->binEye, eye, sizeof(ctx->binEye));
+    std::memcpy(ctx->binCam, cameraRotate, sizeof(ctx->binCam));
+    ctx->binVersion = ctx->sceneVersion;
+    ctx->binsValid = true;
+    if (pl.piped) {
+      CK(hipEventRecord(ctx->binsBuilt, S));
+      ctx->binGen++;
+      ctx->binGenSeen[at.slot] = ctx->binGen;
     }
   }
-  // a frame in band order (probePolicy) records no costs and launches no reorder; the
-  // slot's last order list stays valid for its next ordered frame (any list covers every tile)
-  // Batches of frames run unsplit (probePolicy) -- also on small screen-tile shares, whose launch lasts
-  // about as long as its longest unsplit tile (c4's 1/8 share, 20 frames in one 1.3 ms launch: single
-  // 8x8 tiles of 1.2-1.5 ms): splitting there measured c4 N = 8 0.0726 -> 0.0688 ms per frame over 20
-  // frames but 0.0484 -> 0.0549 over 200, N = 4 0.0867 -> 0.0962 (round 6, not kept)
-  const bool splitThis = nF == 1;
-  // (a batch does not run the split items a one-frame launch's reorder listed: band order, once)
-  p.tileOrder = ordered && ctx->orderValid[slot] && !(!splitThis && ctx->orderSplit[slot]) ? order : nullptr;
-  p.orderCap = orderCap;
-  p.tileCost = ordered ? cost : nullptr;
-  p.tileCostMax = ordered ? cost + ctx->numItems : nullptr;
-  if (piped && probing) {
-    if (int e = waitOthers()) return e;
+  // a frame in flight on the other slot's stream must not read bins still being built
+  if (pl.piped && ctx->binGenSeen[at.slot] != ctx->binGen) {
+    CK(hipStreamWaitEvent(S, ctx->binsBuilt, 0));
+    ctx->binGenSeen[at.slot] = ctx->binGen;
   }
+  p->binStart = ctx->bins.binStart;
+  p->binTris = ctx->bins.binTris;
+  p->binGeo = ctx->bins.binGeo;
+  p->binBox = ctx->bins.binBox;
+  p->binTilesX = ctx->bins.tilesX;
+  p->binTilesY = ctx->bins.tilesY;
+  if (!pl.pass) return PT_OK;
+  const int n = pl.piped ? at.D : 0, cap = std::max(nF, pl.piped ? ctx->batchCap : 1);
+  // the slot's previous launch (on S) may still read the old results and lists
+  auto waitSlot = [&]() { return hipStreamSynchronize(S); };
+  // per frame: the share's entries (colStride int2, compacted per wave tile), then its numItems tile masks
+  const size_t primBytes = p->colStride * sizeof(int2) + (size_t)ctx->numItems * sizeof(unsigned long long);
+  if (int rc = frameBuffer(ctx, ctx->d_prim, ctx->primCap, n, at.slot, nF, cap,
+                           [&](int f) { return (size_t)f * primBytes; }, waitSlot))
+    return rc;
+  p->primHit = ctx->d_prim[at.slot];
+  p->primMask = reinterpret_cast<unsigned long long*>(ctx->d_prim[at.slot] + (size_t)ctx->primCap[at.slot] * p->colStride);
+  // the regen kernels claim from per-queue lists of the tiles the pass left paths in (all variants
+  // but the large scenes' MIS one, pt_regen.hip regenLists)
+  if (pl.regen && regenTakesLists(c.integrator, rs)) {
+    // per slot, like the results: every queue's segment of live items (liveStride records of 16 bytes)
+    if (int rc = frameBuffer(ctx, ctx->d_live, ctx->liveCap, n, at.slot, nF, cap,
+                             [&](int f) { return (size_t)NUM_QUEUES * liveStride(ctx->perQueue, f) * sizeof(uint4); },
+                             waitSlot))
+      return rc;
+    p->liveItems = p->primHit ? ctx->d_live[at.slot] : nullptr;  // (a share that owns no tile has no results and no lists)
+  }
+  return PT_OK;
+}
+
+// The launch's own kernels on its stream, between the launch's begin and end events: the slot's
+// work-queue counters zeroed, the camera-ray pass and its lists, the frame kernel, the tile reorder
+static int enqueueFrame(pt_ctx* ctx, const FramePlan& pl, const FrameSlot& at, const LaunchShape& g, RenderParams& p,
+                        int* cost, int* order, int split) {
+  const pt_config& c = ctx->cfg;
+  hipStream_t S = at.S;
+  hipEvent_t evb, eve;
   int erc = launchEvents(ctx, &evb, &eve);
   if (erc) return erc;
 #if PT_WAVE_TRACE
   // diagnostics build: each wave's {start, end, tiles | longest tile's pixel << 32,
   // longest tile's duration, its most node-loop / leaf-loop iterations of a lane} (100 MHz wall
   // clock), appended per frame to $PT_WAVE_TRACE_FILE (tools/wave_trace.py)
-  const size_t nTrace = (size_t)grid * (bs / 64) * WAVE_TRACE_WORDS;
+  const size_t nTrace = (size_t)g.grid * (g.bs / 64) * WAVE_TRACE_WORDS;
   unsigned long long* dTrace = nullptr;
   {
     CK(hipMalloc(&dTrace, nTrace * sizeof(unsigned long long)));
@@ -1778,12 +1604,12 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
 #endif
   // the slot's work-queue counters zeroed for this launch: by the camera-ray pass (block 0), else by a memset
   p.zeroQueue = p.primHit != nullptr;
-  if (!p.primHit) CK(hipMemsetAsync(queue, 0, (size_t)NUM_QUEUES * CTL_LINE_INTS * sizeof(int), S));
+  if (!p.primHit) CK(hipMemsetAsync(p.queue, 0, (size_t)NUM_QUEUES * CTL_LINE_INTS * sizeof(int), S));
   CK(hipEventRecord(evb, S));
   if (p.primHit) CK(launchPrimary(p, S));
   if (p.liveItems) CK(launchLiveList(p, S));  // the frame kernel claims only tiles the pass left paths in
-  if (regen) CK(launchRegen(p, c.integrator, grid, S, cull, rs));
-  else CK(launchRender(p, c.integrator, grid, S, cull, count, wide));
+  if (pl.regen) CK(launchRegen(p, c.integrator, g.grid, S, pl.cull, g.rs));
+  else CK(launchRender(p, c.integrator, g.grid, S, pl.cull, pl.count, pl.wide));
 #if PT_WAVE_TRACE
   if (dTrace) {
     std::vector<unsigned long long> tr(nTrace);
@@ -1798,39 +1624,141 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
     }
   }
 #endif
-  if (ordered) {
+  if (pl.ordered) {
     CK(launchReorder(cost, cost + ctx->numItems, cost + 2 * (size_t)ctx->numItems, cost + 3 * (size_t)ctx->numItems,
-                     order, ctx->perQueue, orderCap, ctx->numItems, group, grid * (BLOCK / 64), splitThis ? splitPct : 0, S));
-    ctx->orderValid[slot] = true;
-    ctx->orderSplit[slot] = splitThis && splitPct > 0;
+                     order, ctx->perQueue, ctx->orderCap, ctx->numItems, std::max(1, PT_TILE_GROUP),
+                     g.grid * (BLOCK / 64), split, S));
+    ctx->orderValid[at.slot] = true;
+    ctx->orderSplit[at.slot] = split > 0;
   }
   // kernel_ms: the frame's own kernels (camera-ray pass, frame kernel, reorder), so the
-  // policy probe weighs the order's cost too; the running-mean update below is not in it
+  // policy probe weighs the order's cost too; the running-mean update is not in it
   CK(hipEventRecord(eve, S));
+  return PT_OK;
+}
+
+// A pipelined launch's running-mean update: on the caller's stream, in frame order, after the
+// launch's kernels (direct: the frame's kernels updated the running mean themselves)
+static int enqueueMix(pt_ctx* ctx, const FrameSlot& at, int nF, bool direct, uint32_t frameCounter) {
+  const pt_config& c = ctx->cfg;
+  const int slot = at.slot, colIdx = at.colIdx;
+  const size_t shareN = (size_t)ctx->numItems * 64;
+  CK(hipEventRecord(ctx->kernelDone[slot], at.S));
+  ctx->slotBusy[slot] = true;
+  if (at.S != ctx->slotStream[slot])  // the slot's resources: its stream's later work follows this launch
+    CK(hipStreamWaitEvent(ctx->slotStream[slot], ctx->kernelDone[slot], 0));
+  if (at.S != ctx->stream) CK(hipStreamWaitEvent(ctx->stream, ctx->kernelDone[slot], 0));
+  if (ctx->mixPending && ctx->lastMixStream != ctx->stream)  // the caller switched streams: keep frame order
+    CK(hipStreamWaitEvent(ctx->stream, ctx->mixDone[ctx->lastCol], 0));
+  ctx->lastMixStream = ctx->stream;
+  if (ctx->d_mom) {
+    CK(launchMixMoments(packParams(ctx, c.tile_rank, c.tile_world), ctx->d_accum, ctx->d_mom, ctx->d_col[colIdx],
+                        shareN, nF, frameCounter, ctx->stream));
+    // the frames the moments hold: a restart, a continuation, or a gap (not valid)
+    ctx->momFrames = frameCounter == 0 ? (uint32_t)nF : (frameCounter == ctx->momFrames ? ctx->momFrames + (uint32_t)nF : 0u);
+  } else if (!direct)
+    CK(launchMix(packParams(ctx, c.tile_rank, c.tile_world), ctx->d_accum, ctx->d_col[colIdx], shareN, nF,
+                 frameCounter, ctx->stream));
+  CK(hipEventRecord(ctx->mixDone[colIdx], ctx->stream));  // direct: the frame's kernels updated it
+  ctx->lastSlot = slot;
+  ctx->lastCol = colIdx;
+  ctx->mixPending = true;
+  ctx->frameNo++;
+  return PT_OK;
+}
+
+// One launch: frame frameCounter, or -- pipelined, with no policy probe running and the batch
+// not starting a running mean -- up to `want` consecutive frames of the same camera
+// (RenderParams::nFrames, at most ctx->batchCap). *done = the frames rendered.
+static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[16], uint32_t frameCounter,
+                     int want = 1, int* done = nullptr) {
+  if (!ctx) return PT_E_INVALID;
+  if (done) *done = 1;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const pt_config& c = ctx->cfg;
+  if (c.integrator == PT_BASIC_CPU_COMPAT) return renderBasic(ctx, frameCounter);
+  if (!ctx->d_bvh || !eye || !cameraRotate) return fail(ctx, ctx->d_bvh ? PT_E_INVALID : PT_E_NOSCENE, "no scene");
+  // where the launch runs, and what it uses
+  FrameSlot at;
+  const bool piped = pipedFrames(ctx);
   if (piped) {
-    // the running-mean updates on the caller's stream, in frame order, after this launch's kernel
-    CK(hipEventRecord(ctx->kernelDone[slot], S));
-    ctx->slotBusy[slot] = true;
-    if (S != ctx->slotStream[slot])  // the slot's resources: its stream's later work follows this launch
-      CK(hipStreamWaitEvent(ctx->slotStream[slot], ctx->kernelDone[slot], 0));
-    if (S != ctx->stream) CK(hipStreamWaitEvent(ctx->stream, ctx->kernelDone[slot], 0));
-    if (ctx->mixPending && ctx->lastMixStream != ctx->stream)  // the caller switched streams: keep frame order
-      CK(hipStreamWaitEvent(ctx->stream, ctx->mixDone[ctx->lastCol], 0));
-    ctx->lastMixStream = ctx->stream;
-    if (ctx->d_mom) {
-      CK(launchMixMoments(packParams(ctx, c.tile_rank, c.tile_world), ctx->d_accum, ctx->d_mom, ctx->d_col[colIdx],
-                          shareN, nF, frameCounter, ctx->stream));
-      // the frames the moments hold: a restart, a continuation, or a gap (not valid)
-      ctx->momFrames = frameCounter == 0 ? (uint32_t)nF : (frameCounter == ctx->momFrames ? ctx->momFrames + (uint32_t)nF : 0u);
-    } else if (!direct)
-      CK(launchMix(packParams(ctx, c.tile_rank, c.tile_world), ctx->d_accum, ctx->d_col[colIdx], shareN, nF,
-                   frameCounter, ctx->stream));
-    CK(hipEventRecord(ctx->mixDone[colIdx], ctx->stream));  // direct: the frame's kernels updated it
-    ctx->lastSlot = slot;
-    ctx->lastCol = colIdx;
-    ctx->mixPending = true;
-    ctx->frameNo++;
+    if (int e = ensureSlots(ctx, ctx->pipeDepth)) return e;
+    at.D = ctx->pipeDepth;
+    at.slot = (int)(ctx->frameNo % (unsigned)at.D);
+    at.nCol = 2 * at.D + 1;
+    at.colIdx = (int)(ctx->frameNo % (unsigned)at.nCol);
+    at.solo = ctx->solo && pipeIdle(ctx, at.D);
   }
+  const FramePlan pl = planFrame(ctx, at.solo, want);
+  const hipStream_t S = at.S = piped && !at.solo ? ctx->slotStream[at.slot] : ctx->stream;
+  LaunchShape g;
+  if (int rc = gridFor(ctx, pl, at, &g)) return rc;
+  int ovfDepth = 0;
+  if (int rc = ensureOverflow(ctx, (size_t)g.fullGrid * g.bs, &ovfDepth, pl.regen ? regenLdsStack() : LDS_STACK, at.D))
+    return rc;
+  // the colour buffer's previous launch (nCol back) has been mixed (the slot's queue counters,
+  // order list and camera-ray results belong to its previous launch on this same stream)
+  if (piped && ctx->frameNo >= (unsigned long long)at.nCol && !(S == ctx->stream && ctx->lastMixStream == S))
+    CK(hipStreamWaitEvent(S, ctx->mixDone[at.colIdx], 0));
+  RenderParams p = fillParams(ctx, pl, at, g, ovfDepth, eye, cameraRotate, frameCounter);
+  int *cost = nullptr, *order = nullptr;
+  if (int rc = tileOrderLists(ctx, pl.ordered, at.slot, &cost, &order)) return rc;
+  // the tree (the runtime's own, checked against the uploaded one, unless asked
+  // not to) and the split policy: probePolicy
+  bool useFast = false;
+  const int splitPct = probePolicy(ctx, frameCounter, pl.ordered,
+                                   !pl.count && !pl.regen && ctx->fastReady && !(c.flags & PT_FLAG_REFERENCE_TREE),
+                                   &useFast, at.slot, S);
+  // the large-scene regen kernel walks the 4-wide runtime tree (checked against the uploaded one)
+  if (pl.regen && pl.walk4) useFast = true;
+  if (pl.regen && pl.wide)  // its own LDS copy's size: the top of the tree, or all of it
+    p.scene.f4nTop = g.rs.fullTree ? ctx->f4nDev : std::min(regenTop4(g.rs, c.integrator), ctx->f4nDev);
+  p.scene.fast = useFast ? 1 : 0;
+  ctx->lastFast = useFast;
+  p.packets = PT_PACKETS && (useFast ? ctx->fDepth : ctx->depth) + 1 <= PKT_DEPTH;
+  // While the policy probe times frames (PT_SPLIT_AUTO, 20 frames after a restart) a pipelined
+  // frame starts only after the previous one has ended, and each launch is one frame.
+  const bool probing = pl.ordered && PT_SPLIT_AUTO && (ctx->treeDecided < 0 || ctx->splitDecided < 0);
+  const int nF = piped && !probing ? std::max(1, std::min(want, ctx->batchCap)) : 1;
+  if (done) *done = nF;
+  p.nFrames = nF;
+  // One megakernel frame issued while no other launch is in flight (a display() call, SURVEY 8(d)'s
+  // per-call time): the kernel mixes each pixel's sample into the running mean itself (IS:868-871;
+  // one writer per pixel, the previous frame's update is ordered before it on the caller's stream)
+  // -- no colour buffer round trip and no running-mean update launch: c4 per call 0.785 -> 0.772 ms.
+  // The regen kernel keeps the update launch: the read of the running mean at each path's end stalls
+  // its lock-step waves (c2 0.455 either way, c3 0.578 -> 0.587 ms)
+  // A PT_FLAG_MOMENTS context never does: its samples pass through the colour buffer to mixMomentsKernel.
+  const bool direct = piped && at.solo && nF == 1 && !pl.regen && PT_DIRECT_SOLO && !ctx->d_mom;
+  if (direct && ctx->mixPending && ctx->lastMixStream != S) CK(hipStreamWaitEvent(S, ctx->mixDone[ctx->lastCol], 0));
+  if (piped) {
+    // its last frames' running-mean update has read the colour buffer
+    if (int rc = frameBuffer(ctx, ctx->d_col, ctx->colCap, at.nCol, at.colIdx, nF, std::max(nF, ctx->batchCap),
+                             [&](int f) { return (size_t)f * p.colStride * COL_F * sizeof(float); },
+                             [&]() { return hipEventSynchronize(ctx->mixDone[at.colIdx]); }))
+      return rc;
+  }
+  p.col = piped && !direct ? ctx->d_col[at.colIdx] : nullptr;
+  if (pl.bins)
+    if (int rc = bindBins(ctx, pl, at, g.rs, nF, eye, cameraRotate, &p)) return rc;
+  // a frame in band order (probePolicy) records no costs and launches no reorder; the
+  // slot's last order list stays valid for its next ordered frame (any list covers every tile)
+  // Batches of frames run unsplit (probePolicy) -- also on small screen-tile shares, whose launch lasts
+  // about as long as its longest unsplit tile (c4's 1/8 share, 20 frames in one 1.3 ms launch: single
+  // 8x8 tiles of 1.2-1.5 ms): splitting there measured c4 N = 8 0.0726 -> 0.0688 ms per frame over 20
+  // frames but 0.0484 -> 0.0549 over 200, N = 4 0.0867 -> 0.0962 (round 6, not kept)
+  const bool splitThis = nF == 1;
+  // (a batch does not run the split items a one-frame launch's reorder listed: band order, once)
+  p.tileOrder = pl.ordered && ctx->orderValid[at.slot] && !(!splitThis && ctx->orderSplit[at.slot]) ? order : nullptr;
+  p.orderCap = ctx->orderCap;
+  p.tileCost = cost;
+  p.tileCostMax = pl.ordered ? cost + ctx->numItems : nullptr;
+  if (piped && probing) {
+    if (int e = waitOthers(ctx, at)) return e;
+  }
+  if (int rc = enqueueFrame(ctx, pl, at, g, p, cost, order, splitThis ? splitPct : 0)) return rc;
+  if (piped)
+    if (int rc = enqueueMix(ctx, at, nF, direct, frameCounter)) return rc;
   commitLaunch(ctx, nF);
   return PT_OK;
 }

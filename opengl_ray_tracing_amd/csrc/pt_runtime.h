@@ -1,6 +1,7 @@
 // pt_runtime.h -- what the host files of the C-ABI share (pt_runtime.cpp: contexts, uploads, the
 // frame path, gather, stats; pt_post.cpp: the display post-processing): the context, the error
 // helpers, and the few functions of pt_runtime.cpp the post-processing calls. Internal: not installed.
+// (The launch policy of the frame path -- pure functions of this context -- is pt_plan.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,7 +19,7 @@ static constexpr int EV_RING = 64;
 // sequence number) runs on slot stream g % depth (8 by default) with its own work queues,
 // overflow stack, tile order and camera-ray results, and writes its sample colours to colour
 // buffer g % (2 * depth + 1). While k other launches are in flight its persistent grid is 1.5 /
-// (k + 1) of residency (renderOne), so the frames in flight share the GPU by space: their waves
+// (k + 1) of residency (gridFor), so the frames in flight share the GPU by space: their waves
 // are resident together, and a frame whose last long paths keep a few waves busy leaves the
 // rest of the machine to the others. Its running-mean update (mixKernel) runs on the caller's
 // stream, in frame order, once the launch's kernel has ended: the accumulation is updated in
@@ -94,6 +95,7 @@ struct pt_ctx {
   int accelDevice = -1, accelNodes = 0, accelDepth = 0;
   int rootRef = REF_NONE;
   int nTri = 0, nNodes = 0, depth = 0, maxStack = 0;
+  size_t sceneBytes = 0;  // the scene's records on the device (pt_plan.h sceneBytes, largeScene)
   // env
   float4* d_hdr = nullptr;
   float2* d_cache = nullptr;  // sample table (x, y); the pdf lives in d_hdr[k].w

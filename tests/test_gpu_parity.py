@@ -162,7 +162,7 @@ def test_frame_kernels_agree(request, name, integrator):
     d, sd = render_gpu(cfg, tris, nodes, hdr, frames=2, integrator=integrator, max_bounce=mb)
     e, se = render_gpu(cfg, tris, nodes, hdr, frames=2, integrator=integrator, max_bounce=mb, stream=True)
     # streams of frames run the regen kernel by default for Lambert and MIS at its shader's own 2
-    # bounces (pt_runtime.cpp regenAll); a synchronous display() call's single frame the megakernel
+    # bounces (pt_plan.h regenAll); a synchronous display() call's single frame the megakernel
     assert sb.regen == 0 and sd.regen == 0
     assert se.regen == (1 if integrator == "lambert" or (integrator == "mis" and mb <= 2) else 0)
     if integrator == "mis" and se.regen:  # the MIS wide kernel on a scene that fits the L2s: 3 waves/SIMD
@@ -354,7 +354,7 @@ def test_frame_batches_equal_serial_frames(request, name, tile, batch, flags):
     a, sa = run(0, True)
     b, sb = run(FLAG_SERIAL_FRAMES, False)
     assert sa.frames == sb.frames == sum(c[2] for c in calls)
-    few = sa.frames_in_flight <= 3  # pt_runtime.cpp batchFor: few hardware queues, more frames per launch
+    few = sa.frames_in_flight <= 3  # pt_plan.h batchFor: few hardware queues, more frames per launch
     mis = 32 if cfg.max_bounce > 2 else 16  # MIS beyond 2 bounces: the megakernel's batches
     m = (12 if few else 2) if cfg.integrator == "lambert" else (mis if few else 4)
     auto = min(m * tile[1], 32)
@@ -426,3 +426,69 @@ def test_camera_ray_pass_equals_megakernel_camera_rays(request, name, integrator
     for x, y in zip(a, b):
         assert np.array_equal(x, y)
     assert sa.rays == sb.rays
+
+
+@pytest.fixture(scope="module")
+def grow_scenes():
+    """A scene past PT_WIDE_SCENE_MB (c3's teapot on a 330 x 330 heightfield: 222 946 triangles,
+    51.0 MiB of triangle records), c3's own scene, one small env and one camera for both."""
+    s = scenes.scene_c3()
+    v, i = scenes.heightfield(330)
+    s.add_mesh(v, i, scenes.Material(baseColor=(0.6, 0.6, 0.65), roughness=0.4, metallic=0.2, specular=0.5),
+               scenes.get_transform_matrix((0, 0, 0), (0, -1.2, 0), (13.0, 13.0, 13.0)), True)
+    s.build_bvh("binned", 8)
+    large = s.encode()
+    assert large[0].size // 36 == 222946
+    s = scenes.scene_c3()
+    s.build_bvh(scenes.CONFIGS["c3"].builder, 8)
+    return large, s.encode(), scenes.synthetic_env(), orbit_camera(*scenes.CONFIGS["c3"].camera)
+
+
+@pytest.mark.parametrize("integrator,mb,flags", [("mis", 2, 0), ("disney", 5, "regen|primary")])
+def test_frame_buffers_grow_with_the_batch(grow_scenes, integrator, mb, flags):
+    """A context's frames per launch rise after its per-frame buffers exist when a Disney/MIS context
+    uploads a large scene (1 or 2 frames per launch) and then a small one: the next batch is larger
+    than every colour buffer, the slot's camera-ray results and (where the regen kernel takes them:
+    the Disney context here) its live-item lists, which are freed after their last reader and
+    reallocated. The images before and after equal the oracle's bit for bit, and the small scene's
+    image and rays equal a fresh context's."""
+    from opengl_ray_tracing_amd import FLAG_PRIMARY_PASS, FLAG_REGEN
+    fl = FLAG_REGEN | FLAG_PRIMARY_PASS if flags else 0
+    (ltris, lnodes), (stris, snodes), hdr, (eye, rot) = grow_scenes
+    w, h = 64, 48
+
+    def small(r):
+        r.upload_scene(stris, snodes)
+        r0 = r.stats().rays
+        r.render_frames(eye, rot, 0, 1)
+        r.render_frames(eye, rot, 1, 20)
+        st = r.stats()
+        return r.accum(), st.rays - r0, st
+
+    with Renderer(w, h, integrator, max_bounce=mb, flags=fl) as r:
+        r.upload_scene(ltris, lnodes)
+        r.upload_env(hdr)
+        r.render_frames(eye, rot, 0, 1)
+        r.render_frames(eye, rot, 1, 4)
+        big, st = r.accum(), r.stats()
+        assert st.regen == 1
+        if integrator == "mis":
+            assert st.waves_per_simd == 4
+        assert st.frame_batch == (2 if st.frames_in_flight <= 3 else 1)
+        a, ra, sa = small(r)
+        assert sa.frame_batch > st.frame_batch
+    with Renderer(w, h, integrator, max_bounce=mb, flags=fl) as r:
+        r.upload_env(hdr)
+        b, rb, _ = small(r)
+    assert np.array_equal(a, b)
+    assert ra == rb
+
+    def oracle_frames(tris, nodes, n):
+        orc = oracle.Oracle(tris, nodes, hdr)
+        acc = np.zeros((h, w, 4), np.float32)
+        for f in range(n):
+            acc, _ = orc.render(w, h, integrator, f, eye, rot, accum=acc, max_bounce=mb)
+        return acc
+
+    parity.assert_parity(a.reshape(-1, 4), oracle_frames(stris, snodes, 21).reshape(-1, 4), f"grown/{integrator}")
+    parity.assert_parity(big.reshape(-1, 4), oracle_frames(ltris, lnodes, 5).reshape(-1, 4), f"large/{integrator}")
