@@ -319,7 +319,7 @@ void pt_denoise_defaults(pt_denoise_params* prm);  /* 5, 2.0, 0.02, 0.2, 6, 1.5 
 int pt_denoise_params_size(void);                  /* sizeof(pt_denoise_params) of the loaded library */
 
 /* The camera's first hit of every pixel of the whole frame (a tile_world > 1 context's non-owned
- * pixels included): startPath's ray with the jitter terms 0 (the pixel centre), pt_trace_closest's
+ * pixels included): the frame kernels' camera ray with the jitter terms 0 (the pixel centre), pt_trace_closest's
  * hit search (reference tie rules), then the integrators' hit record. Three float4 planes,
  * width x height each, row 0 = the bottom row like the accumulation:
  *   pos_t   = (P.x, P.y, P.z, t)

@@ -39,29 +39,29 @@ HIP_FLAGS = [
 CXX_FLAGS = ["-O2", "-fPIC", "-pthread", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall",
              "-D__HIP_PLATFORM_AMD__", f"-I{ROCM}/include"]
 
+# what every device file sees: pt_device.h and pt_trace.h include pt_kernels.h and pt_fmath.h
+_DEV = [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]
+_FRAME = [*_DEV, CSRC / "pt_frame.h", CSRC / "pt_trace.h"]  # pt_frame.h's device half includes pt_trace.h
+_HOST = [CSRC / "pt_runtime.h", CSRC / "pt_frame.h", CSRC / "pt_kernels.h", INCLUDE / "pt_abi.h", CSRC / "pt_rccl.h"]
+
 SOURCES = {
-    "pt_kernels.o": ("hip", CSRC / "pt_kernels.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", CSRC / "pt_trace.h", INCLUDE / "pt_scene.h",
-                                                       INCLUDE / "pt_fmath.h"]),
-    "pt_regen.o": ("hip", CSRC / "pt_regen.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", CSRC / "pt_trace.h",
-                                                   INCLUDE / "pt_fmath.h"]),
-    "pt_envcache.o": ("hip", CSRC / "pt_envcache.hip", [CSRC / "pt_kernels.h"]),
-    "pt_primary.o": ("hip", CSRC / "pt_primary.hip", [CSRC / "pt_kernels.h"]),
+    "pt_kernels.o": ("hip", CSRC / "pt_kernels.hip", [*_FRAME, INCLUDE / "pt_scene.h"]),
+    "pt_regen.o": ("hip", CSRC / "pt_regen.hip", _FRAME),
+    "pt_primary.o": ("hip", CSRC / "pt_primary.hip", _FRAME),
+    "pt_guides.o": ("hip", CSRC / "pt_guides.hip", _FRAME),
+    "pt_display.o": ("hip", CSRC / "pt_display.hip", _FRAME),
+    "pt_basic.o": ("hip", CSRC / "pt_basic.hip", [*_DEV, INCLUDE / "pt_scene.h"]),
+    "pt_diag.o": ("hip", CSRC / "pt_diag.hip", _DEV),
+    "pt_envcache.o": ("hip", CSRC / "pt_envcache.hip", _DEV),
     "pt_build.o": ("hip", CSRC / "pt_build.hip", [CSRC / "pt_kernels.h"]),
-    "pt_guides.o": ("hip", CSRC / "pt_guides.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", CSRC / "pt_trace.h",
-                                                     INCLUDE / "pt_fmath.h"]),
-    "pt_denoise.o": ("hip", CSRC / "pt_denoise.hip", [CSRC / "pt_atrous.h", CSRC / "pt_device.h", CSRC / "pt_kernels.h",
+    "pt_denoise.o": ("hip", CSRC / "pt_denoise.hip", [CSRC / "pt_atrous.h", *_DEV]),
+    "pt_temporal.o": ("hip", CSRC / "pt_temporal.hip", _DEV),
+    "pt_variance.o": ("hip", CSRC / "pt_variance.hip", [CSRC / "pt_atrous.h", *_DEV]),
+    "pt_runtime.o": ("cxx", CSRC / "pt_runtime.cpp", [*_HOST, CSRC / "pt_plan.h", CSRC / "pt_accel.h", INCLUDE / "pt_scene.h",
                                                        INCLUDE / "pt_fmath.h"]),
-    "pt_temporal.o": ("hip", CSRC / "pt_temporal.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]),
-    "pt_moments.o": ("hip", CSRC / "pt_moments.hip", [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]),
-    "pt_variance.o": ("hip", CSRC / "pt_variance.hip", [CSRC / "pt_atrous.h", CSRC / "pt_device.h", CSRC / "pt_kernels.h",
-                                                         INCLUDE / "pt_fmath.h"]),
-    "pt_runtime.o": ("cxx", CSRC / "pt_runtime.cpp", [CSRC / "pt_runtime.h", CSRC / "pt_plan.h", CSRC / "pt_kernels.h", CSRC / "pt_accel.h",
-                                                       INCLUDE / "pt_abi.h", INCLUDE / "pt_scene.h", INCLUDE / "pt_fmath.h",
-                                                       CSRC / "pt_rccl.h"]),
-    "pt_post.o": ("cxx", CSRC / "pt_post.cpp", [CSRC / "pt_runtime.h", CSRC / "pt_kernels.h", INCLUDE / "pt_abi.h",
-                                                 CSRC / "pt_rccl.h"]),
+    "pt_post.o": ("cxx", CSRC / "pt_post.cpp", _HOST),
     "pt_rccl.o": ("cxx", CSRC / "pt_rccl.cpp", [CSRC / "pt_rccl.h"]),
-    "scene.o": ("cxx", CSRC / "scene.cpp", [INCLUDE / "pt_scene.h"]),
+    "scene.o": ("cxx", CSRC / "scene.cpp", [INCLUDE / "pt_scene.h", CSRC / "pt_accel.h", CSRC / "pt_introsort.h"]),
 }
 
 
@@ -154,12 +154,25 @@ PLAN_TABLE = ROOT / "tests" / "native" / "plan_table"
 def build_plan_table(force: bool = False) -> Path:
     """Test infrastructure: the frame path's launch policy (csrc/pt_plan.h) on contexts filled by hand
     (tests/native/plan_table.cpp), host-only: the HIP headers for the types, no HIP library."""
-    deps = [PLAN_TABLE_SRC, CSRC / "pt_plan.h", CSRC / "pt_runtime.h", CSRC / "pt_kernels.h", CSRC / "pt_rccl.h",
-            INCLUDE / "pt_abi.h"]
+    deps = [PLAN_TABLE_SRC, CSRC / "pt_plan.h", *_HOST]
     if force or _stale(PLAN_TABLE, deps):
         _run(["g++", "-std=c++17", "-O1", "-Wall", "-Wno-unused-function", "-D__HIP_PLATFORM_AMD__", f"-I{ROCM}/include",
               f"-I{INCLUDE}", f"-I{CSRC}", str(PLAN_TABLE_SRC), "-o", str(PLAN_TABLE)])
     return PLAN_TABLE
+
+
+SHARE_TABLE_SRC = ROOT / "tests" / "native" / "share_table.cpp"
+SHARE_TABLE = ROOT / "tests" / "native" / "share_table"
+
+
+def build_share_table(force: bool = False) -> Path:
+    """Test infrastructure: the screen-tile share's arithmetic (csrc/pt_frame.h, the host half the kernels
+    share) printed as tables (tests/native/share_table.cpp), host-only like plan_table."""
+    deps = [SHARE_TABLE_SRC, CSRC / "pt_frame.h", CSRC / "pt_kernels.h"]
+    if force or _stale(SHARE_TABLE, deps):
+        _run(["g++", "-std=c++17", "-O1", "-Wall", "-Wno-unused-function", "-D__HIP_PLATFORM_AMD__", f"-I{ROCM}/include",
+              f"-I{INCLUDE}", f"-I{CSRC}", str(SHARE_TABLE_SRC), "-o", str(SHARE_TABLE)])
+    return SHARE_TABLE
 
 
 def build_oracle(force: bool = False) -> Path:
@@ -175,5 +188,6 @@ if __name__ == "__main__":
     build_oracle(force="--force" in sys.argv)
     build_abi_caller(force="--force" in sys.argv)
     build_plan_table(force="--force" in sys.argv)
+    build_share_table(force="--force" in sys.argv)
     print(LIB)
     print(ORACLE_LIB)

@@ -645,16 +645,4 @@ __device__ __forceinline__ V3 tonemapPixel(float4 c, float limit, float gamma) {
   return v3(r, g, b);
 }
 
-// pack (unpack) the pixels of shard tiles t % world == rank in (tile, row, col) order
-__device__ __forceinline__ bool packedPixel(const PackParams& p, long k, int& px, int& py) {
-  const long perTile = (long)p.shardSize * p.shardSize;
-  long j = k / perTile;
-  int within = (int)(k - j * perTile);
-  long g = j * p.world + p.rank;
-  int gy = (int)(g / p.shardsX), gx = (int)(g - (long)gy * p.shardsX);
-  px = gx * p.shardSize + within % p.shardSize;
-  py = gy * p.shardSize + within / p.shardSize;
-  return px < p.width && py < p.height;
-}
-
 }  // namespace pt

@@ -1,0 +1,208 @@
+// pt_display.hip -- what follows a frame kernel over the pixels of a share (pt_frame.h Share, one
+// lane per slot): pass3's tonemap, the pack / unpack of the multi-GPU tile gather, the 8-bit display
+// forms, and the running-mean update of a batch of pipelined frames (mixFrames).
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "pt_device.h"
+#include "pt_frame.h"
+#include "pt_kernels.h"
+
+namespace pt {
+
+// ------------------------------------------------------------ epilogues
+// (tonemapPixel: pt_device.h, shared with the denoiser's colour term)
+__global__ void tonemapKernel(const float4* accum, float* rgb, int n, float limit, float gamma) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const V3 c = tonemapPixel(accum[i], limit, gamma);
+  rgb[3 * i] = c.x;
+  rgb[3 * i + 1] = c.y;
+  rgb[3 * i + 2] = c.z;
+}
+hipError_t launchTonemap(const float4* accum, float* rgb, int n, float limit, float gamma, hipStream_t s) {
+  hipLaunchKernelGGL(tonemapKernel, dim3((n + 255) / 256), dim3(256), 0, s, accum, rgb, n, limit, gamma);
+  return hipGetLastError();
+}
+// pass3's fragColor as the GLUT_RGBA window stores it (OpenglRayTracing/main.cpp glutInitDisplayMode,
+// an 8-bit unsigned-normalised framebuffer): round(clamp(x, 0, 1) * 255), as one fused multiply-add
+// (NaN -> 0)
+__device__ __forceinline__ uint32_t unorm8(float x) {
+  const float c = fminf(fmaxf(x, 0.0f), 1.0f);
+  return (uint32_t)__builtin_fmaf(c, 255.0f, 0.5f);
+}
+
+// packed slots are (r, g, b): the running mean's alpha is 1 for every rendered pixel
+// (IS:868-871 writes vec4(color, 1)), so the gather moves 12 bytes per pixel, not 16
+__global__ void packKernel(PackParams p, const float4* accum, float* packed) {
+  long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.count) return;
+  int px, py;
+  const float4 c = pixelOfSlot(p.share, k, px, py) ? accum[(size_t)py * p.share.width + px] : make_float4(0, 0, 0, 0);
+  packed[3 * k] = c.x;
+  packed[3 * k + 1] = c.y;
+  packed[3 * k + 2] = c.z;
+}
+__global__ void unpackKernel(PackParams p, float4* accum, const float* packed) {
+  long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.count) return;
+  int px, py;
+  if (pixelOfSlot(p.share, k, px, py))
+    accum[(size_t)py * p.share.width + px] = make_float4(packed[3 * k], packed[3 * k + 1], packed[3 * k + 2], 1.0f);
+}
+hipError_t launchPack(const PackParams& p, const float4* accum, float* packed, hipStream_t s) {
+  if (p.count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(packKernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, packed);
+  return hipGetLastError();
+}
+hipError_t launchUnpack(const PackParams& p, float4* accum, const float* packed, hipStream_t s) {
+  if (p.count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(unpackKernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, packed);
+  return hipGetLastError();
+}
+
+// The displayed frame (pass3 into the 8-bit window) of a screen-tile split: each rank packs its
+// own tiles' display values (3 bytes per pixel, packed order) and rank 0 writes its own tiles and
+// unpacks every other rank's into one RGBA8 image -- a quarter of the f32 gather's bytes over xGMI.
+__global__ void displayPackKernel(PackParams p, const float4* accum, float limit, float gamma, uint8_t* packed) {
+  long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.count) return;
+  int px, py;
+  uint32_t r = 0, g = 0, b = 0;
+  if (pixelOfSlot(p.share, k, px, py)) {
+    const V3 c = tonemapPixel(accum[(size_t)py * p.share.width + px], limit, gamma);
+    r = unorm8(c.x), g = unorm8(c.y), b = unorm8(c.z);
+  }
+  packed[3 * k] = (uint8_t)r;
+  packed[3 * k + 1] = (uint8_t)g;
+  packed[3 * k + 2] = (uint8_t)b;
+}
+__global__ void displayOwnKernel(PackParams p, const float4* accum, float limit, float gamma, uchar4* image) {
+  long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.count) return;
+  int px, py;
+  if (!pixelOfSlot(p.share, k, px, py)) return;
+  const size_t i = (size_t)py * p.share.width + px;
+  const V3 c = tonemapPixel(accum[i], limit, gamma);
+  image[i] = make_uchar4((uint8_t)unorm8(c.x), (uint8_t)unorm8(c.y), (uint8_t)unorm8(c.z), 255);
+}
+hipError_t launchDisplayPack(const PackParams& p, const float4* accum, float limit, float gamma, uint8_t* packed,
+                             hipStream_t s) {
+  if (p.count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(displayPackKernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, limit,
+                     gamma, packed);
+  return hipGetLastError();
+}
+hipError_t launchDisplayOwn(const PackParams& p, const float4* accum, float limit, float gamma, uchar4* image,
+                            hipStream_t s) {
+  if (p.count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(displayOwnKernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, limit,
+                     gamma, image);
+  return hipGetLastError();
+}
+// blockIdx.y = rank - 1 of ranks 1..world-1 (their packed buffers in d.src)
+__global__ void displayUnpackKernel(RanksUnpack d, uchar4* image) {
+  const int rank = blockIdx.y + 1;
+  const uint8_t* src = static_cast<const uint8_t*>(d.src[rank]);
+  if (!src) return;
+  PackParams p = d.base;
+  p.share.rank = rank;
+  p.count = d.count[rank];
+  long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.count) return;
+  int px, py;
+  if (pixelOfSlot(p.share, k, px, py))
+    image[(size_t)py * p.share.width + px] = make_uchar4(src[3 * k], src[3 * k + 1], src[3 * k + 2], 255);
+}
+hipError_t launchDisplayUnpack(const RanksUnpack& d, int world, uchar4* image, hipStream_t s) {
+  long most = 0;
+  for (int k = 1; k < world; k++) most = d.count[k] > most ? d.count[k] : most;
+  if (world < 2 || most <= 0) return hipSuccess;
+  hipLaunchKernelGGL(displayUnpackKernel, dim3((unsigned)((most + 255) / 256), (unsigned)(world - 1)), dim3(256), 0, s,
+                     d, image);
+  return hipGetLastError();
+}
+
+// unpackKernel of ranks 1..world-1 in one launch (blockIdx.y = rank - 1): rank 0's reassembly of
+// a gather of the f32 running means after each batch of frames
+__global__ void unpackRanksKernel(RanksUnpack d, float4* accum) {
+  const int rank = blockIdx.y + 1;
+  const float* src = static_cast<const float*>(d.src[rank]);
+  if (!src) return;
+  PackParams p = d.base;
+  p.share.rank = rank;
+  p.count = d.count[rank];
+  long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.count) return;
+  int px, py;
+  if (pixelOfSlot(p.share, k, px, py))
+    accum[(size_t)py * p.share.width + px] = make_float4(src[3 * k], src[3 * k + 1], src[3 * k + 2], 1.0f);
+}
+hipError_t launchUnpackRanks(const RanksUnpack& d, int world, float4* accum, hipStream_t s) {
+  long most = 0;
+  for (int k = 1; k < world; k++) most = d.count[k] > most ? d.count[k] : most;
+  if (world < 2 || most <= 0) return hipSuccess;
+  hipLaunchKernelGGL(unpackRanksKernel, dim3((unsigned)((most + 255) / 256), (unsigned)(world - 1)), dim3(256), 0, s,
+                     d, accum);
+  return hipGetLastError();
+}
+
+// The running means of a batch of pipelined frames (storeSample's update, deferred to frame order):
+// frame f's colours at col + f * colStride, slot k of the share (pt_frame.h slotOf), its weight
+// 1 / (frameCounter + f + 1); the pixel's mean after each frame is the one serial frames store (mixf
+// of the same floats).
+// MOMENTS (a PT_FLAG_MOMENTS context, pt_abi.h): plus the running means of the sample luminance l and
+// of l * l, kept per pixel in a float2 plane (m1, m2) -- the same loop, the same weights and the same
+// mixf as the colour, so the accumulation equals a plain context's bit for bit.
+// tests/variance_ref.py (moments_update) is the specification: l = (0.3 r + 0.6 g) + 0.1 b is
+// tonemapPixel's luminance, one f32 operation each (no fused multiply-add).
+// Per pixel and launch: 32 B of accumulation and 16 B of moments (read + written once each, streaming
+// like the accumulation) and 12 B per frame of sample colour.
+template <bool MOMENTS>
+__device__ __forceinline__ void mixFrames(const PackParams& p, float4* accum, float2* moments, const float* col,
+                                          size_t colStride, int nFrames, uint32_t frameCounter) {
+  long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.count) return;
+  int px, py;
+  if (!pixelOfSlot(p.share, k, px, py)) return;
+  const size_t i = (size_t)py * p.share.width + px;
+  float4 a = ldStream(accum + i);
+  float2 m = make_float2(0.0f, 0.0f);
+  if (MOMENTS) m = ldStream(moments + i);
+  for (int f = 0; f < nFrames; f++) {
+    const float3 c = ldCol(col + ((size_t)f * colStride + k) * COL_F);
+    const float w = 1.0f / (float)(frameCounter + (uint32_t)f + 1u);
+    a = make_float4(mixf(a.x, c.x, w), mixf(a.y, c.y, w), mixf(a.z, c.z, w), 1.0f);
+    if (MOMENTS) {
+      const float l = (0.3f * c.x + 0.6f * c.y) + 0.1f * c.z;
+      m = make_float2(mixf(m.x, l, w), mixf(m.y, l * l, w));
+    }
+  }
+  stStream(accum + i, a);
+  if (MOMENTS) stStream(moments + i, m);
+}
+__global__ void mixKernel(PackParams p, float4* accum, const float* col, size_t colStride, int nFrames,
+                          uint32_t frameCounter) {
+  mixFrames<false>(p, accum, nullptr, col, colStride, nFrames, frameCounter);
+}
+__global__ void mixMomentsKernel(PackParams p, float4* accum, float2* moments, const float* col, size_t colStride,
+                                 int nFrames, uint32_t frameCounter) {
+  mixFrames<true>(p, accum, moments, col, colStride, nFrames, frameCounter);
+}
+hipError_t launchMix(const PackParams& p, float4* accum, const float* col, size_t colStride, int nFrames,
+                     uint32_t frameCounter, hipStream_t s) {
+  if (p.count <= 0 || nFrames <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mixKernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, col, colStride,
+                     nFrames, frameCounter);
+  return hipGetLastError();
+}
+hipError_t launchMixMoments(const PackParams& p, float4* accum, float2* moments, const float* col, size_t colStride,
+                            int nFrames, uint32_t frameCounter, hipStream_t s) {
+  if (p.count <= 0 || nFrames <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mixMomentsKernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, moments, col,
+                     colStride, nFrames, frameCounter);
+  return hipGetLastError();
+}
+
+}  // namespace pt

@@ -1,6 +1,6 @@
 // pt_guides.hip -- guide buffers of the camera's first hit (pt_abi.h pt_render_guides): for every
-// pixel of the frame the camera ray through the pixel centre (startPath's ray, pt_regen.hip,
-// with the jitter terms 0), the batch query's hit search (Tracer::trace: the runtime's tree,
+// pixel of the frame the camera ray through the pixel centre (pt_frame.h cameraDir, the frame
+// kernels' ray with the jitter terms 0), the batch query's hit search (Tracer::trace: the runtime's tree,
 // results checked against the reference's, reference tie rules) and the integrators' hit record
 // (finishHit). One lane per pixel, one wave per 8x8 tile; the waves of a resident grid walk the
 // tiles in a grid-stride loop, so the traversal stack's overflow area is bounded by the grid.
@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "pt_device.h"
+#include "pt_frame.h"
 #include "pt_kernels.h"
 #include "pt_trace.h"
 
@@ -32,18 +33,12 @@ __global__ __launch_bounds__(BLOCK) void guidesKernel(GuideParams p) {
   const int numTiles = tilesX * tilesY;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   constexpr int WAVES = BLOCK / 64;
-  const float* M = p.cam;
-  const V3 c0 = v3(M[0], M[1], M[2]), c1 = v3(M[4], M[5], M[6]), c2 = v3(M[8], M[9], M[10]), c3 = v3(M[12], M[13], M[14]);
   const V3 o = v3(p.eye[0], p.eye[1], p.eye[2]);
   for (int tile = blockIdx.x * WAVES + wave; tile < numTiles; tile += gridDim.x * WAVES) {
     const int ty = tile / tilesX, tx = tile - ty * tilesX;
     const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
     if (px >= W || py >= H) continue;
-    // startPath (IS:846-850) with ax = ay = 0
-    const float pixx = (float)(2 * px + 1) / (float)W - 1.0f;
-    const float pixy = (float)(2 * py + 1) / (float)H - 1.0f;
-    const float x = pixx + 0.0f, y = pixy + 0.0f, z = -1.5f;
-    const V3 d = normalize((c0 * x + c1 * y) + (c2 * z + c3 * 0.0f));
+    const V3 d = cameraDir(p.cam, W, H, px, py, 0.0f, 0.0f);  // IS:846-850 with ax = ay = 0
     float t;
     const int tri = tr.trace(o, d, t);
     float4 a = make_float4(0.0f, 0.0f, 0.0f, PT_INF);

@@ -1,5 +1,5 @@
 // pt_kernels.h -- kernel parameter blocks and launchers shared by
-// pt_kernels.hip (device) and pt_runtime.cpp (host).
+// the .hip files (device) and pt_runtime.cpp / pt_post.cpp (host).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -208,10 +208,21 @@ struct FrameRef {
   uint32_t sampleIndex;
 };
 
+// A context's screen-tile share of the image: shard tiles (shardSize x shardSize pixels, row-major ids
+// over the image, shardsX per row) g with g % world == rank, in id order. pt_frame.h holds everything
+// derived from it: the share's wave tiles, its slots (the packed order of pt_pack_owned) and their pixels.
+struct Share {
+  int width, height;
+  int shardSize;  // shard tile edge (multiple of 8)
+  int shardsX;    // shard tiles per row
+  int rank, world;
+};
+
 struct RenderParams {
   SceneView scene;
   Env env;
-  int width, height;
+  int width, height;    // the six fields of the context's Share (pt_frame.h shareOf / setShare) keep their places
+                        // in the block: the frame kernels' scalar register use follows its layout
   uint32_t frameCounter;  // running-mean count: weight 1/(frameCounter+1) (IS:868-871)
   uint32_t sampleIndex;   // RNG / Sobol sample index: frameCounter*sample_world + sample_rank
   int maxBounce;
@@ -225,8 +236,8 @@ struct RenderParams {
   // A batch of nFrames consecutive frames of one camera in this launch (pt_render_frames_async):
   // frame f draws sample index sampleIndex + f * sampleStride and writes its colours to
   // col + f * colStride and its camera-ray results to primHit + f * colStride, each indexed by the
-  // pixel's slot in this context's screen-tile share (shareIndex: the packed order of
-  // pt_pack_owned; colStride = the share's slots), so a 1/N share's buffers are 1/N of a frame. Work
+  // pixel's slot in this context's screen-tile share (pt_frame.h slotOf: the packed order of
+  // pt_pack_owned; colStride = slots(share)), so a 1/N share's buffers are 1/N of a frame. Work
   // item k of the launch is item k / nFrames of frame k % nFrames, so the frames of one tile
   // run side by side (the same camera rays, the same nodes). nFrames 1: a single frame.
   int nFrames;
@@ -260,9 +271,9 @@ struct RenderParams {
   int zeroQueue;  // the camera-ray pass zeroes `queue` for the frame kernel after it (no memset)
   int* queue;           // NUM_QUEUES counters (stride CTL_LINE_INTS), zeroed before each launch
   int perQueue;         // items per queue (band), claimed once per frame of the launch
-  int numItems;         // 8x8 wave tiles owned by this rank
+  int numItems;         // 8x8 wave tiles owned by this rank (slots(share) / 64)
   int shardSize;        // shard tile edge (multiple of 8)
-  int shardTiles;       // (shardSize/8)^2
+  int shardTiles;       // (shardSize/8)^2, the divisor of the kernels' tile -> shard tile step
   int shardsX;          // shard tiles per row
   int rank, world;
   int* ovf;             // traversal stack overflow (per thread ovfDepth ints), may be null
@@ -288,7 +299,7 @@ struct TraceParams {
   int ovfDepth;
 };
 
-// BasicRayTracingWithC++ (pt_kernels.hip basicKernel): one sample k of every pixel
+// BasicRayTracingWithC++ (pt_basic.hip basicKernel): one sample k of every pixel
 constexpr int BASIC_MAX_DEPTH = 31;  // pathTracing vertices kept for the fold (the reference's cutoff is 8)
 struct BasicParams {
   const double* shapes;         // nShapes x PT_SHAPE_DOUBLES
@@ -308,8 +319,8 @@ struct BasicParams {
 };
 
 struct PackParams {
-  int width, height, shardSize, shardsX, rank, world;
-  long count;
+  Share share;
+  long count;  // slots(share)
 };
 // rank 0's unpack of ranks 1..world-1's packed buffers in one launch (pt_display_unpack: RGB8
 // display values; pt_unpack_ranks: f32 running means); null buffers are skipped; base's rank /
@@ -403,11 +414,18 @@ hipError_t launchPrimary(const RenderParams& p, hipStream_t s);
 // the live items of every work queue from the pass's tile masks (p.liveItems), for the regen kernels
 hipError_t launchLiveList(const RenderParams& p, hipStream_t s);
 // the path-regeneration kernel (pt_regen.hip): the variant and launch shape of a frame
+struct RegenVariant {     // one instantiation of regenKernel and what the host needs to know of it
+  const void* fn = nullptr;
+  int waves = 0;          // waves per SIMD it is compiled for (0: the integrator's default)
+  int block = BLOCK;      // threads per block
+  bool lists = true;      // it claims from live-item lists after a camera-ray pass
+  int top4 = 0;           // 4-wide nodes it stages in LDS (PT_REGEN_TOP4[_3])
+};
 struct RegenShape {
   bool wide = false;      // the large-scene variant (WIDE_REGEN_WAVES, 4-wide walk, dynamic ray fetch)
   bool fullTree = false;  // ... with the whole 4-wide tree in LDS (small trees, uniform integrators)
   bool small = false;     // the MIS variant at PT_WIDE_REGEN_WAVES_SMALL waves per SIMD (scenes that fit the L2s)
-  int block = BLOCK;      // threads per block
+  RegenVariant v;         // the kernel these choose (pt_regen.hip regenVariant)
   int blocksPerCU = 0;    // resident blocks per CU
   size_t dynLds = 0;      // dynamic LDS bytes per block (the tree)
 };
@@ -417,7 +435,7 @@ hipError_t regenShape(int integrator, bool cull, bool wide, int f4nDev, bool sma
 hipError_t launchRegen(const RenderParams& p, int integrator, int grid, hipStream_t s, bool cull, const RegenShape& r);
 bool regenTakesLists(int integrator, const RegenShape& r);  // the variant claims from live-item lists after a pass
 int regenLdsStack();
-int regenTop4(const RegenShape& r, int integrator);  // 4-wide nodes the wide regen kernel stages in LDS (PT_REGEN_TOP4[_3])
+int regenTop4(const RegenShape& r, int integrator);  // 4-wide nodes the wide regen kernel stages in LDS
 hipError_t launchTrace(const TraceParams& p, int grid, hipStream_t s, bool cull);
 // Guide buffers (pt_guides.hip): the camera's first hit of every pixel centre, one lane per pixel,
 // one wave per 8x8 tile (a grid-stride loop over the tiles), three float4 planes
@@ -527,7 +545,7 @@ hipError_t launchUnpack(const PackParams& p, float4* accum, const float* packed,
 // 1 / (frameCounter + f + 1)) (IS:868-871, pass2.fsh:15) -- each pixel read and written once
 hipError_t launchMix(const PackParams& p, float4* accum, const float* col, size_t colStride, int nFrames,
                      uint32_t frameCounter, hipStream_t s);
-// launchMix of a PT_FLAG_MOMENTS context (pt_moments.hip): the same update of accum, and with the same
+// launchMix of a PT_FLAG_MOMENTS context (pt_display.hip mixFrames<true>): the same update of accum, and with the same
 // weights the running means (m1, m2) of each sample's luminance l and of l * l in `moments`
 hipError_t launchMixMoments(const PackParams& p, float4* accum, float2* moments, const float* col, size_t colStride,
                             int nFrames, uint32_t frameCounter, hipStream_t s);

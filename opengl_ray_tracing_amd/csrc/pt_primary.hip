@@ -1,4 +1,5 @@
-// pt_primary.hip -- camera-ray bins: for one camera, the triangles each 8x8
+// pt_primary.hip -- camera-ray bins, and the camera-ray pass that reads them before a frame
+// kernel (primaryKernel, liveListKernel; at the end). The bins: for one camera, the triangles each 8x8
 // pixel tile's camera rays can hit, so the megakernel finds a camera ray's
 // closest hit by testing its tile's few triangles (pass1.fsh hitTriangle
 // IS:251-301, the same test as the traversal's) instead of walking the BVH
@@ -27,7 +28,9 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
+#include "pt_frame.h"
 #include "pt_kernels.h"
+#include "pt_trace.h"
 
 namespace pt {
 
@@ -218,6 +221,140 @@ void freePrimaryBins(PrimaryBins& b) {
                   (void*)b.binTris, (void*)b.binGeo, (void*)b.binBox, b.tmp})
     if (p) (void)hipFree(p);
   b = PrimaryBins{};
+}
+
+// ------------------------------------------------------------ camera-ray pass
+// Camera-ray pass: the bin path of primaryPacket (pt_kernels.hip) for every 8x8 tile of the
+// rank, one wave per tile, before the megakernel. Inside the persistent
+// megakernel (3 waves/SIMD) a tile's camera rays are a chain of dependent
+// round trips (claim, bin, triangles, refReachable, env) that the few resident
+// waves cannot hide; here a launch of one short wave per tile keeps up to 8
+// waves per SIMD in flight and claims nothing. Sky pixels are finished here;
+// every other pixel's result goes to primHit for the megakernel.
+__global__ __launch_bounds__(64) void primaryKernel(RenderParams p) {
+  __shared__ float4 s_tri[PT_PASS_BIN_CAP * 4];
+  __shared__ float4 s_box[PT_PASS_BIN_CAP * 2];
+  __shared__ int s_idx[PT_PASS_BIN_CAP];
+  // block b: tile b / nFrames of frame b % nFrames (a batch's frames of one tile side by side).
+  // (Blocks of 2 / 4 / 8 such one-wave items, fewer workgroups for the dispatcher: c2's 1/8 share of
+  // a 20-frame batch 88.6 -> 92.2 / 93.4 / 102.2 us; one block per tile for several frames: DESIGN.md 3b.)
+  const int fr = (int)(blockIdx.x % (unsigned)p.nFrames);
+  const int w = (int)(blockIdx.x / (unsigned)p.nFrames);
+  const int lane = threadIdx.x;
+  if (p.zeroQueue && blockIdx.x == 0)  // the frame kernel's work-queue counters, zeroed for it (it runs next on this stream)
+    for (int q = lane; q < NUM_QUEUES; q += 64) p.queue[q * CTL_LINE_INTS] = 0;
+  const int2 o = tileOrigin(shareOf(p), w, p.shardTiles);
+  const int px = o.x + (lane & 7);
+  const int py = o.y + (lane >> 3);
+  const bool valid = px < p.width && py < p.height;
+  const int tx = o.x >> 3, ty = o.y >> 3;
+  int b0 = 0, b1 = 0;  // a tile wholly outside the image has no bin (and no valid lane)
+  if (tx < p.binTilesX && ty < p.binTilesY) {
+    b0 = p.binStart[ty * p.binTilesX + tx];
+    b1 = p.binStart[ty * p.binTilesX + tx + 1];
+  }
+  const int n = b1 - b0;
+  // the tile's results compacted (RenderParams::primMask): the slots that need a path, in slot order
+  int2* out = p.primHit + ((size_t)fr * p.numItems + w) * 64;
+  unsigned long long* mask = p.primMask + (size_t)fr * p.numItems + w;
+  const FrameRef fp = frameRef(p, fr);  // this block's frame (storeSample's colour buffer)
+  if (n > PT_PASS_BIN_CAP) {  // the frame kernel traces this tile's camera rays (the megakernel as a packet)
+    const unsigned long long m = __ballot(valid);
+    if (valid) out[__popcll(m & ((1ull << lane) - 1ull))] = make_int2(PRIM_TILE, 0);
+    if (lane == 0) *mask = m;
+    return;
+  }
+  // the bin's triangles and their leaf boxes in bin order (binGeo / binBox, gathered at bin build): one
+  // round trip after binStart instead of binTris -> geo, and refReachable's leaf box from LDS
+  // (an empty bin -- every camera ray of the tile is sky -- stages nothing and needs no barrier)
+  if (n > 0) {
+    for (int t = lane >> 2; t < n; t += 16) {  // one float4 of one triangle (and of its leaf box) per lane
+      s_tri[4 * t + (lane & 3)] = p.binGeo[4 * (size_t)(b0 + t) + (lane & 3)];
+      if ((lane & 3) < 2) s_box[2 * t + (lane & 3)] = p.binBox[2 * (size_t)(b0 + t) + (lane & 3)];
+      else if ((lane & 3) == 2) s_idx[t] = p.binTris[b0 + t];
+    }
+    __syncthreads();
+  }
+  uint32_t seed;
+  const V3 dir = cameraRay(p, fp.sampleIndex, valid ? px : 0, valid ? py : 0, seed);
+  const V3 eye = v3(p.eye[0], p.eye[1], p.eye[2]);
+  float tbest;
+  int best;
+  bool tie;
+  closestInBin(n, valid, eye, dir, [&](int k) { return s_tri + 4 * k; }, tbest, best, tie);
+  uint32_t rays = 0;
+  int res = PRIM_MISS;
+  if (valid) {
+    res = best >= 0 ? s_idx[best] : PRIM_MISS;
+    if (tie || (res >= 0 && !refReachableBox(p.scene, s_box[2 * best], s_box[2 * best + 1], eye, dir, tbest))) {
+      res = PRIM_RETRACE;  // counted by the megakernel's retrace
+    } else {
+      rays = 1;
+      if (res == PRIM_MISS) storeSample(p, fp, px, py, sampleHdr(p.env, dir));
+    }
+  }
+  const bool need = valid && res != PRIM_MISS;
+  const unsigned long long m = __ballot(need);
+  if (need) out[__popcll(m & ((1ull << lane) - 1ull))] = make_int2(res, __float_as_int(tbest));
+  if (lane == 0) *mask = m;
+  addRays(p.rayShards, rays);
+}
+
+hipError_t launchPrimary(const RenderParams& p, hipStream_t s) {
+  if (!p.primHit || !p.primMask || !p.binStart || !p.binGeo || !p.binBox || p.numItems <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(primaryKernel, dim3((unsigned)p.numItems * (unsigned)p.nFrames), dim3(64), 0, s, p);
+  return hipGetLastError();
+}
+
+// Live-item lists (RenderParams::liveItems): block q walks work queue q's items in claim order
+// (TileCursor::next: item `it` is tile q * perQueue + it / nFrames of frame it % nFrames) and keeps,
+// in that order, those whose camera-ray mask is not 0 -- a ballot per wave, the waves' counts
+// summed through LDS -- so a regen wave's claim never lands on a tile the pass has finished
+// (c2 at 1080p: 55 % of the tiles are all sky, c3 96 %). The list is a function
+// of the masks alone: the same items in the same order on every run.
+constexpr int LIVE_BS = 1024;
+__global__ __launch_bounds__(LIVE_BS) void liveListKernel(RenderParams p) {
+  __shared__ int s_wave[LIVE_BS / 64];
+  const int q = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int nF = p.nFrames, total = p.perQueue * nF;
+  uint4* seg = p.liveItems + (size_t)q * liveStride(p.perQueue, nF);
+  uint4* out = seg + LIVE_HEAD;
+  auto load = [&](int it, int& t, int& fr) -> unsigned long long {
+    const int k = it / nF;
+    fr = it - k * nF;
+    t = q * p.perQueue + k;
+    return it < total && t < p.numItems ? p.primMask[(size_t)fr * p.numItems + t] : 0ull;
+  };
+  int base = 0;  // live items of the rounds before this one
+  int t, fr;
+  unsigned long long m = load((int)threadIdx.x, t, fr);
+  for (int it0 = 0; it0 < total; it0 += LIVE_BS) {
+    int tn, frn;  // the next round's mask, in flight across this round's barriers
+    const unsigned long long mn = load(it0 + LIVE_BS + (int)threadIdx.x, tn, frn);
+    const unsigned long long b = __ballot(m != 0);
+    if (lane == 0) s_wave[wv] = __popcll(b);
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int w = 0; w < LIVE_BS / 64; w++) {
+      const int c = s_wave[w];
+      before += w < wv ? c : 0;
+      all += c;
+    }
+    if (m != 0)
+      out[base + before + __popcll(b & ((1ull << lane) - 1ull))] = make_uint4((uint32_t)t, (uint32_t)fr, (uint32_t)m, (uint32_t)(m >> 32));
+    base += all;
+    __syncthreads();
+    m = mn;
+    t = tn;
+    fr = frn;
+  }
+  if (threadIdx.x == 0) seg[0] = make_uint4((uint32_t)base, 0u, 0u, 0u);  // the count, on the segment's first line
+}
+
+hipError_t launchLiveList(const RenderParams& p, hipStream_t s) {
+  if (!p.primMask || !p.liveItems || p.numItems <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(liveListKernel, dim3(NUM_QUEUES), dim3(LIVE_BS), 0, s, p);
+  return hipGetLastError();
 }
 
 }  // namespace pt

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "pt_device.h"
+#include "pt_frame.h"
 #include "pt_kernels.h"
 #include "pt_trace.h"
 
@@ -71,7 +72,7 @@ constexpr int regenTop4W(int waves) { return waves == 3 ? PT_REGEN_TOP4_3 : PT_R
 // hand-out's state; materials staged in LDS per block measured c2 -0.6 %, within noise. Both knobs
 // were deleted in round 6, git history keeps them.)
 
-// live-item lists (pt_kernels.hip liveListKernel) for every regen variant but the MIS one of the scenes
+// live-item lists (pt_primary.hip liveListKernel) for every regen variant but the MIS one of the scenes
 // that outgrow the L2s, whose launches fill the machine for milliseconds: a list kernel between the
 // pass and the frame kernel waits there for room as long as the pass itself (c5 4.07 -> 4.49 ms per frame)
 constexpr bool regenLists(int integ, int waves) {
@@ -97,14 +98,13 @@ struct PathState {
   bool haveB;    // MIS: a BRDF ray follows the shadow ray
 };
 
-__device__ __forceinline__ uint32_t sampleOf(const RenderParams& p, const PathState& s) {
-  return p.sampleIndex + (uint32_t)s.fr * p.sampleStride;
-}
-
+// The path's finished sample: pt_frame.h storeSample's two stores, kept as this kernel's own text. With
+// the shared function (the frame's colour pointer formed first, then the slot) the wide MIS variant
+// spills 13 VGPRs for 10 (hipcc -Rpass-analysis=kernel-resource-usage).
 __device__ __forceinline__ void writeAccum(const RenderParams& p, const PathState& s, V3 color) {
   const int px = s.px, py = s.py;
-  if (p.col) {  // pipelined frame: the sample colour; mixKernel updates the running mean in frame order
-    stCol(p.col + ((size_t)s.fr * p.colStride + shareIndex(p, px, py)) * COL_F, color.x, color.y, color.z);
+  if (p.col) {  // pipelined frame: the sample colour; mixFrames updates the running mean in frame order
+    stCol(p.col + ((size_t)s.fr * p.colStride + slotOf(shareOf(p), px, py)) * COL_F, color.x, color.y, color.z);
     return;
   }
   float4* a = p.accum + (size_t)py * p.width + px;
@@ -127,7 +127,10 @@ __device__ __forceinline__ int rankBelow(unsigned long long m) {
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-// the first pixel of 8x8 wave tile `tile` of this context's screen-tile share
+// The first pixel of 8x8 wave tile `tile` of this context's share: pt_frame.h tileOrigin's two
+// coordinates, kept as this kernel's own text for the same reason as writeAccum (calling tileOrigin
+// here, whole or per coordinate, moves the wide variants' VGPR spills from 18 / 3 / 22 / 22 to 20 / 4 /
+// 27 / 26-32). tests/test_share.py pins tileOrigin; test_frame_kernels_agree pins these to it.
 __device__ __forceinline__ int tilePx(const RenderParams& p, int tile, int sub) {
   const int j = tile / p.shardTiles, sI = tile - j * p.shardTiles;
   const int g = j * p.world + p.rank;
@@ -139,18 +142,9 @@ __device__ __forceinline__ int tilePy(const RenderParams& p, int tile, int sub) 
   return (g / p.shardsX) * p.shardSize + (sI / sub) * 8;
 }
 
-// main IS:846-850: seed and camera ray of pixel (px, py)
+// main IS:846-850: seed and camera ray of pixel (px, py) (pt_frame.h cameraRay)
 __device__ __forceinline__ void startPath(const RenderParams& p, PathState& s) {
-  const int W = p.width, H = p.height;
-  s.seed = ((uint32_t)s.px * 1973u + (uint32_t)s.py * 9277u + sampleOf(p, s) * 26699u) | 1u;
-  float pixx = (float)(2 * s.px + 1) / (float)W - 1.0f;
-  float pixy = (float)(2 * s.py + 1) / (float)H - 1.0f;
-  float ax = (randf(s.seed) - 0.5f) / (float)W;
-  float ay = (randf(s.seed) - 0.5f) / (float)H;
-  float x = pixx + ax, y = pixy + ay, z = -1.5f;
-  const float* M = p.cam;
-  V3 c0 = v3(M[0], M[1], M[2]), c1 = v3(M[4], M[5], M[6]), c2 = v3(M[8], M[9], M[10]), c3 = v3(M[12], M[13], M[14]);
-  s.d = normalize((c0 * x + c1 * y) + (c2 * z + c3 * 0.0f));
+  s.d = cameraRay(p, frameRef(p, s.fr).sampleIndex, s.px, s.py, s.seed);
   s.o = v3(p.eye[0], p.eye[1], p.eye[2]);
   s.kind = K_PRIMARY;
   s.bounce = 0;
@@ -200,7 +194,7 @@ __device__ __forceinline__ bool continueFromHit(const RenderParams& p, PathState
     s.shC = (c * dot(N, L)) / pdf_light;
     shadow = true;
   }
-  const uint32_t gi = grayCode(sampleOf(p, s) + 1u);
+  const uint32_t gi = grayCode(frameRef(p, s.fr).sampleIndex + 1u);
   float u = sobolf(2u * (uint32_t)nb, gi);
   float v = sobolf(2u * (uint32_t)nb + 1u, gi);
   cranleyPatterson(s.px, s.py, u, v);
@@ -659,24 +653,30 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
 #endif
 constexpr int FULL_BS = 256 * PT_WIDE_REGEN_WAVES_U;  // one block per CU: all its waves share the tree
 constexpr size_t LDS_BYTES = 160 * 1024;
-template <int I>
-static const void* regenFn(bool cull, bool wide, bool full, bool small) {
-  if constexpr (I != 2 && PT_REGEN_YIELD > 0)  // the uniform integrators' variant only
-    if (full) return (const void*)regenKernel<I, true, wideRegenWaves(I), true, FULL_BS, true>;
-  if constexpr (I == 2 && PT_WIDE_REGEN_WAVES_SMALL != PT_WIDE_REGEN_WAVES)
-    if (wide && small) return (const void*)regenKernel<I, true, PT_WIDE_REGEN_WAVES_SMALL, true>;
-  if (wide) return (const void*)regenKernel<I, true, wideRegenWaves(I), true>;
-  return cull ? (const void*)regenKernel<I, true> : (const void*)regenKernel<I, false>;
+// The one statement of which instantiation a frame runs and of what follows from it (RegenVariant):
+// regenShape keeps it, launchRegen launches its fn, the runtime reads its lists / top4 / block.
+template <int I, bool CULL, int WAVES = 0, bool W4 = false, int BS = BLOCK, bool FULL = false>
+static RegenVariant variantOf() {
+  return {(const void*)regenKernel<I, CULL, WAVES, W4, BS, FULL>, WAVES, BS, regenLists(I, WAVES), regenTop4W(WAVES)};
 }
-static const void* regenFnI(int integrator, bool cull, bool wide, bool full, bool small = false) {
-  return integrator == 0   ? regenFn<0>(cull, wide, full, small)
-         : integrator == 1 ? regenFn<1>(cull, wide, full, small)
-                           : regenFn<2>(cull, wide, full, small);
+template <int I>
+static RegenVariant regenVariantI(bool cull, bool wide, bool small, bool full) {
+  if constexpr (I != 2 && PT_REGEN_YIELD > 0)  // the uniform integrators' variant only
+    if (full) return variantOf<I, true, wideRegenWaves(I), true, FULL_BS, true>();
+  if constexpr (I == 2 && PT_WIDE_REGEN_WAVES_SMALL != PT_WIDE_REGEN_WAVES)
+    if (wide && small) return variantOf<I, true, PT_WIDE_REGEN_WAVES_SMALL, true>();
+  if (wide) return variantOf<I, true, wideRegenWaves(I), true>();
+  return cull ? variantOf<I, true>() : variantOf<I, false>();
+}
+static RegenVariant regenVariant(int integrator, bool cull, bool wide, bool small, bool full) {
+  return integrator == 0   ? regenVariantI<0>(cull, wide, small, full)
+         : integrator == 1 ? regenVariantI<1>(cull, wide, small, full)
+                           : regenVariantI<2>(cull, wide, small, full);
 }
 
 static long long fullStaticLds(int integrator) {
   hipFuncAttributes fa;
-  if (hipFuncGetAttributes(&fa, regenFnI(integrator, true, true, true)) != hipSuccess) return -1;
+  if (hipFuncGetAttributes(&fa, regenVariant(integrator, true, true, false, true).fn) != hipSuccess) return -1;
   return (long long)fa.sharedSizeBytes;
 }
 
@@ -697,57 +697,33 @@ hipError_t regenShape(int integrator, bool cull, bool wide, int f4nDev, bool sma
   // the walks run traceRay4, which reads an LDS top at the built 8-float4 stride
   r.fullTree = PT_LDS_TREE && PT_REGEN_YIELD > 0 && r.wide && integrator != 2 && f4nDev > 0 &&
                treeBytes + staticBytes <= LDS_BYTES;
-  r.block = r.fullTree ? FULL_BS : BLOCK;
   r.dynLds = r.fullTree ? treeBytes : 0;
-  const void* f = regenFnI(integrator, cull, r.wide, r.fullTree, r.small);
+  r.v = regenVariant(integrator, cull, r.wide, r.small, r.fullTree);
+  const void* f = r.v.fn;
   if (r.fullTree) {
     // room for any tree that fits beside the static LDS; a function attribute is per device, and
     // setting it is cheap, so every shape query on the current device sets it
     hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_BYTES - staticBytes));
     if (e != hipSuccess) return e;
   }
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&r.blocksPerCU, f, r.block, r.dynLds);
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&r.blocksPerCU, f, r.v.block, r.dynLds);
   *out = r;
   return e;
 }
 
-template <int I>
-static hipError_t launchRegenI(const RenderParams& p, int grid, hipStream_t s, bool cull, const RegenShape& r) {
-  if constexpr (I != 2 && PT_REGEN_YIELD > 0) {
-    if (r.fullTree) {
-      hipLaunchKernelGGL((regenKernel<I, true, wideRegenWaves(I), true, FULL_BS, true>), dim3(grid), dim3(FULL_BS),
-                         r.dynLds, s, p);
-      return hipGetLastError();
-    }
-  }
-  if (r.fullTree) return hipErrorInvalidValue;
-  if constexpr (I == 2 && PT_WIDE_REGEN_WAVES_SMALL != PT_WIDE_REGEN_WAVES)
-    if (r.wide && r.small) {
-      hipLaunchKernelGGL((regenKernel<I, true, PT_WIDE_REGEN_WAVES_SMALL, true>), dim3(grid), dim3(BLOCK), 0, s, p);
-      return hipGetLastError();
-    }
-  if (r.wide)
-    hipLaunchKernelGGL((regenKernel<I, true, wideRegenWaves(I), true>), dim3(grid), dim3(BLOCK), 0, s, p);
-  else if (cull) hipLaunchKernelGGL((regenKernel<I, true>), dim3(grid), dim3(BLOCK), 0, s, p);
-  else hipLaunchKernelGGL((regenKernel<I, false>), dim3(grid), dim3(BLOCK), 0, s, p);
+// the kernel the shape's occupancy was asked of, with its block and dynamic LDS; a shape made for
+// another integrator or culling than the caller names is refused
+hipError_t launchRegen(const RenderParams& p, int integrator, int grid, hipStream_t s, bool cull, const RegenShape& r) {
+  if (!r.v.fn || r.v.fn != regenVariant(integrator, cull, r.wide, r.small, r.fullTree).fn) return hipErrorInvalidValue;
+  if (r.fullTree && p.scene.f4nTop * W4_LDS_F4 * sizeof(float4) > r.dynLds) return hipErrorInvalidValue;
+  void* args[] = {const_cast<RenderParams*>(&p)};
+  (void)hipLaunchKernel(r.v.fn, dim3(grid), dim3(r.v.block), args, r.dynLds, s);
   return hipGetLastError();
 }
 
-hipError_t launchRegen(const RenderParams& p, int integrator, int grid, hipStream_t s, bool cull, const RegenShape& r) {
-  if (r.fullTree && p.scene.f4nTop * W4_LDS_F4 * sizeof(float4) > r.dynLds) return hipErrorInvalidValue;
-  switch (integrator) {
-    case 0: return launchRegenI<0>(p, grid, s, cull, r);
-    case 1: return launchRegenI<1>(p, grid, s, cull, r);
-    default: return launchRegenI<2>(p, grid, s, cull, r);
-  }
-}
-
-bool regenTakesLists(int integrator, const RegenShape& r) {
-  return regenLists(integrator, r.wide ? (r.small ? PT_WIDE_REGEN_WAVES_SMALL : wideRegenWaves(integrator)) : 0);
-}
+// (the integrator stays in these two signatures, which the library exports; the shape's descriptor answers)
+bool regenTakesLists(int, const RegenShape& r) { return r.v.lists; }
 int regenLdsStack() { return REGEN_LDS_STACK; }
-int regenTop4(const RegenShape& r, int integrator) {
-  return regenTop4W(r.small ? PT_WIDE_REGEN_WAVES_SMALL : wideRegenWaves(integrator));
-}
+int regenTop4(const RegenShape& r, int) { return r.v.top4; }
 
 }  // namespace pt

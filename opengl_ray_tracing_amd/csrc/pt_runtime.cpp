@@ -149,11 +149,10 @@ static int createOne(pt_ctx** out, const pt_config* cfg) {
   }
   CKC(hipMalloc(&ctx->d_ctl, CTL_BYTES));
   CKC(hipMemset(ctx->d_ctl, 0, CTL_BYTES));
-  ctx->shardsX = (cfg->width + ss - 1) / ss;
-  ctx->shardsY = (cfg->height + ss - 1) / ss;
-  const int numShards = ctx->shardsX * ctx->shardsY;
-  const int owned = (numShards - cfg->tile_rank + cfg->tile_world - 1) / cfg->tile_world;
-  ctx->numItems = owned * (ss / 8) * (ss / 8);
+  const Share share = shareOf(ctx, cfg->tile_rank, cfg->tile_world);
+  ctx->shardsX = share.shardsX;
+  ctx->shardsY = shardsY(share);
+  ctx->numItems = waveTiles(share);
   ctx->perQueue = (ctx->numItems + NUM_QUEUES - 1) / NUM_QUEUES;
   // the path-regeneration kernel with the 4-wide walk for every integrator on any scene
   // (PT_REGEN_WIDE = 1; 0: never; unset: Lambert frames and large Disney/MIS scenes)
@@ -1418,7 +1417,7 @@ static int gridFor(pt_ctx* ctx, const FramePlan& pl, const FrameSlot& at, Launch
     CK(renderBlocksPerCU(c.integrator, pl.cull, pl.count, pl.wide, &nb));
   }
   if (nb < 1) nb = 1;
-  g->bs = pl.regen ? g->rs.block : BLOCK;
+  g->bs = pl.regen ? g->rs.v.block : BLOCK;
   ctx->lastWaves = nb * g->bs / 64 / 4;  // 4 SIMDs per CU
   ctx->lastRegen = pl.regen;
   // Frames in flight share the GPU by space, not by time: a frame's persistent grid is
@@ -1473,8 +1472,10 @@ static RenderParams fillParams(const pt_ctx* ctx, const FramePlan& pl, const Fra
   p.env.h = ctx->hdrH;
   p.env.res = ctx->hdrW;
   p.env.nt = pl.envNt;
-  p.width = c.width;
-  p.height = c.height;
+  // the share's six fields, the rank's wave tiles (== ctx->numItems) and colStride: per-frame buffers are indexed
+  // by the pixel's slot in this context's share (pt_frame.h slotOf), so a 1/N share's colour and camera-ray
+  // buffers are 1/N of a frame (c5 at N = 8, 16 frames per launch: ~2.4 GB of colour buffers instead of ~19 GB)
+  setShare(p, shareOf(ctx, c.tile_rank, c.tile_world));
   p.frameCounter = frameCounter;
   p.sampleIndex = sampleIndex(c, frameCounter);
   p.sampleStride = c.sample_world > 0 ? (uint32_t)c.sample_world : 1u;
@@ -1484,20 +1485,10 @@ static RenderParams fillParams(const pt_ctx* ctx, const FramePlan& pl, const Fra
   p.accum = ctx->d_accum;
   p.queue = reinterpret_cast<int*>(ctx->d_ctl + CTL_QUEUES) + (size_t)at.slot * NUM_QUEUES * CTL_LINE_INTS;
   p.perQueue = ctx->perQueue;
-  p.numItems = ctx->numItems;
-  p.shardSize = ctx->shardSize;
-  p.shardTiles = (ctx->shardSize / 8) * (ctx->shardSize / 8);
-  p.shardsX = ctx->shardsX;
-  p.rank = c.tile_rank;
-  p.world = c.tile_world;
   p.ovf = ovfDepth ? ctx->d_ovf + (size_t)at.slot * g.fullGrid * g.bs * ovfDepth : nullptr;
   p.ovfDepth = ovfDepth;
   p.stats = reinterpret_cast<unsigned long long*>(ctx->d_ctl + CTL_STATS);
   p.rayShards = reinterpret_cast<unsigned long long*>(ctx->d_ctl + CTL_RAYS);
-  // per-frame buffers indexed by the pixel's slot in this context's share (shareIndex): a 1/N share's
-  // colour and camera-ray buffers are 1/N of a frame (c5 at N = 8, 16 frames per launch: ~2.4 GB of
-  // colour buffers instead of ~19 GB)
-  p.colStride = (size_t)ctx->numItems * 64;
   return p;
 }
 
@@ -1962,17 +1953,15 @@ int pt_tonemap(pt_ctx* ctx, float limit, float gamma, float* rgb_out) {
   return PT_OK;
 }
 
+// rank's share of a world-way screen-tile split of the context's image (the one place a Share is filled)
+extern "C++" Share shareOf(const pt_ctx* ctx, int rank, int world) {
+  return makeShare(ctx->cfg.width, ctx->cfg.height, ctx->shardSize, rank, world);
+}
+
 extern "C++" PackParams packParams(const pt_ctx* ctx, int rank, int world) {
   PackParams p;
-  p.width = ctx->cfg.width;
-  p.height = ctx->cfg.height;
-  p.shardSize = ctx->shardSize;
-  p.shardsX = ctx->shardsX;
-  p.rank = rank;
-  p.world = world;
-  const int numShards = ctx->shardsX * ctx->shardsY;
-  const long owned = (numShards - rank + world - 1) / world;
-  p.count = owned * (long)ctx->shardSize * ctx->shardSize;
+  p.share = shareOf(ctx, rank, world);
+  p.count = slots(p.share);
   return p;
 }
 

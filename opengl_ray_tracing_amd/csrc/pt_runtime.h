@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "pt_abi.h"
+#include "pt_frame.h"
 #include "pt_kernels.h"
 #include "pt_rccl.h"
 
@@ -281,6 +282,7 @@ static void dfree(T*& p) {
 int joinGather(pt_ctx* ctx);  // the device group's gather of the last frame has landed in the accumulation
 int joinPipe(pt_ctx* ctx);    // the caller's stream waits for the last pipelined frame's running-mean update
 SceneView sceneView(const pt_ctx* ctx);
+Share shareOf(const pt_ctx* ctx, int rank, int world);
 PackParams packParams(const pt_ctx* ctx, int rank, int world);
 void dropHistory(pt_ctx* ctx);  // the temporal history shows another scene or another light after an upload
 #pragma GCC visibility pop

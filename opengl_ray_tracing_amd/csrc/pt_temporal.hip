@@ -38,7 +38,7 @@ __global__ __launch_bounds__(TEMPORAL_TILE* TEMPORAL_TILE) void temporalKernel(T
     if (__float_as_int(nrmP.w) >= 0) {
       const float4 posP = p.posT[i];
       const V3 Pp = v3(posP.x, posP.y, posP.z), Np = v3(nrmP.x, nrmP.y, nrmP.z);
-      // the centre's position in the history camera: the inverse of startPath's ray
+      // the centre's position in the history camera: the inverse of the camera ray (pt_frame.h cameraDir)
       const V3 v = Pp - v3(p.eye[0], p.eye[1], p.eye[2]);
       const float a = dot(v3(p.c0[0], p.c0[1], p.c0[2]), v);
       const float b = dot(v3(p.c1[0], p.c1[1], p.c1[2]), v);

@@ -989,16 +989,6 @@ struct TileCursor {
   }
 };
 
-// Slot of pixel (px, py) in this context's screen-tile share, in the packed order of pt_pack_owned
-// (pt_kernels.hip packedPixel): the index of a pipelined frame's colour and camera-ray buffers
-// (RenderParams::colStride slots per frame). (px, py) must be one of the share's pixels.
-__device__ __forceinline__ size_t shareIndex(const RenderParams& p, int px, int py) {
-  const int ss = p.shardSize;
-  const int gx = px / ss, gy = py / ss;
-  const int j = (gy * p.shardsX + gx) / p.world;  // the share's j-th shard tile
-  return (size_t)j * ss * ss + (size_t)((py - gy * ss) * ss + (px - gx * ss));
-}
-
 // The camera-ray pass's compacted results (RenderParams::primMask / primHit) of wave tile w of frame fr:
 // the tile's mask, its entries, and slot k's result (PRIM_MISS for a slot outside the mask)
 __device__ __forceinline__ unsigned long long primTileMask(const RenderParams& p, int fr, int w) {

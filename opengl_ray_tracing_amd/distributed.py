@@ -7,7 +7,7 @@ the per-pixel path:
   Every pixel's value depends only on (pixel, frameCounter) and its own running
   mean (pass1.fsh:73-76, :118-122, :868-871), so the reassembled frame is
   bit-identical to a single-GPU render. The packed order (tile, row, column)
-  matches the kernels in csrc/pt_kernels.hip (packKernel / unpackKernel).
+  matches csrc/pt_frame.h pixelOfSlot (csrc/pt_display.hip packKernel / unpackKernel).
 * sample streams (weak scaling): every rank renders the whole frame from its
   own interleaved sample stream (pt_config.sample_rank / sample_world: rank r
   draws samples r, r+W, r+2W, ...), with no collective per frame; the image is

@@ -47,7 +47,7 @@ def expf(x: np.ndarray) -> np.ndarray:
 
 
 def camera_rays(w: int, h: int, eye, rot) -> np.ndarray:
-    """startPath's camera ray (pt_regen.hip) through each pixel centre: the jitter terms are 0.
+    """The frame kernels' camera ray (pt_frame.h cameraDir) through each pixel centre: the jitter terms are 0.
     -> (h * w, 6) origin, direction; pixel (px, py) at row py * w + px."""
     M = np.ascontiguousarray(rot, F).reshape(16)
     px = np.tile(np.arange(w, dtype=np.int64), h)

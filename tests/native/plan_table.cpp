@@ -18,11 +18,10 @@ static pt_ctx make(int integrator, int maxBounce = -1, unsigned flags = 0, int t
   c.max_bounce = maxBounce;
   c.flags = flags;
   c.tile_world = tileWorld;
-  const int ss = x.shardSize;
-  x.shardsX = (c.width + ss - 1) / ss;
-  x.shardsY = (c.height + ss - 1) / ss;
-  const int owned = (x.shardsX * x.shardsY - c.tile_rank + c.tile_world - 1) / c.tile_world;
-  x.numItems = owned * (ss / 8) * (ss / 8);
+  const Share share = makeShare(c.width, c.height, x.shardSize, c.tile_rank, c.tile_world);
+  x.shardsX = share.shardsX;
+  x.shardsY = shardsY(share);
+  x.numItems = waveTiles(share);
   x.perQueue = (x.numItems + NUM_QUEUES - 1) / NUM_QUEUES;
   x.pipe = pipelines(c);
   x.regenWide = -1;

@@ -2,7 +2,7 @@
 
 binRect below restates binRectKernel (pt_primary.hip) in numpy float64. For
 seeded camera rays of several frames and cameras -- generated with the
-reference's ray generation (IS:846-850, float32, as pt_kernels.hip cameraRay)
+reference's ray generation (IS:846-850, float32, as pt_frame.h cameraRay)
 -- the CPU oracle's brute-force closest hit (hitArray over every triangle,
 IS:853-854) must lie in the bin of the ray's 8x8 tile: the rectangle binRect
 gives that triangle must contain the tile. (The GPU test
@@ -58,7 +58,7 @@ def wang(s):
 
 
 def camera_rays(px, py, frame, eye, cam, w, h):
-    """cameraRay (pt_kernels.hip) / IS:73-89, 846-850 in float32."""
+    """cameraRay (pt_frame.h) / IS:73-89, 846-850 in float32."""
     f32 = np.float32
     with np.errstate(over="ignore"):
         seed = (px.astype(np.uint32) * np.uint32(1973) + py.astype(np.uint32) * np.uint32(9277)

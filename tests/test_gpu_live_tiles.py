@@ -1,4 +1,4 @@
-"""The regen kernels' live-item lists (pt_kernels.hip liveListKernel, pt_trace.h TileCursor::nextLive):
+"""The regen kernels' live-item lists (pt_primary.hip liveListKernel, pt_trace.h TileCursor::nextLive):
 after the camera-ray pass each work queue hands out only the tiles the pass left paths in. The
 shapes are the smallest at which a list can go wrong -- no live tile at all, one live tile near the
 end of the queues, fewer tiles than queues, tiles live in some frames of a batch only, screen-tile

@@ -1,6 +1,6 @@
 """float32 numpy restatement of the per-pixel sample moments and the variance-guided a-trous
 filter (include/pt_abi.h PT_FLAG_MOMENTS / pt_denoise_var) -- TEST INFRASTRUCTURE, and the
-specification: csrc/pt_moments.hip and csrc/pt_variance.hip mirror every operation below in the
+specification: csrc/pt_display.hip (mixFrames) and csrc/pt_variance.hip mirror every operation below in the
 same order, so the GPU output equals this file's bit for bit (no fused multiply-adds, + - * / sqrt
 correctly rounded, the one transcendental include/pt_fmath.h ptm_expf through denoise_ref.expf).
 
