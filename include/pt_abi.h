@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 11 /* 2: in-process multi-GPU fields at the end of pt_config / pt_frame_stats;
+#define PT_ABI_VERSION 12 /* 2: in-process multi-GPU fields at the end of pt_config / pt_frame_stats;
                              3: scene-upload fields at the end of pt_frame_stats, pt_build_bvh_device;
                              4: BASIC shapes as doubles, its double image, the replayed random stream;
                              5: the displayed frame of a screen-tile split (pt_display_*);
@@ -42,7 +42,10 @@ extern "C" {
                              10: per-pixel sample moments (PT_FLAG_MOMENTS, pt_download_moments) and the
                                 variance-guided filter (pt_denoise_var); no existing struct changes;
                              11: diagnostics only: pt_fmath_* ids 7-10 (the float approximations and
-                                ptm_sincosf) and pt_sph_texel_device; no existing struct changes */
+                                ptm_sincosf) and pt_sph_texel_device; no existing struct changes;
+                             12: adaptive sampling: converged 8x8 tiles retire from the sample moments
+                                (PT_FLAG_ADAPTIVE, pt_adaptive_update, pt_adaptive_status,
+                                pt_download_tile_error); no existing struct changes */
 
 /* error codes */
 #define PT_OK 0
@@ -84,6 +87,10 @@ extern "C" {
                                      the running mean (pt_download_moments, pt_denoise_var); not with
                                      PT_BASIC_CPU_COMPAT, PT_FLAG_COUNT_FETCHES, PT_FLAG_SERIAL_FRAMES,
                                      tile_world > 1 or n_devices > 1 (pt_create: PT_E_INVALID) */
+#define PT_FLAG_ADAPTIVE 0x2000u  /* 8x8 tiles whose pixels have converged stop taking samples (pt_adaptive_update);
+                                     needs PT_FLAG_MOMENTS, with every restriction of that flag, and not with
+                                     PT_FLAG_NO_BINS (pt_create: PT_E_INVALID). Every frame runs the camera-ray
+                                     pass of PT_FLAG_PRIMARY_PASS */
 
 /* in-process multi-GPU (pt_config.n_devices > 1) */
 #define PT_MAX_DEVICES 8
@@ -491,6 +498,74 @@ int pt_denoise_var(pt_ctx* ctx, const pt_denoise_var_params* prm, const void* d_
 /* Test hook: step A's plane of the last pt_denoise_var, width*height f32 into host or device memory;
  * synchronous. PT_E_INVALID before one. */
 int pt_download_variance(pt_ctx* ctx, float* v);
+
+/* Adaptive sampling. Every frame above spends one sample on every pixel for as long as the caller keeps
+ * rendering. A PT_FLAG_ADAPTIVE context (a PT_FLAG_MOMENTS context, too) can stop: pt_adaptive_update
+ * looks at every 8x8 tile of the image -- tile (tx, ty) is entry ty * tilesX + tx, tilesX = (width + 7) / 8,
+ * row 0 at the bottom like the accumulation -- and retires those whose pixels have all converged. A
+ * retired tile costs nothing from then on: the camera-ray pass writes it an empty mask, so no frame
+ * kernel claims it, no ray of it is traced or counted, and the running-mean update leaves its pixels
+ * alone. Retirement is permanent until the running mean restarts, which keeps everything exact: an
+ * active pixel has taken every frame so far, so its weight 1 / (frameCounter + f + 1) is still the right
+ * one and its accumulation and moments are bit for bit a PT_FLAG_MOMENTS context's; a retired pixel
+ * keeps, bit for bit, the accumulation and moments it had at the update that retired its tile.
+ *
+ * The decision, with kf = (float)pt_moments_frames, thr2 = threshold * threshold, for every tile T that
+ * is not retired, over its pixels inside the image, each operation one IEEE f32 operation
+ * (tests/adaptive_ref.py restates it; the GPU equals it bit for bit):
+ *   L = (0.3 r + 0.6 g) + 0.1 b of the accumulation;  q = 1 + L / limit;  gd = 1 / (q q)
+ *   d = m2 - m1 m1;  d = d > 0 ? d : 0;  v = (d / kf) (gd gd)       (pt_denoise_var's step A with n_p = kf,
+ *                                                                    without guides: sky pixels count too)
+ *   err2[T] = the largest v (e = v > e ? v : e from 0: a NaN never wins)
+ *   frames >= min_frames and err2[T] <= thr2:  retired_at[T] = frames
+ * A tile retired earlier keeps its err2 and retired_at. Both planes are zero at creation and are
+ * cleared, with every tile active again, by a launch with frameCounter == 0 and by everything that
+ * invalidates the moments (pt_upload_accum, pt_clear_accum, pt_upload_scene, pt_upload_env). A gap in
+ * frameCounter (moments not valid) leaves the retired tiles retired until such a restart; updates fail
+ * meanwhile.
+ *
+ * The display() loop:
+ *   pt_render_frame_async(ctx, eye, rot, frameCounter);
+ *   if (frameCounter % N == N - 1) {
+ *     pt_adaptive_update(ctx, &prm);
+ *     pt_adaptive_status(ctx, &st);
+ *     if (st.retired == st.tiles) stop;       (the picture is done)
+ *   }
+ *   frameCounter++;
+ * Not part of this: screen-tile shares and device groups (excluded with PT_FLAG_MOMENTS), decisions
+ * finer than a tile, un-retiring, and retirement carried across camera moves. */
+typedef struct pt_adaptive_params {
+  float threshold;   /* a pixel has converged when the standard error of the mean of its tone-mapped
+                        luminance is <= threshold; > 0 and finite */
+  float limit;       /* the tonemap limit of that luminance (pass3: 1.5); > 0 */
+  int   min_frames;  /* no tile retires before the moments hold this many frames; >= 2 */
+} pt_adaptive_params;
+#define PT_ADAPTIVE_PARAMS_SIZE 12 /* sizeof(pt_adaptive_params), asserted by the library */
+
+void pt_adaptive_defaults(pt_adaptive_params* prm);  /* 1 / 255.f, 1.5, 16 */
+int pt_adaptive_params_size(void);                   /* sizeof(pt_adaptive_params) of the loaded library */
+
+typedef struct pt_adaptive_state {
+  int tiles;            /* 8x8 tiles of the image: tilesX * tilesY */
+  int retired;          /* of them retired */
+  uint32_t frames;      /* pt_moments_frames at the last update (0: none since the restart) */
+  float max_err2;       /* the largest err2 over the tiles still active (0 when none is) */
+} pt_adaptive_state;
+#define PT_ADAPTIVE_STATE_SIZE 16 /* sizeof(pt_adaptive_state), asserted by the library */
+int pt_adaptive_state_size(void);                    /* sizeof(pt_adaptive_state) of the loaded library */
+
+/* One decision over every active tile. prm NULL = pt_adaptive_defaults. PT_E_INVALID without
+ * PT_FLAG_ADAPTIVE, with bad parameters, while pt_moments_frames is 0, and when the context's launches
+ * cannot run the camera-ray pass (no runtime tree for the camera-ray bins: nothing could retire).
+ * Asynchronous, on the context's stream, after the frames rendered so far; frames rendered after it see
+ * its result, every frame of one launch the same one. */
+int pt_adaptive_update(pt_ctx* ctx, const pt_adaptive_params* prm);
+/* Synchronous. PT_E_INVALID without PT_FLAG_ADAPTIVE. */
+int pt_adaptive_status(pt_ctx* ctx, pt_adaptive_state* st);
+/* The tile planes, `tiles` entries each, either may be NULL, host or device memory: err2 as the last
+ * update that looked at the tile left it, retired_at the frame count at which the tile retired (0:
+ * active). Synchronous. PT_E_INVALID without PT_FLAG_ADAPTIVE. */
+int pt_download_tile_error(pt_ctx* ctx, float* err2, uint32_t* retired_at);
 
 /* Stream interop: render on the caller's HIP stream (e.g. torch's current
  * stream). NULL restores the context's own stream. */

@@ -13,11 +13,11 @@ from . import _build
 
 _lib = None
 
-ABI_VERSION = 11  # include/pt_abi.h PT_ABI_VERSION
+ABI_VERSION = 12  # include/pt_abi.h PT_ABI_VERSION
 # an older tuning build (tools/tune.py A/B against a previous round's library) loads when its structs
 # match: ABI 7 only added pt_unpack_ranks, ABI 8 the guide buffers and the denoiser, ABI 9 the
-# temporal resolve, ABI 10 the sample moments and the variance-guided filter and ABI 11 the
-# diagnostics of the sky texel decision, which such a build does not have
+# temporal resolve, ABI 10 the sample moments and the variance-guided filter, ABI 11 the
+# diagnostics of the sky texel decision and ABI 12 adaptive sampling, which such a build does not have
 ABI_STRUCTS_SINCE = 6
 c_float_p = C.POINTER(C.c_float)
 c_double_p = C.POINTER(C.c_double)
@@ -67,6 +67,16 @@ class PtDenoiseVarParams(C.Structure):
         ("passes", C.c_int), ("sigma_l", C.c_float), ("sigma_z", C.c_float), ("sigma_a", C.c_float),
         ("normal_log2", C.c_int), ("limit", C.c_float), ("min_temporal", C.c_int),
     ]
+
+
+class PtAdaptiveParams(C.Structure):
+    """pt_adaptive_params (include/pt_abi.h): PT_ADAPTIVE_PARAMS_SIZE bytes."""
+    _fields_ = [("threshold", C.c_float), ("limit", C.c_float), ("min_frames", C.c_int)]
+
+
+class PtAdaptiveState(C.Structure):
+    """pt_adaptive_state (include/pt_abi.h): PT_ADAPTIVE_STATE_SIZE bytes."""
+    _fields_ = [("tiles", C.c_int), ("retired", C.c_int), ("frames", C.c_uint32), ("max_err2", C.c_float)]
 
 
 class PtMaterial(C.Structure):
@@ -137,6 +147,12 @@ SIGNATURES = {
     "pt_denoise_var_params_size": (C.c_int, []),
     "pt_denoise_var": (C.c_int, [C.c_void_p, C.POINTER(PtDenoiseVarParams), C.c_void_p, C.c_void_p]),
     "pt_download_variance": (C.c_int, [C.c_void_p, c_float_p]),
+    "pt_adaptive_defaults": (None, [C.POINTER(PtAdaptiveParams)]),
+    "pt_adaptive_params_size": (C.c_int, []),
+    "pt_adaptive_state_size": (C.c_int, []),
+    "pt_adaptive_update": (C.c_int, [C.c_void_p, C.POINTER(PtAdaptiveParams)]),
+    "pt_adaptive_status": (C.c_int, [C.c_void_p, C.POINTER(PtAdaptiveState)]),
+    "pt_download_tile_error": (C.c_int, [C.c_void_p, c_float_p, C.POINTER(C.c_uint32)]),
     "pt_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pt_synchronize": (C.c_int, [C.c_void_p]),
     "pt_get_stats": (C.c_int, [C.c_void_p, C.POINTER(PtFrameStats)]),

@@ -159,13 +159,18 @@ hipError_t launchUnpackRanks(const RanksUnpack& d, int world, float4* accum, hip
 // tonemapPixel's luminance, one f32 operation each (no fused multiply-add).
 // Per pixel and launch: 32 B of accumulation and 16 B of moments (read + written once each, streaming
 // like the accumulation) and 12 B per frame of sample colour.
-template <bool MOMENTS>
+// ADAPTIVE (a PT_FLAG_ADAPTIVE context, pt_adaptive.hip): a pixel whose 8x8 tile has retired
+// (retiredAt[ty * tilesX + tx] != 0) keeps its accumulation and moments -- the camera-ray pass stored it
+// no sample -- and returns before its loads; every other pixel is a MOMENTS pixel.
+template <bool MOMENTS, bool ADAPTIVE = false>
 __device__ __forceinline__ void mixFrames(const PackParams& p, float4* accum, float2* moments, const float* col,
-                                          size_t colStride, int nFrames, uint32_t frameCounter) {
+                                          size_t colStride, int nFrames, uint32_t frameCounter,
+                                          const uint32_t* retiredAt = nullptr) {
   long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= p.count) return;
   int px, py;
   if (!pixelOfSlot(p.share, k, px, py)) return;
+  if (ADAPTIVE && retiredAt[(size_t)(py >> 3) * ((p.share.width + 7) >> 3) + (px >> 3)] != 0u) return;
   const size_t i = (size_t)py * p.share.width + px;
   float4 a = ldStream(accum + i);
   float2 m = make_float2(0.0f, 0.0f);
@@ -190,6 +195,10 @@ __global__ void mixMomentsKernel(PackParams p, float4* accum, float2* moments, c
                                  int nFrames, uint32_t frameCounter) {
   mixFrames<true>(p, accum, moments, col, colStride, nFrames, frameCounter);
 }
+__global__ void mixAdaptiveKernel(PackParams p, float4* accum, float2* moments, const float* col, size_t colStride,
+                                  int nFrames, uint32_t frameCounter, const uint32_t* retiredAt) {
+  mixFrames<true, true>(p, accum, moments, col, colStride, nFrames, frameCounter, retiredAt);
+}
 hipError_t launchMix(const PackParams& p, float4* accum, const float* col, size_t colStride, int nFrames,
                      uint32_t frameCounter, hipStream_t s) {
   if (p.count <= 0 || nFrames <= 0) return hipSuccess;
@@ -202,6 +211,14 @@ hipError_t launchMixMoments(const PackParams& p, float4* accum, float2* moments,
   if (p.count <= 0 || nFrames <= 0) return hipSuccess;
   hipLaunchKernelGGL(mixMomentsKernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, moments, col,
                      colStride, nFrames, frameCounter);
+  return hipGetLastError();
+}
+hipError_t launchMixAdaptive(const PackParams& p, float4* accum, float2* moments, const float* col, size_t colStride,
+                             int nFrames, uint32_t frameCounter, const uint32_t* retiredAt, hipStream_t s) {
+  if (!retiredAt) return hipErrorInvalidValue;
+  if (p.count <= 0 || nFrames <= 0) return hipSuccess;
+  hipLaunchKernelGGL(mixAdaptiveKernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, moments,
+                     col, colStride, nFrames, frameCounter, retiredAt);
   return hipGetLastError();
 }
 

@@ -287,6 +287,10 @@ struct RenderParams {
   int* tileCost;        // per tile: summed cost of its items this frame (shader cycles), null = not recorded
   int* tileCostMax;     // per tile: its longest item this frame
   unsigned long long* waveTrace;  // PT_WAVE_TRACE builds only: WAVE_TRACE_WORDS u64 per wave (pt_runtime.cpp, tools/wave_trace.py)
+  // PT_FLAG_ADAPTIVE (pt_adaptive.hip): per 8x8 tile of the whole image (ty * tilesX + tx, tilesX =
+  // (width + 7) / 8) the frame count at which the tile retired, 0 = active; null without the flag. Only
+  // the camera-ray pass reads it: a retired tile gets mask 0, so no frame kernel touches it
+  const uint32_t* retiredAt;
 };
 
 struct TraceParams {
@@ -549,5 +553,27 @@ hipError_t launchMix(const PackParams& p, float4* accum, const float* col, size_
 // weights the running means (m1, m2) of each sample's luminance l and of l * l in `moments`
 hipError_t launchMixMoments(const PackParams& p, float4* accum, float2* moments, const float* col, size_t colStride,
                             int nFrames, uint32_t frameCounter, hipStream_t s);
+// launchMixMoments of a PT_FLAG_ADAPTIVE context (mixFrames' third case): a pixel whose 8x8 tile is
+// retired (retiredAt, RenderParams::retiredAt's plane) is left alone, before any of its loads
+hipError_t launchMixAdaptive(const PackParams& p, float4* accum, float2* moments, const float* col, size_t colStride,
+                             int nFrames, uint32_t frameCounter, const uint32_t* retiredAt, hipStream_t s);
+// Adaptive sampling's decision (pt_adaptive.hip tileErrorKernel, pt_abi.h pt_adaptive_update): one
+// wave per 8x8 tile of the whole image; a tile not yet retired takes err2 = the largest variance of
+// the mean of its pixels' tone-mapped luminance and retires (retiredAt = frames) when frames >=
+// minFrames and err2 <= thr2
+struct TileErrorParams {
+  int width, height;
+  int tilesX, tiles;
+  const float4* accum;
+  const float2* moments;
+  float* err2;
+  uint32_t* retiredAt;
+  float kf;                  // (float)frames
+  float limit;
+  float thr2;                // threshold * threshold
+  uint32_t frames;           // the frames the moments hold
+  int minFrames;
+};
+hipError_t launchTileError(const TileErrorParams& p, hipStream_t s);
 
 }  // namespace pt

@@ -182,8 +182,9 @@ static inline FramePlan planFrame(const pt_ctx* ctx, bool solo, int want) {
   // The camera-ray pass (primaryKernel) traces the camera rays ahead of the frame kernel: on
   // request, and by default for the large-scene regen kernel (c5 7.52 -> 6.86 ms), whose lanes
   // then start from the camera ray's hit; the megakernel is faster with its camera rays inside
-  // (c2 0.372 vs 0.383 ms with the pass)
-  f.pass = (c.flags & PT_FLAG_PRIMARY_PASS) || (f.regen && f.wide);
+  // (c2 0.372 vs 0.383 ms with the pass). Adaptive sampling retires tiles in the pass: every kernel
+  // of a PT_FLAG_ADAPTIVE context runs behind it
+  f.pass = (c.flags & (PT_FLAG_PRIMARY_PASS | PT_FLAG_ADAPTIVE)) || (f.regen && f.wide);
   // camera-ray bins need the reference facts refReachable checks a bin's winner against
   f.bins = PT_BINS && !f.count && ctx->fastReady && !(c.flags & PT_FLAG_NO_BINS) && (!f.regen || f.pass);
   return f;

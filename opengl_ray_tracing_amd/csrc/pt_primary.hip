@@ -249,9 +249,19 @@ __global__ __launch_bounds__(64) void primaryKernel(RenderParams p) {
   const bool valid = px < p.width && py < p.height;
   const int tx = o.x >> 3, ty = o.y >> 3;
   int b0 = 0, b1 = 0;  // a tile wholly outside the image has no bin (and no valid lane)
+  // PT_FLAG_ADAPTIVE: the frame count at which the tile retired (pt_adaptive.hip; the bins' tiles are the
+  // image's: ty * tilesX + tx), read beside the bin's bounds -- three scalar loads in one round trip
+  uint32_t gone = 0u;
   if (tx < p.binTilesX && ty < p.binTilesY) {
     b0 = p.binStart[ty * p.binTilesX + tx];
     b1 = p.binStart[ty * p.binTilesX + tx + 1];
+    if (p.retiredAt) gone = p.retiredAt[ty * p.binTilesX + tx];
+  }
+  // a retired tile takes no sample: an empty mask, so no frame kernel claims it, no sky colour stored,
+  // no ray counted
+  if (gone != 0u) {
+    if (lane == 0) p.primMask[(size_t)fr * p.numItems + w] = 0ull;
+    return;
   }
   const int n = b1 - b0;
   // the tile's results compacted (RenderParams::primMask): the slots that need a path, in slot order

@@ -147,6 +147,15 @@ static int createOne(pt_ctx** out, const pt_config* cfg) {
     CKC(hipMalloc(&ctx->d_mom, npix * sizeof(float2)));
     CKC(hipMemset(ctx->d_mom, 0, npix * sizeof(float2)));
   }
+  if (cfg->flags & PT_FLAG_ADAPTIVE) {
+    ctx->adaptTilesX = (cfg->width + 7) / 8;
+    ctx->adaptTiles = ctx->adaptTilesX * ((cfg->height + 7) / 8);
+    CKC(hipMalloc(&ctx->d_err2, (size_t)ctx->adaptTiles * sizeof(float)));
+    CKC(hipMemset(ctx->d_err2, 0, (size_t)ctx->adaptTiles * sizeof(float)));
+    CKC(hipMalloc(&ctx->d_retiredAt, (size_t)ctx->adaptTiles * sizeof(uint32_t)));
+    CKC(hipMemset(ctx->d_retiredAt, 0, (size_t)ctx->adaptTiles * sizeof(uint32_t)));
+    CKC(hipEventCreateWithFlags(&ctx->adaptDone, hipEventDisableTiming));
+  }
   CKC(hipMalloc(&ctx->d_ctl, CTL_BYTES));
   CKC(hipMemset(ctx->d_ctl, 0, CTL_BYTES));
   const Share share = shareOf(ctx, cfg->tile_rank, cfg->tile_world);
@@ -210,6 +219,16 @@ int pt_create(pt_ctx** out, const pt_config* cfg) {
     else if (n > 1) why = "n_devices > 1";
     if (why) {
       g_create_err = std::string("pt_create: PT_FLAG_MOMENTS cannot be combined with ") + why;
+      return PT_E_INVALID;
+    }
+  }
+  if (cfg->flags & PT_FLAG_ADAPTIVE) {
+    // tiles retire from the moments, in the camera-ray pass, which needs the camera-ray bins
+    const char* why = nullptr;
+    if (!(cfg->flags & PT_FLAG_MOMENTS)) why = "needs PT_FLAG_MOMENTS";
+    else if (cfg->flags & PT_FLAG_NO_BINS) why = "cannot be combined with PT_FLAG_NO_BINS";
+    if (why) {
+      g_create_err = std::string("pt_create: PT_FLAG_ADAPTIVE ") + why;
       return PT_E_INVALID;
     }
   }
@@ -280,6 +299,8 @@ void pt_destroy(pt_ctx* ctx) {
     if (ctx->mixDone[k]) (void)hipEventDestroy(ctx->mixDone[k]);
   }
   if (ctx->binsBuilt) (void)hipEventDestroy(ctx->binsBuilt);
+  dfree(ctx->d_err2); dfree(ctx->d_retiredAt);
+  if (ctx->adaptDone) (void)hipEventDestroy(ctx->adaptDone);
   for (hipEvent_t e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->own) (void)hipStreamDestroy(ctx->own);
@@ -715,13 +736,43 @@ extern "C++" void dropHistory(pt_ctx* ctx) {
 
 // the sample moments no longer describe the accumulation (it was replaced, or the scene or the
 // light its samples saw): invalid until a launch restarts them at frameCounter 0
-static void dropMoments(pt_ctx* ctx) { ctx->momFrames = 0; }
+// ... and with them goes what adaptive sampling decided from them
+static int clearAdaptive(pt_ctx* ctx);
+static int dropMoments(pt_ctx* ctx) {
+  ctx->momFrames = 0;
+  return clearAdaptive(ctx);
+}
+
+// the caller's stream waits for the last update or clear of the tile planes when that ran on another
+// stream (pt_set_stream since)
+static int joinAdaptive(pt_ctx* ctx) {
+  if (ctx->adaptStream && ctx->adaptStream != ctx->stream) CK(hipStreamWaitEvent(ctx->stream, ctx->adaptDone, 0));
+  return PT_OK;
+}
+
+// Every tile of a PT_FLAG_ADAPTIVE context active again, its error 0: on the caller's stream, after the
+// running-mean updates of the launches so far (and so after their camera-ray passes), with adaptDone
+// for the next pass of each slot. Nothing to clear (no update since the last clear) enqueues nothing.
+static int clearAdaptive(pt_ctx* ctx) {
+  ctx->adaptFrames = 0;
+  if (!ctx->d_retiredAt || !ctx->adaptDirty) return PT_OK;
+  if (int rc = joinPipe(ctx)) return rc;
+  if (int rc = joinAdaptive(ctx)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  CK(hipMemsetAsync(ctx->d_retiredAt, 0, (size_t)ctx->adaptTiles * sizeof(uint32_t), ctx->stream));
+  CK(hipMemsetAsync(ctx->d_err2, 0, (size_t)ctx->adaptTiles * sizeof(float), ctx->stream));
+  CK(hipEventRecord(ctx->adaptDone, ctx->stream));
+  ctx->adaptStream = ctx->stream;
+  ctx->adaptGen++;
+  ctx->adaptDirty = false;
+  return PT_OK;
+}
 
 static int uploadScene(pt_ctx* ctx, const float* tris, const SceneHost& h) {
   if (int rc = syncStreams(ctx)) return rc;  // no frame in flight reads the buffers replaced here
   ctx->policyKey++;  // the tree / split policies are measured again at the next restart
   dropHistory(ctx);
-  dropMoments(ctx);
+  if (int rc = dropMoments(ctx)) return rc;
   CK(hipSetDevice(ctx->cfg.device_id));
   int rc;
   if ((rc = upload(ctx, &ctx->d_pairs, h.pairs)) || (rc = upload(ctx, &ctx->d_geo, h.geo)) ||
@@ -1038,7 +1089,7 @@ static int envOne(pt_ctx* ctx, const float* hdr, int w, int h, const float* cach
 int pt_upload_env(pt_ctx* ctx, const float* hdr, int w, int h, const float* cache) {
   if (!ctx) return PT_E_INVALID;
   dropHistory(ctx);
-  dropMoments(ctx);
+  if (int rc = dropMoments(ctx)) return rc;
   if (ctx->peers.empty()) return envOne(ctx, hdr, w, h, cache);
   // a device group computes calculateHdrCache once (on rank 0's GPU) and uploads it everywhere
   std::vector<float> own;
@@ -1643,8 +1694,16 @@ static int enqueueMix(pt_ctx* ctx, const FrameSlot& at, int nF, bool direct, uin
     CK(hipStreamWaitEvent(ctx->stream, ctx->mixDone[ctx->lastCol], 0));
   ctx->lastMixStream = ctx->stream;
   if (ctx->d_mom) {
-    CK(launchMixMoments(packParams(ctx, c.tile_rank, c.tile_world), ctx->d_accum, ctx->d_mom, ctx->d_col[colIdx],
-                        shareN, nF, frameCounter, ctx->stream));
+    if (ctx->d_retiredAt) {
+      // the retired tiles' pixels left alone: the state this launch's camera-ray pass saw (an update or
+      // a clear since then would be enqueued after this, on this stream -- or on the one the caller left)
+      if (int rc = joinAdaptive(ctx)) return rc;
+      CK(launchMixAdaptive(packParams(ctx, c.tile_rank, c.tile_world), ctx->d_accum, ctx->d_mom, ctx->d_col[colIdx],
+                           shareN, nF, frameCounter, ctx->d_retiredAt, ctx->stream));
+    } else {
+      CK(launchMixMoments(packParams(ctx, c.tile_rank, c.tile_world), ctx->d_accum, ctx->d_mom, ctx->d_col[colIdx],
+                          shareN, nF, frameCounter, ctx->stream));
+    }
     // the frames the moments hold: a restart, a continuation, or a gap (not valid)
     ctx->momFrames = frameCounter == 0 ? (uint32_t)nF : (frameCounter == ctx->momFrames ? ctx->momFrames + (uint32_t)nF : 0u);
   } else if (!direct)
@@ -1730,6 +1789,16 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
       return rc;
   }
   p.col = piped && !direct ? ctx->d_col[at.colIdx] : nullptr;
+  if (ctx->d_retiredAt) {
+    // a restart has every tile active again; the launch's pass runs after the last update or clear
+    if (frameCounter == 0)
+      if (int rc = clearAdaptive(ctx)) return rc;
+    if (ctx->adaptGenSeen[at.slot] != ctx->adaptGen) {
+      CK(hipStreamWaitEvent(S, ctx->adaptDone, 0));
+      ctx->adaptGenSeen[at.slot] = ctx->adaptGen;
+    }
+    p.retiredAt = ctx->d_retiredAt;
+  }
   if (pl.bins)
     if (int rc = bindBins(ctx, pl, at, g.rs, nF, eye, cameraRotate, &p)) return rc;
   // a frame in band order (probePolicy) records no costs and launches no reorder; the
@@ -1903,7 +1972,7 @@ int pt_upload_basic_image(pt_ctx* ctx, const double* rgb) {
 int pt_upload_accum(pt_ctx* ctx, const float* accum) {
   if (!ctx || !accum) return PT_E_INVALID;
   if (int rc = joinGather(ctx)) return rc;
-  dropMoments(ctx);
+  if (int rc = dropMoments(ctx)) return rc;
   for (pt_ctx* m : members(ctx))
     if (int rc = uploadAccumOne(m, accum)) return fromPeer(ctx, m, rc);
   return PT_OK;
@@ -1920,7 +1989,7 @@ int pt_clear_accum(pt_ctx* ctx) {
     if (m->d_basicImg &&
         hipMemsetAsync(m->d_basicImg, 0, (size_t)m->cfg.width * m->cfg.height * 3 * sizeof(double), m->stream) != hipSuccess)
       return fail(ctx, PT_E_HIP, "pt_clear_accum (BASIC image)");
-    dropMoments(m);
+    if (int rc = dropMoments(m)) return fromPeer(ctx, m, rc);
     if (m->d_mom &&
         hipMemsetAsync(m->d_mom, 0, (size_t)m->cfg.width * m->cfg.height * sizeof(float2), m->stream) != hipSuccess)
       return fail(ctx, PT_E_HIP, "pt_clear_accum (moments)");
@@ -1931,6 +2000,106 @@ int pt_clear_accum(pt_ctx* ctx) {
     CK(hipSetDevice(ctx->cfg.device_id));
     CK(hipStreamSynchronize(ctx->stream));
   }
+  return PT_OK;
+}
+
+// ------------------------------------------------------------ adaptive sampling
+static_assert(sizeof(pt_adaptive_params) == PT_ADAPTIVE_PARAMS_SIZE, "pt_adaptive_params layout");
+static_assert(sizeof(pt_adaptive_state) == PT_ADAPTIVE_STATE_SIZE, "pt_adaptive_state layout");
+
+void pt_adaptive_defaults(pt_adaptive_params* prm) {
+  if (!prm) return;
+  prm->threshold = 1.0f / 255.0f;
+  prm->limit = 1.5f;
+  prm->min_frames = 16;
+}
+
+int pt_adaptive_params_size(void) { return (int)sizeof(pt_adaptive_params); }
+int pt_adaptive_state_size(void) { return (int)sizeof(pt_adaptive_state); }
+
+int pt_adaptive_update(pt_ctx* ctx, const pt_adaptive_params* prm) {
+  if (!ctx) return PT_E_INVALID;
+  if (!ctx->d_retiredAt) return fail(ctx, PT_E_INVALID, "pt_adaptive_update: not a PT_FLAG_ADAPTIVE context");
+  pt_adaptive_params P;
+  pt_adaptive_defaults(&P);
+  if (prm) P = *prm;
+  if (!(P.threshold > 0.0f) || !std::isfinite(P.threshold))
+    return fail(ctx, PT_E_INVALID, "pt_adaptive_update: threshold must be > 0 and finite");
+  if (!(P.limit > 0.0f)) return fail(ctx, PT_E_INVALID, "pt_adaptive_update: limit must be > 0");
+  if (P.min_frames < 2) return fail(ctx, PT_E_INVALID, "pt_adaptive_update: min_frames must be >= 2");
+  if (ctx->momFrames == 0)
+    return fail(ctx, PT_E_INVALID, "pt_adaptive_update: the moments are not valid (pt_moments_frames is 0: render from frameCounter 0)");
+  // tiles retire in the camera-ray pass: a context whose launches cannot run it retires nothing
+  if (!planFrame(ctx, false, 2).bins)
+    return fail(ctx, PT_E_INVALID, "pt_adaptive_update: this context's frames run no camera-ray pass (no camera-ray bins for its scene)");
+  // after every launch so far has updated the running mean -- and so after their passes read the planes
+  if (int rc = joinPipe(ctx)) return rc;
+  if (int rc = joinAdaptive(ctx)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  TileErrorParams t;
+  t.width = ctx->cfg.width;
+  t.height = ctx->cfg.height;
+  t.tilesX = ctx->adaptTilesX;
+  t.tiles = ctx->adaptTiles;
+  t.accum = ctx->d_accum;
+  t.moments = ctx->d_mom;
+  t.err2 = ctx->d_err2;
+  t.retiredAt = ctx->d_retiredAt;
+  t.kf = (float)ctx->momFrames;
+  t.limit = P.limit;
+  t.thr2 = P.threshold * P.threshold;
+  t.frames = ctx->momFrames;
+  t.minFrames = P.min_frames;
+  CK(launchTileError(t, ctx->stream));
+  CK(hipEventRecord(ctx->adaptDone, ctx->stream));
+  ctx->adaptStream = ctx->stream;
+  ctx->adaptGen++;
+  ctx->adaptDirty = true;
+  ctx->adaptFrames = ctx->momFrames;
+  return PT_OK;
+}
+
+// the two tile planes on the host, after the frames and updates so far
+static int adaptivePlanes(pt_ctx* ctx, std::vector<float>& err2, std::vector<uint32_t>& retiredAt) {
+  if (int rc = joinPipe(ctx)) return rc;
+  if (int rc = joinAdaptive(ctx)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  err2.resize(ctx->adaptTiles);
+  retiredAt.resize(ctx->adaptTiles);
+  CK(hipMemcpyAsync(err2.data(), ctx->d_err2, err2.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipMemcpyAsync(retiredAt.data(), ctx->d_retiredAt, retiredAt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipStreamSynchronize(ctx->stream));
+  return PT_OK;
+}
+
+int pt_adaptive_status(pt_ctx* ctx, pt_adaptive_state* st) {
+  if (!ctx) return PT_E_INVALID;
+  if (!st) return fail(ctx, PT_E_INVALID, "pt_adaptive_status: null status");
+  if (!ctx->d_retiredAt) return fail(ctx, PT_E_INVALID, "pt_adaptive_status: not a PT_FLAG_ADAPTIVE context");
+  std::vector<float> err2;
+  std::vector<uint32_t> retiredAt;
+  if (int rc = adaptivePlanes(ctx, err2, retiredAt)) return rc;
+  st->tiles = ctx->adaptTiles;
+  st->retired = 0;
+  st->frames = ctx->adaptFrames;
+  st->max_err2 = 0.0f;
+  for (int k = 0; k < ctx->adaptTiles; k++) {
+    if (retiredAt[k] != 0u) st->retired++;
+    else st->max_err2 = err2[k] > st->max_err2 ? err2[k] : st->max_err2;
+  }
+  return PT_OK;
+}
+
+int pt_download_tile_error(pt_ctx* ctx, float* err2, uint32_t* retired_at) {
+  if (!ctx) return PT_E_INVALID;
+  if (!ctx->d_retiredAt) return fail(ctx, PT_E_INVALID, "pt_download_tile_error: not a PT_FLAG_ADAPTIVE context");
+  if (int rc = joinPipe(ctx)) return rc;
+  if (int rc = joinAdaptive(ctx)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const size_t n = (size_t)ctx->adaptTiles;
+  if (err2) CK(hipMemcpyAsync(err2, ctx->d_err2, n * sizeof(float), hipMemcpyDefault, ctx->stream));  // host or device
+  if (retired_at) CK(hipMemcpyAsync(retired_at, ctx->d_retiredAt, n * sizeof(uint32_t), hipMemcpyDefault, ctx->stream));
+  CK(hipStreamSynchronize(ctx->stream));
   return PT_OK;
 }
 
@@ -2030,7 +2199,7 @@ int pt_unpack_ranks(pt_ctx* ctx, int world, const void* const* dpacked) {
     d.count[k] = packParams(ctx, k, world).count;
   }
   CK(launchUnpackRanks(d, world, ctx->d_accum, ctx->stream));
-  dropMoments(ctx);
+  if (int rc = dropMoments(ctx)) return rc;
   return PT_OK;
 }
 
@@ -2041,7 +2210,7 @@ int pt_unpack_rank(pt_ctx* ctx, int rank, int world, const void* dpacked) {
   CK(hipSetDevice(ctx->cfg.device_id));
   PackParams p = packParams(ctx, rank, world);
   CK(launchUnpack(p, ctx->d_accum, reinterpret_cast<const float*>(dpacked), ctx->stream));
-  dropMoments(ctx);
+  if (int rc = dropMoments(ctx)) return rc;
   return PT_OK;
 }
 

@@ -216,6 +216,19 @@ struct pt_ctx {
   // the colour (mixMomentsKernel), and the frames they hold (0: not valid, see noteMoments)
   float2* d_mom = nullptr;
   uint32_t momFrames = 0;
+  // PT_FLAG_ADAPTIVE (pt_adaptive.hip): per 8x8 tile of the image (ty * adaptTilesX + tx) the error the last
+  // pt_adaptive_update found and the frame count at which the tile retired (0: active), allocated and
+  // zeroed at creation. The update writes them on the caller's stream after every earlier launch's
+  // running-mean update (so every earlier camera-ray pass has read them); adaptDone is recorded after
+  // it, and every slot waits for it once before its next pass (adaptGen, like the bins)
+  float* d_err2 = nullptr;
+  uint32_t* d_retiredAt = nullptr;
+  int adaptTilesX = 0, adaptTiles = 0;
+  uint32_t adaptFrames = 0;         // momFrames at the last update (0: none since the restart)
+  bool adaptDirty = false;          // an update since the planes were last zero: a restart has something to clear
+  hipEvent_t adaptDone = nullptr;
+  hipStream_t adaptStream = nullptr;  // the stream adaptDone was last recorded on
+  unsigned adaptGen = 0, adaptGenSeen[MAX_SLOTS] = {};
   // pt_denoise_var: l = lum(tm(input)), step A's variance, the passes' two (l, v) planes
   float* d_lum = nullptr;
   float* d_var0 = nullptr;

@@ -38,6 +38,7 @@ FLAG_HOST_ACCEL = 0x200
 FLAG_MEGAKERNEL = 0x400
 FLAG_PRIMARY_PASS = 0x800
 FLAG_MOMENTS = 0x1000
+FLAG_ADAPTIVE = 0x2000
 GATHER = {"auto": 0, "copy": 1, "rccl": 2}
 
 
@@ -70,6 +71,14 @@ class FrameStats:
     tree4_nodes: int = 0  # 4-wide runtime-tree nodes
 
 
+@dataclass
+class AdaptiveStatus:
+    tiles: int       # 8x8 tiles of the image
+    retired: int     # of them retired
+    frames: int      # moments_frames() at the last adaptive_update (0: none since the restart)
+    max_err2: float  # the largest squared error over the tiles still active
+
+
 def _fp(a: np.ndarray):
     return a.ctypes.data_as(_native.c_float_p)
 
@@ -84,8 +93,9 @@ class Renderer:
     def __init__(self, width: int, height: int, integrator="lambert", max_bounce: int = -1, device: int = 0,
                  tile_rank: int = 0, tile_world: int = 1, tile_size: int = 32, flags: int = 0,
                  basic_samples: int = 128, basic_seed: int = 0, sample_rank: int = 0, sample_world: int = 1,
-                 devices=None, gather="auto", frame_batch: int = 0, moments: bool = False):
-        """moments: keep the per-pixel sample moments beside the running mean (PT_FLAG_MOMENTS:
+                 devices=None, gather="auto", frame_batch: int = 0, moments: bool = False, adaptive: bool = False):
+        """adaptive: converged 8x8 tiles stop taking samples (PT_FLAG_ADAPTIVE: adaptive_update(),
+        adaptive_status(), tile_error()); implies moments. moments: keep the per-pixel sample moments beside the running mean (PT_FLAG_MOMENTS:
         moments(), moments_frames(), and denoise_var()'s variance from them). devices: a list of HIP device ids (2..8, repeats allowed) makes this one context render
         screen tiles on all of them and gather them into the first device's accumulation every
         frame (pt_config.n_devices; gather "auto" / "copy" / "rccl"). frame_batch: most frames per
@@ -98,7 +108,7 @@ class Renderer:
         cfg.max_bounce = int(max_bounce)
         cfg.device_id = int(device)
         cfg.tile_rank, cfg.tile_world, cfg.tile_size = int(tile_rank), int(tile_world), int(tile_size)
-        cfg.flags = int(flags) | (FLAG_MOMENTS if moments else 0)
+        cfg.flags = int(flags) | (FLAG_MOMENTS if moments or adaptive else 0) | (FLAG_ADAPTIVE if adaptive else 0)
         cfg.basic_samples = int(basic_samples)
         cfg.basic_seed = int(basic_seed) & 0xFFFFFFFF
         cfg.sample_rank, cfg.sample_world = int(sample_rank), int(sample_world)
@@ -405,6 +415,32 @@ class Renderer:
         out = np.empty((self.height, self.width), np.float32)
         self._ck(self._lib.pt_download_variance(self._h, _fp(out)), "pt_download_variance")
         return out
+
+    def adaptive_update(self, **params):
+        """One adaptive-sampling decision (pt_adaptive_update; a Renderer(..., adaptive=True)): every
+        8x8 tile whose pixels' standard error of the tone-mapped luminance is <= threshold, once the
+        moments hold min_frames frames, retires and takes no more samples until the running mean
+        restarts. params: threshold, limit, min_frames (defaults: pt_adaptive_defaults). Asynchronous."""
+        prm = self._params("adaptive_update", _native.PtAdaptiveParams(), self._lib.pt_adaptive_defaults, params,
+                           ("threshold", "limit", "min_frames"), ("min_frames",))
+        self._ck(self._lib.pt_adaptive_update(self._h, C.byref(prm)), "pt_adaptive_update")
+
+    def adaptive_status(self) -> AdaptiveStatus:
+        """Tiles, how many have retired, the frames at the last update and the largest error still active."""
+        s = _native.PtAdaptiveState()
+        self._ck(self._lib.pt_adaptive_status(self._h, C.byref(s)), "pt_adaptive_status")
+        return AdaptiveStatus(s.tiles, s.retired, s.frames, s.max_err2)
+
+    def tile_error(self):
+        """(err2, retired_at): per 8x8 tile, (tilesY, tilesX) f32 / uint32, row 0 = bottom
+        (pt_download_tile_error): the squared error the last update found and the frame count at
+        which the tile retired (0: active)."""
+        shape = ((self.height + 7) // 8, (self.width + 7) // 8)
+        err2 = np.empty(shape, np.float32)
+        at = np.empty(shape, np.uint32)
+        self._ck(self._lib.pt_download_tile_error(self._h, _fp(err2), at.ctypes.data_as(C.POINTER(C.c_uint32))),
+                 "pt_download_tile_error")
+        return err2, at
 
     def temporal_resolve(self, frames: int, out_dptr: int | None = None, download: bool = True, **params):
         """The running mean of `frames` frames (frameCounter + 1) blended with the committed history

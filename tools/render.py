@@ -7,6 +7,7 @@ configuration progressively and write the image.
     python tools/render.py --config c4 --frames 4 --denoise --out out/c4.png  # + out/c4_denoised.png
     python tools/render.py --config c4 --frames 64 --denoise var --out out/c4.png  # pt_denoise_var instead
     python tools/render.py --config c2 --drag 8 --step 2 --out out/c2.png     # a camera drag, see below
+    python tools/render.py --config c2 --frames 4096 --adaptive 0.0039 --update-every 48 --out out/c2.png  # see below
 
 PNG: pass3's tonemap (pass3.fsh:14-24, limit 1.5) then imshow's gamma 2.2
 (BasicRayTracingWithC++/main.cpp:169-190); the BASIC config skips the tonemap
@@ -18,6 +19,10 @@ the cameras before it (pt_temporal_resolve / pt_temporal_commit). Writes the las
 running mean to <out>, the resolved image to <out>_resolved.png and the resolved image through the
 a-trous filter (pt_denoise_from; with --denoise var the variance-guided one, pt_denoise_var) to
 <out>_resolved_denoised.png.
+
+--adaptive THR [--update-every N]: adaptive sampling (PT_FLAG_ADAPTIVE). Renders windows of N frames
+(default 16) with a pt_adaptive_update after each, to --frames or until every 8x8 tile has retired,
+and prints frames / retired tiles / max_err2 per update and the rays against frames x pixels.
 """
 from __future__ import annotations
 
@@ -41,7 +46,13 @@ def main():
                          "pt_denoise_var steered by the sample moments")
     ap.add_argument("--drag", type=int, default=0, help="render a drag of N cameras with the temporal resolve")
     ap.add_argument("--step", type=float, default=2.0, help="--drag: degrees between two cameras")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="THR",
+                    help="adaptive sampling (PT_FLAG_ADAPTIVE): 8x8 tiles whose standard error of the tone-mapped "
+                         "luminance is <= THR (e.g. 0.0039 = 1/255) retire; renders to --frames or until every tile has")
+    ap.add_argument("--update-every", type=int, default=16, metavar="N", help="--adaptive: frames between two decisions")
     a = ap.parse_args()
+    if a.adaptive is not None and (a.drag or a.update_every < 1):
+        ap.error("--adaptive: not with --drag, and --update-every must be >= 1")
     if a.frames is None:
         a.frames = 1 if a.drag else 16
     import numpy as np
@@ -58,7 +69,9 @@ def main():
         tm = c[..., :3] * (np.float32(1) / (np.float32(1) + lum / np.float32(1.5)))[..., None]
         write_png(path, np.ascontiguousarray(tm, np.float32), 2.2, flip_rows=True)
 
-    kw = dict(basic_samples=a.frames) if basic else dict(moments=a.denoise == "var")
+    if a.adaptive is not None and basic:
+        ap.error("--adaptive: not for the BASIC config")
+    kw = dict(basic_samples=a.frames) if basic else dict(moments=a.denoise == "var", adaptive=a.adaptive is not None)
     with Renderer(cfg.width, cfg.height, cfg.integrator, max_bounce=cfg.max_bounce, flags=a.flags, **kw) as r:
         if basic:
             r.upload_shapes(scenes.cornell_shapes())
@@ -78,6 +91,22 @@ def main():
                 for f in range(a.frames):
                     r.render_frame(eye, rot, f, sync=False)
                 r.temporal_resolve(a.frames, download=False)
+        elif a.adaptive is not None:
+            # windows of --update-every frames, a decision after each, until every tile has retired
+            done = 0
+            while done < a.frames:
+                n = min(a.update_every, a.frames - done)
+                r.render_frames(eye, rot, done, n)
+                done += n
+                r.adaptive_update(threshold=a.adaptive, min_frames=max(2, min(16, a.update_every)))
+                s = r.adaptive_status()
+                print(f"{a.config}: {s.frames} frames, {s.retired} of {s.tiles} tiles retired, max_err2 {s.max_err2:.3e}")
+                if s.retired == s.tiles:
+                    break
+            pix = done * cfg.width * cfg.height
+            print(f"{a.config}: {r.stats().rays} rays for {done} frames x {cfg.width * cfg.height} pixels = {pix} "
+                  f"pixel samples ({r.stats().rays / pix:.3f} rays per pixel sample)")
+            a.frames = done
         else:
             for f in range(a.frames):
                 r.render_frame(eye, rot, f, sync=False)
