@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PT_ABI_VERSION 12 /* 2: in-process multi-GPU fields at the end of pt_config / pt_frame_stats;
+#define PT_ABI_VERSION 13 /* 2: in-process multi-GPU fields at the end of pt_config / pt_frame_stats;
                              3: scene-upload fields at the end of pt_frame_stats, pt_build_bvh_device;
                              4: BASIC shapes as doubles, its double image, the replayed random stream;
                              5: the displayed frame of a screen-tile split (pt_display_*);
@@ -45,7 +45,10 @@ extern "C" {
                                 ptm_sincosf) and pt_sph_texel_device; no existing struct changes;
                              12: adaptive sampling: converged 8x8 tiles retire from the sample moments
                                 (PT_FLAG_ADAPTIVE, pt_adaptive_update, pt_adaptive_status,
-                                pt_download_tile_error); no existing struct changes */
+                                pt_download_tile_error); no existing struct changes;
+                             13: the sample moments and adaptive sampling on screen-tile shares
+                                (PT_FLAG_SHARE_MOMENTS, pt_pack_owned_stats, pt_unpack_ranks_stats; pt_adaptive_update
+                                and pt_adaptive_status per share); no existing struct changes */
 
 /* error codes */
 #define PT_OK 0
@@ -86,11 +89,18 @@ extern "C" {
 #define PT_FLAG_MOMENTS 0x1000u   /* keep the running means of each sample's luminance and of its square beside
                                      the running mean (pt_download_moments, pt_denoise_var); not with
                                      PT_BASIC_CPU_COMPAT, PT_FLAG_COUNT_FETCHES, PT_FLAG_SERIAL_FRAMES,
-                                     tile_world > 1 or n_devices > 1 (pt_create: PT_E_INVALID) */
+                                     tile_world > 1 (unless PT_FLAG_SHARE_MOMENTS) or n_devices > 1 (pt_create:
+                                     PT_E_INVALID) */
 #define PT_FLAG_ADAPTIVE 0x2000u  /* 8x8 tiles whose pixels have converged stop taking samples (pt_adaptive_update);
                                      needs PT_FLAG_MOMENTS, with every restriction of that flag, and not with
                                      PT_FLAG_NO_BINS (pt_create: PT_E_INVALID). Every frame runs the camera-ray
                                      pass of PT_FLAG_PRIMARY_PASS */
+#define PT_FLAG_SHARE_MOMENTS 0x4000u /* PT_FLAG_MOMENTS (and with it PT_FLAG_ADAPTIVE) on a screen-tile share
+                                     (tile_world > 1): the moments of the rank's own pixels, gathered with
+                                     the running mean (pt_pack_owned_stats, pt_unpack_ranks_stats), and each
+                                     rank deciding its own 8x8 tiles. Needs PT_FLAG_MOMENTS, with every other
+                                     restriction of that flag, and not with sample_world > 1 (pt_create:
+                                     PT_E_INVALID) */
 
 /* in-process multi-GPU (pt_config.n_devices > 1) */
 #define PT_MAX_DEVICES 8
@@ -445,7 +455,8 @@ int pt_display_resolved(pt_ctx* ctx, float limit, float gamma, void* dimage);
  * The context counts the frames the moments hold: a launch with frameCounter == 0 sets the count to
  * its frames, a launch whose frameCounter equals the count adds its frames, any other frameCounter
  * sets it to 0 (not valid), and so do pt_upload_accum, pt_clear_accum (which also zeroes the plane),
- * pt_upload_scene, pt_upload_env, pt_unpack_rank and pt_unpack_ranks. */
+ * pt_upload_scene, pt_upload_env, pt_unpack_rank and pt_unpack_ranks (the last two not on a
+ * PT_FLAG_SHARE_MOMENTS context, below). */
 int pt_moments_frames(pt_ctx* ctx, uint32_t* frames);  /* 0: not valid, or no PT_FLAG_MOMENTS */
 /* width*height*2 f32 into host or device memory, after the frames rendered so far; synchronous.
  * PT_E_INVALID without PT_FLAG_MOMENTS. */
@@ -481,7 +492,7 @@ int pt_denoise_var_params_size(void);                      /* sizeof(pt_denoise_
  *   kf >= min_temporal:  L = lum(c_p);  q = 1 + L / limit;  gd = 1 / (q q) (the tonemap's slope);
  *                        n_p = max(c_p.w, kf) (the accumulation's .w is 1, a resolved image's its sample
  *                        count);  v = (max(m2 - m1 m1, 0) / n_p) (gd gd)
- *   else, or without PT_FLAG_MOMENTS (rank 0 of a tile split; during a drag): over the 7 x 7 window
+ *   else, or without PT_FLAG_MOMENTS (rank 0 of a plain tile split; during a drag): over the 7 x 7 window
  *                        around p (dy outer, dx inner, -3..3) the pixels q inside the image that are hits:
  *                        l_q = lum(tm(c_q));  s1 += l_q;  s2 += l_q l_q;  cnt += 1;
  *                        v = max(s2 / cnt - (s1 / cnt) (s1 / cnt), 0)
@@ -532,8 +543,9 @@ int pt_download_variance(pt_ctx* ctx, float* v);
  *     if (st.retired == st.tiles) stop;       (the picture is done)
  *   }
  *   frameCounter++;
- * Not part of this: screen-tile shares and device groups (excluded with PT_FLAG_MOMENTS), decisions
- * finer than a tile, un-retiring, and retirement carried across camera moves. */
+ * Not part of this: device groups (excluded with PT_FLAG_MOMENTS), decisions finer than a tile,
+ * un-retiring, and retirement carried across camera moves. Screen-tile shares: PT_FLAG_SHARE_MOMENTS
+ * below. */
 typedef struct pt_adaptive_params {
   float threshold;   /* a pixel has converged when the standard error of the mean of its tone-mapped
                         luminance is <= threshold; > 0 and finite */
@@ -546,7 +558,7 @@ void pt_adaptive_defaults(pt_adaptive_params* prm);  /* 1 / 255.f, 1.5, 16 */
 int pt_adaptive_params_size(void);                   /* sizeof(pt_adaptive_params) of the loaded library */
 
 typedef struct pt_adaptive_state {
-  int tiles;            /* 8x8 tiles of the image: tilesX * tilesY */
+  int tiles;            /* 8x8 tiles of the image: tilesX * tilesY (a PT_FLAG_SHARE_MOMENTS share: those it owns) */
   int retired;          /* of them retired */
   uint32_t frames;      /* pt_moments_frames at the last update (0: none since the restart) */
   float max_err2;       /* the largest err2 over the tiles still active (0 when none is) */
@@ -566,6 +578,51 @@ int pt_adaptive_status(pt_ctx* ctx, pt_adaptive_state* st);
  * update that looked at the tile left it, retired_at the frame count at which the tile retired (0:
  * active). Synchronous. PT_E_INVALID without PT_FLAG_ADAPTIVE. */
 int pt_download_tile_error(pt_ctx* ctx, float* err2, uint32_t* retired_at);
+
+/* The sample moments and adaptive sampling on a screen-tile split. A shard tile's edge is a multiple of
+ * 8, so every 8x8 tile of the image belongs to exactly one rank: each rank can keep the moments of its
+ * own pixels and decide its own tiles, and nothing of that needs another rank. A PT_FLAG_SHARE_MOMENTS
+ * context (PT_FLAG_MOMENTS with tile_world > 1, PT_FLAG_ADAPTIVE too) does:
+ *  - The moments plane is still width x height. After a launch it holds this rank's values at the pixels
+ *    it owns -- bit for bit what a one-context PT_FLAG_MOMENTS render holds there (the same update of the
+ *    same floats) -- and everywhere else what was last unpacked (zero at creation). pt_moments_frames
+ *    counts this rank's own frames, by the rule above.
+ *  - pt_unpack_rank, pt_unpack_ranks and pt_unpack_ranks_stats do not invalidate the moments and leave the
+ *    tile planes alone: they write other ranks' pixels only. (On a context without the flag they invalidate
+ *    as before.) pt_upload_accum, pt_clear_accum, pt_upload_scene, pt_upload_env, a gap in frameCounter and
+ *    the restart at frameCounter == 0 keep their effect.
+ *  - pt_adaptive_update decides the 8x8 tiles this rank owns and writes only their entries of the two
+ *    planes, which stay whole-image planes (pt_download_tile_error: 0 at every other rank's entries). The
+ *    ranks' planes have disjoint support: the image's planes are their element-wise sums.
+ *  - pt_adaptive_status counts the tiles this rank owns (0 for a rank past the last shard tile, whose
+ *    updates succeed and do nothing); the image's status is the sum of the ranks' tiles and retired and the
+ *    largest of their max_err2.
+ *  - pt_denoise_var and pt_temporal_resolve on rank 0 after pt_unpack_ranks_stats see a whole moments
+ *    plane, and kf = pt_moments_frames selects step A's moments branch.
+ *
+ * pt_pack_owned_stats: pt_pack_owned with the moments -- pt_owned_pixel_count slots of 5 f32 (r, g, b,
+ * m1, m2), the packed order of pt_pack_owned, a slot outside the image zeros. One launch on the context's
+ * stream, after the frames rendered so far. pt_unpack_ranks_stats: pt_unpack_ranks of such buffers
+ * (dpacked[k] = rank k's, [0] unused, a NULL entry is skipped; world <= 16), one launch: the accumulation
+ * (r, g, b, 1) and the moments (m1, m2) of every other rank's pixels. The caller guarantees that every
+ * rank rendered the same frames: rank 0's pt_moments_frames is then the count of the whole plane. Both
+ * PT_E_INVALID without PT_FLAG_SHARE_MOMENTS and for n_devices > 1 contexts.
+ *
+ * The display() loop of N ranks, one batch of frames per round (rank r of N):
+ *   pt_render_frames_async(ctx, eye, rot, frameCounter, n);  frameCounter += n;
+ *   pt_pack_owned_stats(ctx, send);
+ *   gather send to rank 0's recv[r] (RCCL over xGMI);
+ *   rank 0:  pt_unpack_ranks_stats(ctx, N, recv);            (may run on a communication stream,
+ *                                                             pt_set_stream, while the next batch renders)
+ *   every K rounds:
+ *     pt_adaptive_update(ctx, &prm);  pt_adaptive_status(ctx, &st);
+ *     all-reduce: tiles = sum st.tiles, retired = sum st.retired, max_err2 = max st.max_err2;
+ *     if (retired == tiles) every rank stops;                 (the picture is done)
+ *   rank 0:  pt_render_guides;  pt_denoise_var;  pt_display_denoised.
+ * Not part of this: device groups, sample_world > 1, re-dealing tiles among the ranks as they retire. */
+#define PT_PACK_STATS_F 5 /* f32 per slot of pt_pack_owned_stats */
+int pt_pack_owned_stats(pt_ctx* ctx, void* dpacked);
+int pt_unpack_ranks_stats(pt_ctx* ctx, int world, const void* const* dpacked);
 
 /* Stream interop: render on the caller's HIP stream (e.g. torch's current
  * stream). NULL restores the context's own stream. */

@@ -57,7 +57,7 @@ SOURCES = {
     "pt_denoise.o": ("hip", CSRC / "pt_denoise.hip", [CSRC / "pt_atrous.h", *_DEV]),
     "pt_temporal.o": ("hip", CSRC / "pt_temporal.hip", _DEV),
     "pt_variance.o": ("hip", CSRC / "pt_variance.hip", [CSRC / "pt_atrous.h", *_DEV]),
-    "pt_adaptive.o": ("hip", CSRC / "pt_adaptive.hip", _DEV),
+    "pt_adaptive.o": ("hip", CSRC / "pt_adaptive.hip", _FRAME),
     "pt_runtime.o": ("cxx", CSRC / "pt_runtime.cpp", [*_HOST, CSRC / "pt_plan.h", CSRC / "pt_accel.h", INCLUDE / "pt_scene.h",
                                                        INCLUDE / "pt_fmath.h"]),
     "pt_post.o": ("cxx", CSRC / "pt_post.cpp", _HOST),

@@ -13,11 +13,12 @@ from . import _build
 
 _lib = None
 
-ABI_VERSION = 12  # include/pt_abi.h PT_ABI_VERSION
+ABI_VERSION = 13  # include/pt_abi.h PT_ABI_VERSION
 # an older tuning build (tools/tune.py A/B against a previous round's library) loads when its structs
 # match: ABI 7 only added pt_unpack_ranks, ABI 8 the guide buffers and the denoiser, ABI 9 the
 # temporal resolve, ABI 10 the sample moments and the variance-guided filter, ABI 11 the
-# diagnostics of the sky texel decision and ABI 12 adaptive sampling, which such a build does not have
+# diagnostics of the sky texel decision, ABI 12 adaptive sampling and ABI 13 the moments of a
+# screen-tile share, which such a build does not have
 ABI_STRUCTS_SINCE = 6
 c_float_p = C.POINTER(C.c_float)
 c_double_p = C.POINTER(C.c_double)
@@ -153,6 +154,8 @@ SIGNATURES = {
     "pt_adaptive_update": (C.c_int, [C.c_void_p, C.POINTER(PtAdaptiveParams)]),
     "pt_adaptive_status": (C.c_int, [C.c_void_p, C.POINTER(PtAdaptiveState)]),
     "pt_download_tile_error": (C.c_int, [C.c_void_p, c_float_p, C.POINTER(C.c_uint32)]),
+    "pt_pack_owned_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pt_unpack_ranks_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "pt_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pt_synchronize": (C.c_int, [C.c_void_p]),
     "pt_get_stats": (C.c_int, [C.c_void_p, C.POINTER(PtFrameStats)]),

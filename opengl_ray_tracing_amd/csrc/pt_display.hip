@@ -148,6 +148,67 @@ hipError_t launchUnpackRanks(const RanksUnpack& d, int world, float4* accum, hip
   return hipGetLastError();
 }
 
+// The gather of a PT_FLAG_SHARE_MOMENTS split: packKernel / unpackRanksKernel with the pixel's moments
+// behind its colour, PACK_STATS_F = 5 floats (r, g, b, m1, m2), 20 bytes per slot. One lane per slot;
+// the accumulation (16 B) and the moments (8 B) are touched once per gather, so they stream like the
+// running-mean update's. The packed side is written as the 12-byte pack writes it, one dword store per
+// float and lane: a slot's 20 bytes are 4-byte aligned only, and a wave's five stores together cover
+// 1280 contiguous bytes. (Staging a block's slots through LDS would make each store instruction
+// contiguous; not done: the 12-byte pack has not needed it.) The packed buffers themselves are plain
+// accesses: the collective reads what the pack wrote, and the unpack what the collective wrote.
+__global__ void packStatsKernel(PackParams p, const float4* accum, const float2* moments, float* packed) {
+  long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.count) return;
+  int px, py;
+  float4 c = make_float4(0, 0, 0, 0);
+  float2 m = make_float2(0, 0);
+  if (pixelOfSlot(p.share, k, px, py)) {
+    const size_t i = (size_t)py * p.share.width + px;
+    c = ldStream(accum + i);
+    m = ldStream(moments + i);
+  }
+  float* out = packed + PACK_STATS_F * k;
+  out[0] = c.x;
+  out[1] = c.y;
+  out[2] = c.z;
+  out[3] = m.x;
+  out[4] = m.y;
+}
+hipError_t launchPackStats(const PackParams& p, const float4* accum, const float2* moments, float* packed,
+                           hipStream_t s) {
+  if (!accum || !moments || !packed) return hipErrorInvalidValue;
+  if (p.count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(packStatsKernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, moments,
+                     packed);
+  return hipGetLastError();
+}
+// blockIdx.y = rank - 1 of ranks 1..world-1, as unpackRanksKernel
+__global__ void unpackRanksStatsKernel(RanksUnpack d, float4* accum, float2* moments) {
+  const int rank = blockIdx.y + 1;
+  const float* src = static_cast<const float*>(d.src[rank]);
+  if (!src) return;
+  PackParams p = d.base;
+  p.share.rank = rank;
+  p.count = d.count[rank];
+  long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= p.count) return;
+  int px, py;
+  if (!pixelOfSlot(p.share, k, px, py)) return;
+  const float* in = src + PACK_STATS_F * k;
+  const size_t i = (size_t)py * p.share.width + px;
+  stStream(accum + i, make_float4(in[0], in[1], in[2], 1.0f));
+  stStream(moments + i, make_float2(in[3], in[4]));
+}
+hipError_t launchUnpackRanksStats(const RanksUnpack& d, int world, float4* accum, float2* moments, hipStream_t s) {
+  if (!accum || !moments) return hipErrorInvalidValue;
+  long most = 0;
+  for (int k = 1; k < world; k++) most = d.count[k] > most ? d.count[k] : most;
+  if (world < 2 || most <= 0) return hipSuccess;
+  hipLaunchKernelGGL(unpackRanksStatsKernel, dim3((unsigned)((most + 255) / 256), (unsigned)(world - 1)), dim3(256), 0,
+                     s, d, accum, moments);
+  return hipGetLastError();
+}
+
 // The running means of a batch of pipelined frames (storeSample's update, deferred to frame order):
 // frame f's colours at col + f * colStride, slot k of the share (pt_frame.h slotOf), its weight
 // 1 / (frameCounter + f + 1); the pixel's mean after each frame is the one serial frames store (mixf

@@ -544,6 +544,11 @@ hipError_t launchDisplayOwn(const PackParams& p, const float4* accum, float limi
 hipError_t launchDisplayUnpack(const RanksUnpack& d, int world, uchar4* image, hipStream_t s);
 hipError_t launchUnpackRanks(const RanksUnpack& d, int world, float4* accum, hipStream_t s);
 hipError_t launchUnpack(const PackParams& p, float4* accum, const float* packed, hipStream_t s);
+// The gather of a PT_FLAG_SHARE_MOMENTS split (pt_pack_owned_stats, pt_unpack_ranks_stats): launchPack and
+// launchUnpackRanks with the pixel's moments behind its colour, PACK_STATS_F floats (r, g, b, m1, m2) per slot
+constexpr int PACK_STATS_F = 5;
+hipError_t launchPackStats(const PackParams& p, const float4* accum, const float2* moments, float* packed, hipStream_t s);
+hipError_t launchUnpackRanksStats(const RanksUnpack& d, int world, float4* accum, float2* moments, hipStream_t s);
 // the running-mean updates of nFrames pipelined frames over the rank's owned pixels (PackParams
 // mapping), in frame order: for f = 0 .. nFrames-1, accum = mix(accum, col + f * colStride,
 // 1 / (frameCounter + f + 1)) (IS:868-871, pass2.fsh:15) -- each pixel read and written once
@@ -558,12 +563,15 @@ hipError_t launchMixMoments(const PackParams& p, float4* accum, float2* moments,
 hipError_t launchMixAdaptive(const PackParams& p, float4* accum, float2* moments, const float* col, size_t colStride,
                              int nFrames, uint32_t frameCounter, const uint32_t* retiredAt, hipStream_t s);
 // Adaptive sampling's decision (pt_adaptive.hip tileErrorKernel, pt_abi.h pt_adaptive_update): one
-// wave per 8x8 tile of the whole image; a tile not yet retired takes err2 = the largest variance of
-// the mean of its pixels' tone-mapped luminance and retires (retiredAt = frames) when frames >=
-// minFrames and err2 <= thr2
+// wave per 8x8 wave tile of the context's share (the whole image with world 1), which is the image's
+// tile (y / 8) * tilesX + x / 8 of the two planes; a tile not yet retired takes err2 = the largest
+// variance of the mean of its pixels' tone-mapped luminance and retires (retiredAt = frames) when
+// frames >= minFrames and err2 <= thr2
 struct TileErrorParams {
-  int width, height;
-  int tilesX, tiles;
+  Share share;
+  int shardTiles;            // pt_frame.h shardTiles(share)
+  int waveTiles;             // pt_frame.h waveTiles(share): the waves of the launch (0: a rank that owns nothing)
+  int tilesX;                // image tiles per row, (width + 7) / 8
   const float4* accum;
   const float2* moments;
   float* err2;

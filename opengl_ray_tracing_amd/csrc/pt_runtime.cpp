@@ -210,17 +210,25 @@ int pt_create(pt_ctx** out, const pt_config* cfg) {
   }
   if (cfg->flags & PT_FLAG_MOMENTS) {
     // the moments are collected from the pipelined frames' colour buffer, which these do not have,
-    // and are this context's own: gathering them across ranks is not part of the library yet
+    // and are this context's own: a screen-tile share keeps them only when it says how they are
+    // gathered (PT_FLAG_SHARE_MOMENTS: pt_pack_owned_stats / pt_unpack_ranks_stats)
+    const bool shared = (cfg->flags & PT_FLAG_SHARE_MOMENTS) != 0;
     const char* why = nullptr;
     if (cfg->integrator == PT_BASIC_CPU_COMPAT) why = "PT_BASIC_CPU_COMPAT";
     else if (cfg->flags & PT_FLAG_COUNT_FETCHES) why = "PT_FLAG_COUNT_FETCHES";
     else if (cfg->flags & PT_FLAG_SERIAL_FRAMES) why = "PT_FLAG_SERIAL_FRAMES";
-    else if (cfg->tile_world > 1) why = "tile_world > 1";
+    else if (cfg->tile_world > 1 && !shared) why = "tile_world > 1 (without PT_FLAG_SHARE_MOMENTS)";
     else if (n > 1) why = "n_devices > 1";
+    // (each sample rank's moments are of its own samples: merging them is not the gather's bit-exact copy)
+    else if (shared && cfg->sample_world > 1) why = "PT_FLAG_SHARE_MOMENTS and sample_world > 1";
     if (why) {
       g_create_err = std::string("pt_create: PT_FLAG_MOMENTS cannot be combined with ") + why;
       return PT_E_INVALID;
     }
+  }
+  if ((cfg->flags & PT_FLAG_SHARE_MOMENTS) && !(cfg->flags & PT_FLAG_MOMENTS)) {
+    g_create_err = "pt_create: PT_FLAG_SHARE_MOMENTS needs PT_FLAG_MOMENTS";
+    return PT_E_INVALID;
   }
   if (cfg->flags & PT_FLAG_ADAPTIVE) {
     // tiles retire from the moments, in the camera-ray pass, which needs the camera-ray bins
@@ -2032,15 +2040,17 @@ int pt_adaptive_update(pt_ctx* ctx, const pt_adaptive_params* prm) {
   // tiles retire in the camera-ray pass: a context whose launches cannot run it retires nothing
   if (!planFrame(ctx, false, 2).bins)
     return fail(ctx, PT_E_INVALID, "pt_adaptive_update: this context's frames run no camera-ray pass (no camera-ray bins for its scene)");
-  // after every launch so far has updated the running mean -- and so after their passes read the planes
+  // after every launch so far has updated the running mean -- and so after their passes read the planes.
+  // (A share reads its own pixels only: rank 0's update needs no ordering against an unpack of the
+  // other ranks' pixels in flight on a communication stream.)
   if (int rc = joinPipe(ctx)) return rc;
   if (int rc = joinAdaptive(ctx)) return rc;
   CK(hipSetDevice(ctx->cfg.device_id));
   TileErrorParams t;
-  t.width = ctx->cfg.width;
-  t.height = ctx->cfg.height;
+  t.share = shareOf(ctx, ctx->cfg.tile_rank, ctx->cfg.tile_world);
+  t.shardTiles = shardTiles(t.share);
+  t.waveTiles = waveTiles(t.share);
   t.tilesX = ctx->adaptTilesX;
-  t.tiles = ctx->adaptTiles;
   t.accum = ctx->d_accum;
   t.moments = ctx->d_mom;
   t.err2 = ctx->d_err2;
@@ -2079,11 +2089,18 @@ int pt_adaptive_status(pt_ctx* ctx, pt_adaptive_state* st) {
   std::vector<float> err2;
   std::vector<uint32_t> retiredAt;
   if (int rc = adaptivePlanes(ctx, err2, retiredAt)) return rc;
-  st->tiles = ctx->adaptTiles;
+  // over the image tiles of this context's share (every tile with tile_world 1): a shard tile's edge
+  // is a multiple of 8, so a tile's first pixel names its owner
+  const Share sh = shareOf(ctx, ctx->cfg.tile_rank, ctx->cfg.tile_world);
+  st->tiles = 0;
   st->retired = 0;
   st->frames = ctx->adaptFrames;
   st->max_err2 = 0.0f;
   for (int k = 0; k < ctx->adaptTiles; k++) {
+    const int ty = k / ctx->adaptTilesX, tx = k - ty * ctx->adaptTilesX;
+    const int g = (ty * 8 / sh.shardSize) * sh.shardsX + tx * 8 / sh.shardSize;
+    if (g % sh.world != sh.rank) continue;
+    st->tiles++;
     if (retiredAt[k] != 0u) st->retired++;
     else st->max_err2 = err2[k] > st->max_err2 ? err2[k] : st->max_err2;
   }
@@ -2186,6 +2203,15 @@ int pt_display_unpack(pt_ctx* ctx, int world, const void* const* dpacked, void* 
   return PT_OK;
 }
 
+// Another rank's pixels were written into the accumulation. A plain context's moments no longer
+// describe it (they were this context's own samples of those pixels). A PT_FLAG_SHARE_MOMENTS
+// context's moments and tile planes are of its own pixels and tiles only, which an unpack does not
+// write: they stay valid -- rank 0 unpacks after every batch
+static int unpackedOthers(pt_ctx* ctx) {
+  if (ctx->cfg.flags & PT_FLAG_SHARE_MOMENTS) return PT_OK;
+  return dropMoments(ctx);
+}
+
 int pt_unpack_ranks(pt_ctx* ctx, int world, const void* const* dpacked) {
   if (!ctx || !dpacked || world < 1 || world > DISPLAY_MAX_WORLD) return PT_E_INVALID;
   if (!ctx->peers.empty()) return fail(ctx, PT_E_INVALID, "device groups gather inside pt_render_frame");
@@ -2199,7 +2225,7 @@ int pt_unpack_ranks(pt_ctx* ctx, int world, const void* const* dpacked) {
     d.count[k] = packParams(ctx, k, world).count;
   }
   CK(launchUnpackRanks(d, world, ctx->d_accum, ctx->stream));
-  if (int rc = dropMoments(ctx)) return rc;
+  if (int rc = unpackedOthers(ctx)) return rc;
   return PT_OK;
 }
 
@@ -2210,7 +2236,46 @@ int pt_unpack_rank(pt_ctx* ctx, int rank, int world, const void* dpacked) {
   CK(hipSetDevice(ctx->cfg.device_id));
   PackParams p = packParams(ctx, rank, world);
   CK(launchUnpack(p, ctx->d_accum, reinterpret_cast<const float*>(dpacked), ctx->stream));
-  if (int rc = dropMoments(ctx)) return rc;
+  if (int rc = unpackedOthers(ctx)) return rc;
+  return PT_OK;
+}
+
+// The gather of a PT_FLAG_SHARE_MOMENTS split: the running means with the moments, 5 f32 per slot
+static int shareMomentsOnly(pt_ctx* ctx, const char* what) {
+  if (!ctx->peers.empty()) return fail(ctx, PT_E_INVALID, "device groups gather inside pt_render_frame");
+  if (!(ctx->cfg.flags & PT_FLAG_SHARE_MOMENTS) || !ctx->d_mom)
+    return fail(ctx, PT_E_INVALID, std::string(what) + ": not a PT_FLAG_SHARE_MOMENTS context");
+  return PT_OK;
+}
+
+int pt_pack_owned_stats(pt_ctx* ctx, void* dpacked) {
+  if (!ctx) return PT_E_INVALID;
+  if (!dpacked) return fail(ctx, PT_E_INVALID, "pt_pack_owned_stats: null buffer");
+  if (int rc = shareMomentsOnly(ctx, "pt_pack_owned_stats")) return rc;
+  if (int rc = joinPipe(ctx)) return rc;  // after the frames rendered so far, as pt_pack_owned
+  CK(hipSetDevice(ctx->cfg.device_id));
+  PackParams p = packParams(ctx, ctx->cfg.tile_rank, ctx->cfg.tile_world);
+  CK(launchPackStats(p, ctx->d_accum, ctx->d_mom, reinterpret_cast<float*>(dpacked), ctx->stream));
+  return PT_OK;
+}
+
+// On the caller's stream, which may be a communication stream while the next launch renders: that
+// launch's running-mean update writes only this rank's pixels, this only the others'
+int pt_unpack_ranks_stats(pt_ctx* ctx, int world, const void* const* dpacked) {
+  if (!ctx) return PT_E_INVALID;
+  if (!dpacked || world < 1 || world > DISPLAY_MAX_WORLD)
+    return fail(ctx, PT_E_INVALID, "pt_unpack_ranks_stats: world must be 1..16 and the buffer list not null");
+  if (int rc = shareMomentsOnly(ctx, "pt_unpack_ranks_stats")) return rc;
+  if (int rc = joinPipe(ctx)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  RanksUnpack d;
+  std::memset(&d, 0, sizeof(d));
+  d.base = packParams(ctx, 0, world);
+  for (int k = 1; k < world; k++) {
+    d.src[k] = dpacked[k];
+    d.count[k] = packParams(ctx, k, world).count;
+  }
+  CK(launchUnpackRanksStats(d, world, ctx->d_accum, ctx->d_mom, ctx->stream));
   return PT_OK;
 }
 

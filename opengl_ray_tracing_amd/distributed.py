@@ -50,6 +50,15 @@ def owned_pixels(width: int, height: int, rank: int, world: int, shard: int = 32
     return np.stack([px[v], py[v]], 1).astype(np.int32)
 
 
+def owned_image_tiles(width: int, height: int, rank: int, world: int, shard: int = 32) -> np.ndarray:
+    """(tilesY, tilesX) bool: the 8x8 tiles of the image (adaptive sampling's, row 0 = bottom) that
+    lie in `rank`'s shard tiles. `shard` is a multiple of 8, so a tile never straddles two shard
+    tiles: its first pixel names its owner, and every tile has exactly one."""
+    sx, _ = shard_grid(width, height, shard)
+    ty, tx = np.mgrid[0:(height + 7) // 8, 0:(width + 7) // 8]
+    return ((ty * 8 // shard) * sx + tx * 8 // shard) % world == rank
+
+
 def pack(accum: np.ndarray, rank: int, world: int, shard: int = 32) -> np.ndarray:
     h, w = accum.shape[:2]
     px, py, v = packed_coords(w, h, rank, world, shard)
@@ -78,6 +87,11 @@ class FrameGather:
       whole accumulation to rank 0 when it is wanted, bit-identical to a 1-GPU render).
     * "accum" -- the running mean itself (3 f32 per pixel, pt_pack_owned / pt_unpack_ranks: the
       other ranks' buffers in one launch) into rank 0's accumulation after every batch of frames.
+      With `moments=True` (every rank a Renderer(..., share_moments=True)) the sample moments travel
+      with it: 5 f32 per pixel (r, g, b, m1, m2; pt_pack_owned_stats / pt_unpack_ranks_stats), so rank
+      0's moments plane is whole after each gather (denoise_var's temporal variance), and
+      `adaptive_status()` / `tile_error()` combine the ranks' adaptive-sampling decisions, each over
+      its own 8x8 tiles, into the image's.
 
     Device buffers are torch tensors (torch is the allocator/collective plumbing here).
     The renderer runs on a torch stream of its own; each call packs the frame just
@@ -90,8 +104,8 @@ class FrameGather:
     """
 
     def __init__(self, renderer, rank: int, world: int, device, overlap: bool = True, mode: str = "accum",
-                 limit: float = 1.5, gamma: float = 0.0, proxy: bool = False):
-        """proxy: one process on one GPU times rank `rank`'s share of the split with its real
+                 limit: float = 1.5, gamma: float = 0.0, proxy: bool = False, moments: bool = False):
+        """moments: gather the sample moments with the running mean (accum mode only). proxy: one process on one GPU times rank `rank`'s share of the split with its real
         per-batch work -- the pack, and on rank 0 the unpack of every other rank's buffer -- but
         no collective (the receive buffers keep what they hold; tools/shard_time.py)."""
         import torch
@@ -99,10 +113,14 @@ class FrameGather:
 
         if mode not in ("accum", "display"):
             raise ValueError(f"mode {mode!r}")
+        if moments and mode != "accum":
+            raise ValueError("moments=True gathers with the running mean: mode 'accum' only")
         self.torch, self.dist = torch, dist
+        self.moments = bool(moments)
         self.proxy = proxy
         self.r, self.rank, self.world, self.device = renderer, rank, world, device
         self.mode, self.limit, self.gamma = mode, float(limit), float(gamma)
+        self._floats = 5 if moments else 3
         counts = [renderer.owned_pixel_count(k, world) for k in range(world)]
         self.maxc = max(counts)
         self.overlap = overlap and (proxy or not _staged())
@@ -113,8 +131,8 @@ class FrameGather:
         nbuf = 2 if self.overlap else 1
         if mode == "display":  # packed slots: 3 u8 (r, g, b of the displayed pixel)
             shape, dtype = (self.maxc * 3,), torch.uint8
-        else:  # packed slots: 3 f32 (r, g, b; pt_pack_owned), 12 bytes per pixel over xGMI
-            shape, dtype = (self.maxc, 3), torch.float32
+        else:  # packed slots: 3 f32 (r, g, b; pt_pack_owned), 12 bytes per pixel over xGMI -- 5 f32, 20 bytes, with the moments
+            shape, dtype = (self.maxc, self._floats), torch.float32
         self.send = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(nbuf)]
         self.recv = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(world)] \
             if rank == 0 else None
@@ -141,12 +159,16 @@ class FrameGather:
                 self.r.display_own(self.images[i].data_ptr(), self.limit, self.gamma)
             else:
                 self.r.display_pack(self.send[i].data_ptr(), self.limit, self.gamma)
+        elif self.moments:
+            self.r.pack_owned_stats(self.send[i].data_ptr())
         else:
             self.r.pack_owned(self.send[i].data_ptr())
 
     def _unpack(self, i):
         if self.mode == "display":
             self.r.display_unpack(self.world, self._recv_ptrs, self.images[i].data_ptr())
+        elif self.moments:  # every other rank's running means and moments in one launch
+            self.r.unpack_ranks_stats(self.world, self._recv_ptrs)
         else:  # every other rank's running means in one launch (pt_unpack_ranks)
             self.r.unpack_ranks(self.world, self._recv_ptrs)
 
@@ -184,12 +206,13 @@ class FrameGather:
     def gather_accum(self):
         """Bring every rank's running mean to rank 0's accumulation (3 f32 per pixel, once,
         synchronous): rank 0 then holds the whole accumulation, bit-identical to a 1-GPU
-        render. Collective: every rank calls it."""
+        render -- with moments=True the moments too (5 f32 per pixel). Collective: every rank
+        calls it."""
         torch, dist = self.torch, self.dist
         self.synchronize()
         with torch.cuda.stream(self.render_stream):  # every allocation, copy and kernel in one stream order
-            buf = torch.zeros((self.maxc, 3), dtype=torch.float32, device=self.device)
-            self.r.pack_owned(buf.data_ptr())
+            buf = torch.zeros((self.maxc, self._floats), dtype=torch.float32, device=self.device)
+            (self.r.pack_owned_stats if self.moments else self.r.pack_owned)(buf.data_ptr())
             recv = [torch.zeros_like(buf) for _ in range(self.world)] if self.rank == 0 else None
             if _staged():
                 host = buf.cpu()
@@ -201,8 +224,48 @@ class FrameGather:
             else:
                 dist.gather(buf, gather_list=recv, dst=0)
             if self.rank == 0:
-                self.r.unpack_ranks(self.world, [0] + [t.data_ptr() for t in recv[1:]])
+                (self.r.unpack_ranks_stats if self.moments else self.r.unpack_ranks)(
+                    self.world, [0] + [t.data_ptr() for t in recv[1:]])
         self.render_stream.synchronize()
+
+    def _reduce(self, a: np.ndarray, op, dst=None) -> np.ndarray:
+        """One small host array combined over the ranks (all-reduce, or a reduce to rank `dst`):
+        through the device under RCCL, as it is under gloo."""
+        torch, dist = self.torch, self.dist
+        t = torch.from_numpy(np.ascontiguousarray(a))
+        if not _staged():
+            t = t.to(self.device)
+        if dst is None:
+            dist.all_reduce(t, op=op)
+        else:
+            dist.reduce(t, dst=dst, op=op)
+        return t.cpu().numpy()
+
+    def adaptive_status(self):
+        """The image's adaptive-sampling status on every rank (collective; every rank a
+        Renderer(..., adaptive=True, share_moments=True)): each rank's adaptive_status() is over the
+        8x8 tiles it owns; tiles and retired are summed, max_err2 is the largest, so `retired ==
+        tiles` says on every rank at once that the picture is done. With proxy=True: this rank's own."""
+        from .renderer import AdaptiveStatus
+        st = self.r.adaptive_status()
+        if self.proxy:
+            return st
+        n = self._reduce(np.array([st.tiles, st.retired], np.int64), self.dist.ReduceOp.SUM)
+        # f32 -> f64 is exact, and so is the frame count: one reduction for both
+        m = self._reduce(np.array([np.float32(st.max_err2), st.frames], np.float64), self.dist.ReduceOp.MAX)
+        return AdaptiveStatus(int(n[0]), int(n[1]), int(m[1]), float(np.float32(m[0])))
+
+    def tile_error(self):
+        """The image's tile planes on rank 0 (collective; None on the other ranks): the ranks' planes
+        have disjoint support -- a rank writes only its own tiles' entries, the others stay 0 -- so
+        their element-wise sum is the image's (x + 0 is x: exact). (err2, retired_at) as
+        Renderer.tile_error()."""
+        err2, at = self.r.tile_error()
+        if self.proxy:
+            return err2, at
+        err2 = self._reduce(err2, self.dist.ReduceOp.SUM, dst=0)
+        at = self._reduce(at.astype(np.int64), self.dist.ReduceOp.SUM, dst=0)
+        return (err2, at.astype(np.uint32)) if self.rank == 0 else None
 
     def synchronize(self):
         self.comm_stream.synchronize()

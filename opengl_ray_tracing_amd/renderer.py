@@ -39,6 +39,8 @@ FLAG_MEGAKERNEL = 0x400
 FLAG_PRIMARY_PASS = 0x800
 FLAG_MOMENTS = 0x1000
 FLAG_ADAPTIVE = 0x2000
+FLAG_SHARE_MOMENTS = 0x4000
+PACK_STATS_F = 5  # f32 per packed slot of pack_owned_stats: r, g, b, m1, m2
 GATHER = {"auto": 0, "copy": 1, "rccl": 2}
 
 
@@ -73,7 +75,7 @@ class FrameStats:
 
 @dataclass
 class AdaptiveStatus:
-    tiles: int       # 8x8 tiles of the image
+    tiles: int       # 8x8 tiles of the image (of a share_moments share: those it owns)
     retired: int     # of them retired
     frames: int      # moments_frames() at the last adaptive_update (0: none since the restart)
     max_err2: float  # the largest squared error over the tiles still active
@@ -93,8 +95,12 @@ class Renderer:
     def __init__(self, width: int, height: int, integrator="lambert", max_bounce: int = -1, device: int = 0,
                  tile_rank: int = 0, tile_world: int = 1, tile_size: int = 32, flags: int = 0,
                  basic_samples: int = 128, basic_seed: int = 0, sample_rank: int = 0, sample_world: int = 1,
-                 devices=None, gather="auto", frame_batch: int = 0, moments: bool = False, adaptive: bool = False):
-        """adaptive: converged 8x8 tiles stop taking samples (PT_FLAG_ADAPTIVE: adaptive_update(),
+                 devices=None, gather="auto", frame_batch: int = 0, moments: bool = False, adaptive: bool = False,
+                 share_moments: bool = False):
+        """share_moments: moments / adaptive on a screen-tile share (PT_FLAG_SHARE_MOMENTS, with tile_world > 1):
+        the moments of the rank's own pixels, gathered with pack_owned_stats() / unpack_ranks_stats(), and
+        adaptive_update() / adaptive_status() over the rank's own tiles (distributed.FrameGather(moments=True)
+        gathers and combines them). adaptive: converged 8x8 tiles stop taking samples (PT_FLAG_ADAPTIVE: adaptive_update(),
         adaptive_status(), tile_error()); implies moments. moments: keep the per-pixel sample moments beside the running mean (PT_FLAG_MOMENTS:
         moments(), moments_frames(), and denoise_var()'s variance from them). devices: a list of HIP device ids (2..8, repeats allowed) makes this one context render
         screen tiles on all of them and gather them into the first device's accumulation every
@@ -108,7 +114,8 @@ class Renderer:
         cfg.max_bounce = int(max_bounce)
         cfg.device_id = int(device)
         cfg.tile_rank, cfg.tile_world, cfg.tile_size = int(tile_rank), int(tile_world), int(tile_size)
-        cfg.flags = int(flags) | (FLAG_MOMENTS if moments or adaptive else 0) | (FLAG_ADAPTIVE if adaptive else 0)
+        cfg.flags = int(flags) | (FLAG_MOMENTS if moments or adaptive else 0) | (FLAG_ADAPTIVE if adaptive else 0) | \
+            (FLAG_SHARE_MOMENTS if share_moments else 0)
         cfg.basic_samples = int(basic_samples)
         cfg.basic_seed = int(basic_seed) & 0xFFFFFFFF
         cfg.sample_rank, cfg.sample_world = int(sample_rank), int(sample_world)
@@ -294,6 +301,19 @@ class Renderer:
         accumulation, one launch."""
         arr = (C.c_void_p * world)(*[C.c_void_p(int(x)) if x else C.c_void_p() for x in dpacked])
         self._ck(self._lib.pt_unpack_ranks(self._h, int(world), arr), "pt_unpack_ranks")
+
+    def pack_owned_stats(self, dptr: int):
+        """pack_owned with the moments (pt_pack_owned_stats; a Renderer(..., share_moments=True)):
+        owned_pixel_count() slots of 5 f32 (r, g, b, m1, m2) into device memory."""
+        self._ck(self._lib.pt_pack_owned_stats(self._h, C.c_void_p(dptr)), "pt_pack_owned_stats")
+
+    def unpack_ranks_stats(self, world: int, dpacked):
+        """unpack_ranks of pack_owned_stats buffers (pt_unpack_ranks_stats): ranks 1..world-1's running
+        means and moments into the accumulation and the moments plane, one launch. Every rank must have
+        rendered the same frames."""
+        arr = (C.c_void_p * max(world, 1))(*[C.c_void_p(int(x)) if x else C.c_void_p() for x in dpacked]) \
+            if dpacked is not None else None
+        self._ck(self._lib.pt_unpack_ranks_stats(self._h, int(world), arr), "pt_unpack_ranks_stats")
 
     def display_pack(self, dptr: int, limit: float = 1.5, gamma: float = 0.0):
         """This rank's owned pixels of the displayed frame (pass3 into an 8-bit window), 3 u8 each."""

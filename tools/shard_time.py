@@ -9,8 +9,14 @@ on the render stream, and the one-launch unpack of the other N - 1 ranks' buffer
 accumulation on the communication stream) but no collective (PT_SHARD_GATHER=0: render only).
 The N-GPU frame is this plus whatever of the xGMI gather itself does not overlap the next batch.
 
+--moments: the split of PT_FLAG_SHARE_MOMENTS contexts -- the running-mean update with the moments, and
+the 20-byte pack and unpack (pt_pack_owned_stats / pt_unpack_ranks_stats) in place of the 12-byte ones;
+against the same run without it, the per-batch cost of gathering the moments. --pair: both contexts of
+each world in one process, the plain one created first (--moments-first: second) -- creation order alone
+moves these figures by a few per cent, so the pair is measured in both orders and like compared with like.
+
     [PT_VARIANT=<tuning build>] [PT_BATCH=b | PT_BATCH_MUL=m] [PT_SHARD_FRAMES=K] [PT_SHARD_FLAGS=f]
-        python tools/shard_time.py [config] [N ...]
+        python tools/shard_time.py [--moments | --pair [--moments-first]] [config] [N ...]
 """
 import json
 import sys
@@ -24,8 +30,13 @@ import opengl_ray_tracing_amd  # noqa: E402,F401
 
 
 def main():
-    cfg_name = sys.argv[1] if len(sys.argv) > 1 else "c2"
-    worlds = [int(x) for x in sys.argv[2:]] or [1, 2, 4, 8]
+    argv = [x for x in sys.argv[1:] if not x.startswith("--")]
+    cfg_name = argv[0] if argv else "c2"
+    worlds = [int(x) for x in argv[1:]] or [1, 2, 4, 8]
+    # the contexts of each world, in creation order: plain, --moments, or --pair's two
+    kinds = [False, True] if "--pair" in sys.argv else ["--moments" in sys.argv]
+    if "--moments-first" in sys.argv:
+        kinds = kinds[::-1]
     import os
 
     import torch  # noqa: F401  (one HIP runtime with torch, as in bench.py)
@@ -39,50 +50,62 @@ def main():
     mul = int(os.environ.get("PT_BATCH_MUL", "0"))  # frames per launch = mul x N (overrides PT_BATCH)
     from opengl_ray_tracing_amd.distributed import FrameGather
     with_gather = os.environ.get("PT_SHARD_GATHER", "1") != "0"
-    for n in worlds:
-        with Renderer(cfg.width, cfg.height, cfg.integrator, max_bounce=cfg.max_bounce, tile_rank=0,
-                      tile_world=n, frame_batch=mul * n if mul else batch,
-                      flags=int(os.environ.get("PT_SHARD_FLAGS", "0"), 0)) as r:
-            r.upload_scene(tris, nodes)
-            r.upload_env(hdr)
-            g = FrameGather(r, 0, n, "cuda:0", mode="accum", proxy=True,
-                            overlap=os.environ.get("PT_SHARD_OVERLAP", "1") != "0") if with_gather and n > 1 else None
-            per = r.stats().frame_batch
 
-            def frames(first, k):  # bench.py's frames(): batches, each followed by the gather
-                while k > 0:
-                    m = min(per, k)
-                    r.render_frames(eye, rot, first, m)
-                    if g is not None:
-                        g()
-                    first += m
-                    k -= m
+    def measure(r, n, moments, order):
+        g = FrameGather(r, 0, n, "cuda:0", mode="accum", proxy=True, moments=moments,
+                        overlap=os.environ.get("PT_SHARD_OVERLAP", "1") != "0") if with_gather and n > 1 else None
+        per = r.stats().frame_batch
 
-            frames(0, 100)  # policy probe (tree, split, order) + warmup
-            r.synchronize()
-            if g is not None:
-                g.synchronize()
-            r.reset_stats()
-            K = int(os.environ.get("PT_SHARD_FRAMES", "200"))  # 20: the driver's bench line, from an idle GPU
-            if os.environ.get("SHARD_TRACE"):  # a PT_WAVE_TRACE build records the timed frames' waves only
-                os.environ["PT_WAVE_TRACE_FILE"] = f"{os.environ['SHARD_TRACE']}_{cfg_name}_n{n}.bin"
-            t0 = time.perf_counter()
-            frames(100, K)
-            t_sub = time.perf_counter()
-            r.synchronize()
-            if g is not None:
-                g.synchronize()
-            ms = 1e3 * (time.perf_counter() - t0) / K
-            os.environ.pop("PT_WAVE_TRACE_FILE", None)
-            submit_ms = 1e3 * (t_sub - t0) / K  # host time per pt_render_frame_async call
-            st = r.stats()
-        print(json.dumps({"variant": os.environ.get("PT_VARIANT", "base"), "config": cfg_name, "world": n, "rank0_ms_per_frame": round(ms, 4),
+        def frames(first, k):  # bench.py's frames(): batches, each followed by the gather
+            while k > 0:
+                m = min(per, k)
+                r.render_frames(eye, rot, first, m)
+                if g is not None:
+                    g()
+                first += m
+                k -= m
+
+        frames(0, 100)  # policy probe (tree, split, order) + warmup
+        r.synchronize()
+        if g is not None:
+            g.synchronize()
+        r.reset_stats()
+        K = int(os.environ.get("PT_SHARD_FRAMES", "200"))  # 20: the driver's bench line, from an idle GPU
+        if os.environ.get("SHARD_TRACE"):  # a PT_WAVE_TRACE build records the timed frames' waves only
+            os.environ["PT_WAVE_TRACE_FILE"] = f"{os.environ['SHARD_TRACE']}_{cfg_name}_n{n}.bin"
+        t0 = time.perf_counter()
+        frames(100, K)
+        t_sub = time.perf_counter()
+        r.synchronize()
+        if g is not None:
+            g.synchronize()
+        ms = 1e3 * (time.perf_counter() - t0) / K
+        os.environ.pop("PT_WAVE_TRACE_FILE", None)
+        submit_ms = 1e3 * (t_sub - t0) / K  # host time per pt_render_frame_async call
+        st = r.stats()
+        print(json.dumps({"variant": os.environ.get("PT_VARIANT", "base"), "config": cfg_name, "moments": moments,
+                          "created": order, "world": n, "rank0_ms_per_frame": round(ms, 4),
                           "frames": st.frames, "launches": st.launches, "frame_batch": st.frame_batch,
                           "kernel_ms_avg": round(st.kernel_ms_total / max(st.launches, 1), 4),
                           "host_submit_ms": round(submit_ms, 4),
                           "rays_per_frame": st.rays // max(st.frames, 1), "gather": g is not None,
                           "hw_queues": opengl_ray_tracing_amd.HW_QUEUES,
                           "frames_in_flight": st.frames_in_flight}), flush=True)
+
+    for n in worlds:
+        made = []
+        for moments in kinds:
+            r = Renderer(cfg.width, cfg.height, cfg.integrator, max_bounce=cfg.max_bounce, tile_rank=0,
+                         tile_world=n, frame_batch=mul * n if mul else batch,
+                         flags=int(os.environ.get("PT_SHARD_FLAGS", "0"), 0), moments=moments,
+                         share_moments=moments and n > 1)
+            r.upload_scene(tris, nodes)
+            r.upload_env(hdr)
+            made.append((r, moments))
+        for order, (r, moments) in enumerate(made):
+            measure(r, n, moments, order)
+        for r, _ in made:
+            r.close()
 
 
 if __name__ == "__main__":
