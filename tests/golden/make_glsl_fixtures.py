@@ -13,6 +13,8 @@ records what it computes:
                         accumulation (the shader's own main() over every pixel of a
                         160x90 frame, frames 0..n-1) as a sha256, plus 768 sampled
                         pixels of every frame
+  glsl/material_frames.json  the same for shaders O, D and IS on the many-material scene
+                        (tests/material_scene.py), 96x64, frames 0..2, 256 sampled pixels
 
 The shader text's GLSL transcendentals are glibc's double sin / cos / atan2 / asin /
 log / pow rounded to float (oracle/ref_glsl.cpp): the fixtures are the reference's
@@ -37,6 +39,27 @@ import ref_glsl  # noqa: E402
 OUT = Path(__file__).resolve().parent / "glsl"
 FUNC_N, FUNC_SEED = 100_000, 1
 SAMPLES = 768  # sampled pixels per frame (of 14 400)
+MATERIAL_SAMPLES = 256  # of 6 144
+MATERIAL_CASES = [("o_materials", 0, "lambert"), ("d_materials", 1, "disney"), ("is_materials", 2, "mis")]
+MATERIAL_FRAMES = 3
+
+
+def material_frames():
+    """Each shader's own main() on tests/material_scene.py's scene -> glsl/material_frames.json."""
+    import material_scene as ms
+    tris, nodes, hdr, cache, eye, rot = ms.build()[:6]
+    cases = []
+    for name, which, integ in MATERIAL_CASES:
+        outs = ref_glsl.ref_frames(which, tris, nodes, hdr, cache, eye, rot, MATERIAL_FRAMES, ms.W, ms.H)
+        idx = np.random.default_rng(3).choice(ms.W * ms.H, MATERIAL_SAMPLES, replace=False)
+        cases.append({"case": name, "shader": which, "integrator": integ, "scene": "material_scene",
+                      "camera": list(ms.CAMERA), "frames": MATERIAL_FRAMES, "width": ms.W, "height": ms.H,
+                      "digests": [ref_glsl.digest(o) for o in outs], "sample_index": idx.tolist(),
+                      "sample_last": ref_glsl.canonical(outs[-1].reshape(-1, 4)[idx]).tolist(),
+                      "sample_frames": [ref_glsl.canonical(o.reshape(-1, 4)[idx]).tolist() for o in outs]})
+        print(name, [d[:12] for d in cases[-1]["digests"]])
+    (OUT / "material_frames.json").write_text(
+        json.dumps({"generator": "oracle/ref_glsl.cpp ref_glsl_render", "cases": cases}) + "\n")
 
 
 def main():
@@ -66,6 +89,7 @@ def main():
                        "sample_frames": [ref_glsl.canonical(o.reshape(-1, 4)[idx]).tolist() for o in outs]})
         print(name, [d[:12] for d in frames[-1]["digests"]])
     (OUT / "frames.json").write_text(json.dumps({"generator": "oracle/ref_glsl.cpp ref_glsl_render", "cases": frames}) + "\n")
+    material_frames()
 
 
 if __name__ == "__main__":

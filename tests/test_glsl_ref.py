@@ -14,6 +14,10 @@ committed under tests/golden/glsl/ (tests/golden/make_glsl_fixtures.py):
     the teapot, IS on the ImportanceSampling scene, 160x90, frames 0..2 of the
     running mean -- the oracle's accumulation must equal it bit for bit.
 
+Those scenes have one or two materials. tests/test_material_scene.py does the same for O, D and
+IS on the many-material scene of tests/material_scene.py (tests/golden/glsl/material_frames.json,
+96x64, frames 0..2), where every Disney parameter and the emission decide the image.
+
 The GPU kernels are bit-exact against the oracle (tests/test_gpu_*.py), so this pins
 them to the reference text too. Where /root/reference is present the comparison is
 also run live on fresh inputs."""
