@@ -48,7 +48,10 @@ extern "C" {
                                 pt_download_tile_error); no existing struct changes;
                              13: the sample moments and adaptive sampling on screen-tile shares
                                 (PT_FLAG_SHARE_MOMENTS, pt_pack_owned_stats, pt_unpack_ranks_stats; pt_adaptive_update
-                                and pt_adaptive_status per share); no existing struct changes */
+                                and pt_adaptive_status per share); no existing struct changes;
+                             13, additive: ray queries with a range, on host arrays and on device memory
+                                (pt_trace_closest_range, pt_trace_occluded, pt_trace_closest_device,
+                                pt_trace_occluded_device): new symbols only, the version stays */
 
 /* error codes */
 #define PT_OK 0
@@ -272,6 +275,35 @@ int pt_build_bvh_device(pt_ctx* ctx, const float* tris, int nTriangles, int leaf
 /* Batch hitBVH (pass1.fsh:335-382; BVH/main.cpp:571 debug-ray query). rays =
  * n x 6 f32 (origin, direction); miss -> t = 2147483648.f, tri = -1. */
 int pt_trace_closest(pt_ctx* ctx, const float* rays, int n, float* t_out, int* tri_out);
+
+/* Ray queries with a range, on host arrays or on device memory: the closest hit below a bound, and the
+ * occlusion test (what a ray-casting library offers beside "closest": ambient occlusion, visibility
+ * between points, light baking on the uploaded scene). Both are stated against pt_trace_closest. With
+ * (t*, tri*) its result for ray k and b = tmax[k] (tmax NULL: every t* passes):
+ *   ranged closest: (t*, tri*) if tri* >= 0 && t* < b, else the miss values (2147483648.f, -1)
+ *   occluded:       1          if tri* >= 0 && t* < b, else 0
+ * The comparison is strict (b == t* is a miss), a NaN b is a miss, and so is b <= 0.0005f (hitTriangle's
+ * own lower bound, pass1.fsh:251-301). The walk starts its closest-hit bound at b, so a short range costs
+ * a short walk, and the occlusion test ends at the first hit it may report. The context's flags apply as
+ * they do to pt_trace_closest (PT_FLAG_NO_CULL, PT_FLAG_REFERENCE_TREE, PT_FLAG_COUNT_FETCHES; the
+ * default is the runtime's tree with the reference check). pt_frame_stats is not touched. With
+ * n_devices > 1 the queries run on device_ids[0]. PT_E_NOSCENE before pt_upload_scene; PT_E_INVALID for
+ * n < 0 or a NULL required pointer with n > 0; n == 0 is PT_OK and reads and writes nothing.
+ *
+ * The host forms are synchronous. Unlike pt_trace_closest they do not wait for the frames in flight:
+ * the queries have a traversal stack overflow area of their own and may overlap frames. */
+int pt_trace_closest_range(pt_ctx* ctx, const float* rays /* n x 6 f32 */, const float* tmax /* n f32, NULL: no bound */,
+                           int n, float* t_out, int* tri_out);
+int pt_trace_occluded(pt_ctx* ctx, const float* rays, const float* tmax, int n, uint8_t* occ_out /* n u8: 0 / 1 */);
+/* The device forms: every pointer is device memory of the context's device. Asynchronous, in stream
+ * order on the context's stream (pt_set_stream), after any pt_upload_scene issued before them; no host
+ * synchronisation, and no allocation after the first query of a scene (the overflow area is sized at
+ * first use and again after an upload that deepens the trees). Work another stream queued on d_rays or
+ * d_tmax is not ordered before the query, nor the query before another stream's reads of its results:
+ * set that stream with pt_set_stream, or synchronise first (as with pt_display_*). */
+int pt_trace_closest_device(pt_ctx* ctx, const void* d_rays /* n x 6 f32 */, const void* d_tmax /* n f32 or NULL */, int n,
+                            void* d_t /* n f32 */, void* d_tri /* n i32 */);
+int pt_trace_occluded_device(pt_ctx* ctx, const void* d_rays, const void* d_tmax, int n, void* d_occ /* n u8: 0 / 1 */);
 
 /* Accumulation buffer access (lastFrame texture, main.cpp:763-764). */
 int pt_download_accum(pt_ctx* ctx, float* accum_rgba);   /* host or device memory, width*height*4 f32 */

@@ -49,6 +49,7 @@ SOURCES = {
     "pt_regen.o": ("hip", CSRC / "pt_regen.hip", _FRAME),
     "pt_primary.o": ("hip", CSRC / "pt_primary.hip", _FRAME),
     "pt_guides.o": ("hip", CSRC / "pt_guides.hip", _FRAME),
+    "pt_query.o": ("hip", CSRC / "pt_query.hip", _FRAME),
     "pt_display.o": ("hip", CSRC / "pt_display.hip", _FRAME),
     "pt_basic.o": ("hip", CSRC / "pt_basic.hip", [*_DEV, INCLUDE / "pt_scene.h"]),
     "pt_diag.o": ("hip", CSRC / "pt_diag.hip", _DEV),

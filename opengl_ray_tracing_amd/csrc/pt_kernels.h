@@ -303,6 +303,20 @@ struct TraceParams {
   int ovfDepth;
 };
 
+// The ray queries on device memory (pt_query.hip queryKernel; pt_abi.h pt_trace_closest_device,
+// pt_trace_occluded_device): ray k's closest hit below tmax[k], or whether it has one
+struct QueryParams {
+  SceneView scene;
+  const float* rays;   // n x 6 (origin, direction)
+  const float* tmax;   // n bounds; null: none (PT_INF)
+  int n;
+  float* t;            // closest: n distances (a miss PT_INF) ...
+  int* tri;            // ... and uploaded triangle indices (a miss -1)
+  uint8_t* occ;        // occluded: n bytes, 0 / 1
+  int* ovf;            // the queries' own traversal stack overflow (per thread ovfDepth ints), may be null
+  int ovfDepth;
+};
+
 // BasicRayTracingWithC++ (pt_basic.hip basicKernel): one sample k of every pixel
 constexpr int BASIC_MAX_DEPTH = 31;  // pathTracing vertices kept for the fold (the reference's cutoff is 8)
 struct BasicParams {
@@ -441,6 +455,8 @@ bool regenTakesLists(int integrator, const RegenShape& r);  // the variant claim
 int regenLdsStack();
 int regenTop4(const RegenShape& r, int integrator);  // 4-wide nodes the wide regen kernel stages in LDS
 hipError_t launchTrace(const TraceParams& p, int grid, hipStream_t s, bool cull);
+// occluded: the any-hit query into p.occ, else the closest hit into p.t / p.tri
+hipError_t launchQuery(const QueryParams& p, int grid, hipStream_t s, bool occluded, bool cull);
 // Guide buffers (pt_guides.hip): the camera's first hit of every pixel centre, one lane per pixel,
 // one wave per 8x8 tile (a grid-stride loop over the tiles), three float4 planes
 struct GuideParams {

@@ -187,6 +187,19 @@ struct pt_ctx {
   int* d_tri = nullptr;
   size_t traceCap = 0;
   float* d_rgb = nullptr;
+  // The ray queries on device memory (pt_trace_closest_device, pt_trace_occluded_device and their host
+  // forms): their own stack overflow area, sized at first use for the largest grid a query launches and
+  // for the tree depth of the scene (again after an upload that deepens it), so a query
+  // never aliases a frame in flight (d_ovf) and allocates nothing in the steady state. queryDone is
+  // recorded behind every query: a query on another stream (pt_set_stream since) waits for it -- the
+  // area is one query's at a time -- and so does a resize.
+  int* d_queryOvf = nullptr;
+  size_t queryOvfInts = 0;
+  hipEvent_t queryDone = nullptr;
+  hipStream_t queryStream = nullptr;  // the stream queryDone was last recorded on
+  bool queryIssued = false;
+  float* d_queryStage = nullptr;      // the host forms' staging: rays, bounds and results of one call
+  size_t queryStageRays = 0;
   // guide buffers of the last pt_render_guides (valid for the scene version they were traced in) and
   // the denoiser's images: two ping-pong colour planes, their tone-mapped planes, and the
   // image the last pt_denoise wrote (one of the two, or the caller's)

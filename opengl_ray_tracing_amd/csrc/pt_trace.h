@@ -288,13 +288,18 @@ __device__ __forceinline__ bool isLeafRef(int ref) { return ref < 0 && ref != RE
 //
 // TIES: *tie is set when a lane meets a triangle at exactly its current closest
 // t (the visiting order decides such ties; see refReachable).
+//
+// BOUNDED (the ray queries, pt_query.hip): the closest-hit bound starts at `bound` instead of PT_INF, so
+// only triangles with t < bound can win, and among them the same least-t, first-in-order one does. A
+// compile-time switch: without it `bound` is not read, and the frame kernels' walks are what they were.
 template <bool ANYHIT, bool CULL, bool COUNT, class StackType, bool LDSTOP = false, bool TIES = false,
-          int KIND = NODE_EXACT>
+          int KIND = NODE_EXACT, bool BOUNDED = false>
 __device__ __forceinline__ int traceRay(const SceneView& S, V3 o, V3 d, float& tOut, StackType& st, Counters& C,
-                                        bool anyRT = false, const float4* top = nullptr, bool* tie = nullptr) {
+                                        bool anyRT = false, const float4* top = nullptr, bool* tie = nullptr,
+                                        float bound = PT_INF) {
   V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
   const FusedRay fr = fusedRay(o, inv);  // NODE_FUSED
-  float tbest = PT_INF;
+  float tbest = BOUNDED ? bound : PT_INF;
   int best = -1;
   int ref = S.rootRef;   // next item in visiting order (REF_NONE only when the stack is empty too)
   int leaf = REF_NONE;   // parked leaf, precedes ref
@@ -439,13 +444,14 @@ __device__ __forceinline__ void loadNode4Lds(const float4* tree, int k, float4& 
   const float4* n = tree + W4_LDS_F4 * k;
   lx = n[0], ly = n[1], lz = n[2], hx = n[3], hy = n[4], hz = n[5], rf = n[6];
 }
-template <bool CULL, class StackType, bool LDSTOP>
+// (BOUNDED / bound: as traceRay's)
+template <bool CULL, class StackType, bool LDSTOP, bool BOUNDED = false>
 __device__ __forceinline__ int traceRay4(const SceneView& S, V3 o, V3 d, float& tOut, StackType& st, Counters& C,
-                                         bool anyRT, const float4* top, bool* tie) {
+                                         bool anyRT, const float4* top, bool* tie, float bound = PT_INF) {
   const V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
   const FusedRay fr = fusedRay(o, inv);
   const f32x2 sx = {fr.inv.x, fr.noi.x}, sy = {fr.inv.y, fr.noi.y}, sz = {fr.inv.z, fr.noi.z};
-  float tbest = PT_INF;
+  float tbest = BOUNDED ? bound : PT_INF;
   int best = -1;
   int ref = S.f4Root;
   int leaf = REF_NONE;
@@ -1053,8 +1059,8 @@ __device__ __forceinline__ void finishHit(const SceneView& S, int tri, V3 o, V3 
 
 // ------------------------------------------------------------ queries
 // Closest-hit and shadow queries of one lane over the scene, with the reference's results whichever
-// tree is walked: the megakernel's integrators, the batch query (pt_trace_closest) and the guide
-// buffers (pt_guides.hip) share it.
+// tree is walked: the megakernel's integrators, the batch query (pt_trace_closest), the guide
+// buffers (pt_guides.hip) and the ray queries (pt_query.hip) share it.
 template <bool CULL, bool COUNT>
 struct Tracer {
   const SceneView& S;
@@ -1129,6 +1135,65 @@ struct Tracer {
     }
     if (anyhit) return occluded(o, d) ? 0 : -1;
     return trace(o, d, t);
+  }
+  // The ray queries' forms (pt_query.hip; pt_abi.h pt_trace_closest_device, pt_trace_occluded_device): trace()
+  // and occluded() with the closest-hit bound starting at b (b <= PT_INF, not a NaN) instead of PT_INF, a
+  // walk's BOUNDED switch. refReachable's argument holds under a bound: the runtime tree's walk meets every
+  // triangle the ray hits before b, so its winner (least t < b, no tie met) is the reference's bounded winner
+  // iff the reference reaches it; a tie (a first candidate at exactly b is flagged as one too, which only
+  // costs a retrace) or an unreachable winner retraces in the reference order with the same bound; a miss
+  // stands. An any-hit result stands when its triangle is reachable: the reference's closest t is then no
+  // larger, so it is below b as well.
+  __device__ __forceinline__ int traceBounded(V3 o, V3 d, float b, float& t) {
+    if (PT_WIDE4 && !COUNT && S.fast) {
+      bool tie = false;
+      int tri = traceRay4<CULL, Stack, (PT_WIDE4 == 2), true>(S, o, d, t, st, C, false, top, &tie, b);
+      if (tie || (tri >= 0 && !refReachable(S, tri, o, d, t))) {
+        C.rays--;
+        tri = traceRay<false, CULL, false, Stack, false, false, NODE_EXACT, true>(S, o, d, t, st, C, false, nullptr,
+                                                                                  nullptr, b);
+      }
+      return tri;
+    }
+    if (!COUNT && S.fast) {
+      bool tie = false;
+      const SceneView F = fastView(S);
+      const int pos = traceRay<false, CULL, false, Stack, (LDS_NODES > 0), true, FAST_KIND, true>(F, o, d, t, st, C,
+                                                                                                  false, top, &tie, b);
+      int tri = pos >= 0 ? S.fastTri[pos] : -1;
+      if (tie || (tri >= 0 && !refReachable(S, tri, o, d, t))) {
+        C.rays--;
+        tri = traceRay<false, CULL, false, Stack, false, false, NODE_EXACT, true>(S, o, d, t, st, C, false, nullptr,
+                                                                                  nullptr, b);
+      }
+      return tri;
+    }
+    return traceRay<false, CULL, COUNT, Stack, (LDS_NODES > 0), false, NODE_EXACT, true>(S, o, d, t, st, C, false, top,
+                                                                                         nullptr, b);
+  }
+  __device__ __forceinline__ bool occludedBounded(V3 o, V3 d, float b) {
+    float t;
+    if (PT_WIDE4 && !COUNT && S.fast) {
+      bool tie = false;
+      const int tri = traceRay4<CULL, Stack, (PT_WIDE4 == 2), true>(S, o, d, t, st, C, true, top, &tie, b);
+      if (tri < 0) return false;
+      if (refReachable(S, tri, o, d, t)) return true;
+      C.rays--;
+      return traceRay<true, CULL, false, Stack, false, false, NODE_EXACT, true>(S, o, d, t, st, C, false, nullptr,
+                                                                                nullptr, b) >= 0;
+    }
+    if (!COUNT && S.fast) {
+      const SceneView F = fastView(S);
+      const int pos = traceRay<true, CULL, false, Stack, (LDS_NODES > 0), false, FAST_KIND, true>(F, o, d, t, st, C,
+                                                                                                  false, top, nullptr, b);
+      if (pos < 0) return false;
+      if (refReachable(S, S.fastTri[pos], o, d, t)) return true;
+      C.rays--;
+      return traceRay<true, CULL, false, Stack, false, false, NODE_EXACT, true>(S, o, d, t, st, C, false, nullptr,
+                                                                                nullptr, b) >= 0;
+    }
+    return traceRay<true, CULL, false, Stack, (LDS_NODES > 0), false, NODE_EXACT, true>(S, o, d, t, st, C, false, top,
+                                                                                        nullptr, b) >= 0;
   }
 };
 

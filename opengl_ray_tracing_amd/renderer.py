@@ -135,6 +135,7 @@ class Renderer:
         self._h = h
         self.width, self.height = cfg.width, cfg.height
         self.integrator = cfg.integrator
+        self.device = cfg.device_id  # the GPU the context's buffers live on (a device group's first)
         self.tile_rank, self.tile_world = cfg.tile_rank, cfg.tile_world
         self.sample_rank, self.sample_world = cfg.sample_rank, cfg.sample_world
 
@@ -242,6 +243,113 @@ class Renderer:
                  "pt_trace_closest")
         return t, tri
 
+    @staticmethod
+    def _rays_tmax(rays, tmax):
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        b = None if tmax is None else np.ascontiguousarray(tmax, np.float32).reshape(-1)
+        if b is not None and b.size != r.shape[0]:
+            raise ValueError(f"tmax has {b.size} entries for {r.shape[0]} rays")
+        return r, b
+
+    def trace_closest_range(self, rays: np.ndarray, tmax=None):
+        """trace_closest with a bound per ray (pt_trace_closest_range): (t, tri) of the closest hit with
+        t < tmax[k], else the miss values (2147483648.0, -1); tmax None: no bound. Synchronous, and it
+        does not wait for frames in flight."""
+        r, b = self._rays_tmax(rays, tmax)
+        n = r.shape[0]
+        t = np.empty(n, np.float32)
+        tri = np.empty(n, np.int32)
+        self._ck(self._lib.pt_trace_closest_range(self._h, _fp(r), None if b is None else _fp(b), n, _fp(t),
+                                                  tri.ctypes.data_as(_native.c_int_p)), "pt_trace_closest_range")
+        return t, tri
+
+    def trace_occluded(self, rays: np.ndarray, tmax=None) -> np.ndarray:
+        """The occlusion test (pt_trace_occluded): uint8 per ray, 1 when it hits anything at t < tmax[k]
+        (tmax None: anywhere), else 0. Synchronous."""
+        r, b = self._rays_tmax(rays, tmax)
+        n = r.shape[0]
+        occ = np.empty(n, np.uint8)
+        self._ck(self._lib.pt_trace_occluded(self._h, _fp(r), None if b is None else _fp(b), n,
+                                             occ.ctypes.data_as(C.POINTER(C.c_uint8))), "pt_trace_occluded")
+        return occ
+
+    def _query_args(self, what, n, specs):
+        """The device queries' arguments: specs = [(name, value, dtype name, elements per ray, required)].
+        Every value is a raw device pointer (an int; then n is required) or a torch tensor -- contiguous,
+        on the context's device, of that dtype and size -- else ValueError. Returns (n, [pointers],
+        torch module or None when only raw pointers came)."""
+        torch = None
+        tensors = [v for _, v, _, _, _ in specs if v is not None and not isinstance(v, (int, np.integer))]
+        if tensors:
+            import torch
+        for name, v, dt, per, _ in specs:
+            if v is None or isinstance(v, (int, np.integer)):
+                continue
+            if not torch.is_tensor(v):
+                raise ValueError(f"{what}: {name} must be a device pointer (int) or a torch tensor, not {type(v).__name__}")
+            if not v.is_cuda or v.device.index != self.device:
+                raise ValueError(f"{what}: {name} is on {v.device}, the context renders on GPU {self.device}")
+            if v.dtype != getattr(torch, dt):
+                raise ValueError(f"{what}: {name} must be {dt}, not {v.dtype}")
+            if not v.is_contiguous():
+                raise ValueError(f"{what}: {name} must be contiguous")
+            if v.numel() % per:
+                raise ValueError(f"{what}: {name} has {v.numel()} elements, not a multiple of {per}")
+            if n is None and name == "rays":
+                n = v.numel() // per
+        if n is None:
+            raise ValueError(f"{what}: n is required with raw device pointers")
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"{what}: n must be >= 0")
+        ptrs = []
+        for name, v, dt, per, required in specs:
+            if v is None:
+                if required and n > 0:
+                    raise ValueError(f"{what}: {name} is required")
+                ptrs.append(None)
+            elif isinstance(v, (int, np.integer)):
+                ptrs.append(C.c_void_p(int(v)))
+            else:
+                if v.numel() != n * per:
+                    raise ValueError(f"{what}: {name} has {v.numel()} elements for {n} rays ({per} each)")
+                ptrs.append(C.c_void_p(v.data_ptr()))
+        return n, ptrs, torch
+
+    def trace_closest_device(self, rays, tmax=None, out_t=None, out_tri=None, n=None):
+        """trace_closest_range on device memory (pt_trace_closest_device): asynchronous, in stream order on
+        the context's stream (set_stream), without a copy. rays (n x 6 float32), tmax (n float32 or None),
+        out_t (n float32) and out_tri (n int32) are raw device pointers (ints, with n) or torch tensors --
+        contiguous, on the context's device, of those dtypes: anything else raises ValueError. With tensor
+        rays, outputs not given are allocated on the current torch stream's device. Returns (out_t, out_tri)
+        as given or allocated. What produces the rays and what reads the results must be ordered with the
+        context's stream: hand it the producing stream with set_stream, or synchronise."""
+        what = "trace_closest_device"
+        specs = [("rays", rays, "float32", 6, True), ("tmax", tmax, "float32", 1, False)]
+        n, _, torch = self._query_args(what, n, specs)
+        if torch is not None and torch.is_tensor(rays):
+            if out_t is None:
+                out_t = torch.empty(n, dtype=torch.float32, device=rays.device)
+            if out_tri is None:
+                out_tri = torch.empty(n, dtype=torch.int32, device=rays.device)
+        specs += [("out_t", out_t, "float32", 1, True), ("out_tri", out_tri, "int32", 1, True)]
+        n, p, _ = self._query_args(what, n, specs)
+        self._ck(self._lib.pt_trace_closest_device(self._h, p[0], p[1], n, p[2], p[3]), "pt_trace_closest_device")
+        return out_t, out_tri
+
+    def trace_occluded_device(self, rays, tmax=None, out=None, n=None):
+        """trace_occluded on device memory (pt_trace_occluded_device): as trace_closest_device, with one
+        output of n uint8 (0 / 1). Returns out as given or allocated."""
+        what = "trace_occluded_device"
+        specs = [("rays", rays, "float32", 6, True), ("tmax", tmax, "float32", 1, False)]
+        n, _, torch = self._query_args(what, n, specs)
+        if out is None and torch is not None and torch.is_tensor(rays):
+            out = torch.empty(n, dtype=torch.uint8, device=rays.device)
+        specs += [("out", out, "uint8", 1, True)]
+        n, p, _ = self._query_args(what, n, specs)
+        self._ck(self._lib.pt_trace_occluded_device(self._h, p[0], p[1], n, p[2]), "pt_trace_occluded_device")
+        return out
+
     def build_bvh_device(self, tris: np.ndarray, leaf_size: int = 4):
         """pt_build_bvh_device: the GPU binned-SAH tree over tris (n x 36 f32) in the reference's
         node encoding. Returns (nodes (m x 12 f32, dummy node 0, root 1), order (n int32: input
@@ -343,6 +451,12 @@ class Renderer:
                  "pt_download_guides")
         out["tri"] = out["nrm_tri"][..., 3].view(np.int32)
         return out
+
+    def guides_into(self, pos_t: int | None = None, nrm_tri: int | None = None, albedo: int | None = None):
+        """Copy guide planes (H x W x 4 f32 each) into device memory at the given pointers (pt_download_guides
+        with device destinations: stream-ordered, synchronous), for a consumer that stays on the GPU."""
+        p = [C.cast(C.c_void_p(x), _native.c_float_p) if x else None for x in (pos_t, nrm_tri, albedo)]
+        self._ck(self._lib.pt_download_guides(self._h, *p), "pt_download_guides")
 
     def guides_device_ptrs(self):
         p = [C.c_void_p() for _ in range(3)]
