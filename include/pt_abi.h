@@ -51,7 +51,9 @@ extern "C" {
                                 and pt_adaptive_status per share); no existing struct changes;
                              13, additive: ray queries with a range, on host arrays and on device memory
                                 (pt_trace_closest_range, pt_trace_occluded, pt_trace_closest_device,
-                                pt_trace_occluded_device): new symbols only, the version stays */
+                                pt_trace_occluded_device): new symbols only, the version stays;
+                             13, additive: geometry updated in place (pt_update_geometry,
+                                pt_update_geometry_device, pt_download_node_boxes): new symbols only */
 
 /* error codes */
 #define PT_OK 0
@@ -201,6 +203,38 @@ int pt_abi_version(void);  /* PT_ABI_VERSION of the loaded library */
  * Triangle_encoded (main.cpp:51-60); nodes = nNodes x 12 f32 exactly as
  * BVHNode_encoded (main.cpp:69-73) including the dummy node 0, root at 1. */
 int pt_upload_scene(pt_ctx* ctx, const float* tris, int nTriangles, const float* nodes, int nNodes);
+
+/* Geometry updated in place: a deforming or moving object without a new pt_upload_scene (whose host
+ * re-layout, copies and caller-side tree build cost many frames). New positions and shading normals for
+ * the triangles of the last pt_upload_scene, same count, same order: record i = p1 p2 p3 n1 n2 n3
+ * (Triangle_encoded floats 0..17), `stride` floats apart (>= 18; 36 = a whole Triangle_encoded array,
+ * whose floats 18..35 are ignored: materials stay). The uploaded tree keeps its topology; every reachable
+ * node's box becomes the exact bounds of its triangles (leaves) / of its children (internal nodes), with
+ * the reference's min / max (b < a ? b : a, a < b ? b : a), triangles in index order, the left child
+ * before the right: the boxes the reference's builders store for that topology (tests/refit_ref.py
+ * restates it; an internal node without children keeps its box). The context is then what
+ * pt_upload_scene(tris', nodes') would have made it, tris' = the old records with floats 0..17 replaced,
+ * nodes' = the old nodes with those boxes: images, query results and counters are bit for bit a fresh
+ * upload's. The runtime's own tree is rebuilt on the GPU (a scene whose upload left it on the uploaded
+ * tree alone stays there). Everything pt_upload_scene invalidates is invalidated (guides, camera-ray
+ * bins, the temporal history, the moments and adaptive state, the measured launch policies): restart
+ * at frameCounter 0. pt_frame_stats.upload_ms and accel_* describe the update. Returns when the scene is
+ * ready; waits for the frames and queries in flight first. Memory: every uploaded scene keeps its nodes'
+ * boxes on the device (32 bytes per node, what the refit writes and pt_download_node_boxes reads), also a
+ * scene that never updates or has no runtime tree; the update's own tables (8 bytes per node, 8 per
+ * device wide node, 4 per reachable node) and the host form's vertex staging (72 bytes per triangle) are
+ * allocated at the first update of a scene.
+ * PT_E_NOSCENE before pt_upload_scene and on a PT_BASIC_CPU_COMPAT context; PT_E_INVALID for a NULL
+ * pointer, nTriangles != the uploaded count, stride < 18, a PT_FLAG_HOST_ACCEL context (that flag keeps
+ * the GPU builder out) and the device form with n_devices > 1 (the host form updates every device).
+ * Not part of this: adding, removing or re-sorting triangles, and material changes (pt_upload_scene). */
+int pt_update_geometry(pt_ctx* ctx, const float* verts, int nTriangles, int stride);
+/* the same from device memory of the context's device, read in stream order on the context's stream
+ * (pt_set_stream): vertices animated on the GPU need no trip through the host */
+int pt_update_geometry_device(pt_ctx* ctx, const void* d_verts, int nTriangles, int stride);
+/* diagnostic: the uploaded tree's current boxes, nNodes x 6 f32 (lo, hi) by reference node id; entries
+ * of unreachable nodes are unspecified. Synchronous. */
+int pt_download_node_boxes(pt_ctx* ctx, float* boxes);
 
 /* Upload the HDR environment (replaces hdrMap/hdrCache textures,
  * ImportanceSampling_LowDiscrepancySequence/main.cpp:843-853). hdr = w x h x 3

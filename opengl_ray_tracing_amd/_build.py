@@ -55,6 +55,7 @@ SOURCES = {
     "pt_diag.o": ("hip", CSRC / "pt_diag.hip", _DEV),
     "pt_envcache.o": ("hip", CSRC / "pt_envcache.hip", _DEV),
     "pt_build.o": ("hip", CSRC / "pt_build.hip", [CSRC / "pt_kernels.h"]),
+    "pt_refit.o": ("hip", CSRC / "pt_refit.hip", [CSRC / "pt_kernels.h"]),
     "pt_denoise.o": ("hip", CSRC / "pt_denoise.hip", [CSRC / "pt_atrous.h", *_DEV]),
     "pt_temporal.o": ("hip", CSRC / "pt_temporal.hip", _DEV),
     "pt_variance.o": ("hip", CSRC / "pt_variance.hip", [CSRC / "pt_atrous.h", *_DEV]),

@@ -99,6 +99,9 @@ SIGNATURES = {
     "pt_destroy": (None, [C.c_void_p]),
     "pt_last_error": (C.c_char_p, [C.c_void_p]),
     "pt_upload_scene": (C.c_int, [C.c_void_p, c_float_p, C.c_int, c_float_p, C.c_int]),
+    "pt_update_geometry": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int]),
+    "pt_update_geometry_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "pt_download_node_boxes": (C.c_int, [C.c_void_p, c_float_p]),
     "pt_upload_env": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, c_float_p]),
     "pt_upload_shapes": (C.c_int, [C.c_void_p, c_double_p, C.c_int]),
     "pt_download_basic_image": (C.c_int, [C.c_void_p, c_double_p]),

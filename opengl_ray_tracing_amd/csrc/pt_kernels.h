@@ -405,6 +405,36 @@ void freeAccelBuild(AccelBuild& a);
 hipError_t collapseWide4Device(const BuildNode* nodes, int nNodes, int leafSize, float inflate, float inflateRelAbs,
                                float4** out, int* rootRef, int* nDev, int* depth, hipStream_t s);
 
+// New vertex positions in place (pt_refit.hip, pt_abi.h pt_update_geometry): the geometry, pair and
+// shading records rewritten from the caller's vertex records, the uploaded tree's boxes refitted
+// bottom-up into refBox, and the uploaded tree's wide records and the triangles' leaf boxes rewritten
+// from them. The topology comes from the upload (pt_runtime.cpp makeRefit): the tables below are
+// device memory, made at the first update of a scene.
+struct RefitTables {
+  int2* topo = nullptr;       // per reference node: internal (left, right), 0 = absent; leaf (first triangle, -count)
+  int* byHeight = nullptr;    // the reachable nodes, leaves (height 0) first, then by height
+  int* heightStart = nullptr; // heights + 1 offsets into byHeight
+  int2* devKids = nullptr;    // per device wide node: its children's reference ids (0 = absent)
+  int heights = 0;            // heights of the reachable tree (a root leaf: 1)
+  int tailFrom = 0;           // the one-block tail walks heights tailFrom .. heights - 1
+  bool ready = false;
+};
+constexpr int REFIT_TAIL = 1024;  // threads of the tail's block: most nodes of a height it takes over from the launches
+struct RefitParams {
+  const float* verts;  // record i at verts + i * stride: p1 p2 p3 n1 n2 n3
+  int stride;
+  int nTri, nDevNodes;
+  float4* geo;
+  float4* pairs;
+  float4* hitRec;
+  float4* bvh;
+  float4* refBox;
+  float4* leafBox;     // null: the scene has no runtime tree
+};
+// hostStart: the tables' heightStart on the host (heights + 1 entries); ev (nullable): 4 events recorded
+// before the records, the refit, the re-encode and after it
+hipError_t launchRefit(const RefitParams& p, const RefitTables& t, const int* hostStart, hipEvent_t* ev, hipStream_t s);
+
 // calculateHdrCache on the device (pt_envcache.hip); scratch: 2*w*h + 2*w + 1 floats
 hipError_t launchHdrCache(const float* hdr, int w, int h, float4* cache, float* scratch, hipStream_t s);
 // hdr[k].w = cache[k].z, samp[k] = cache[k].xy (the Env render layout)

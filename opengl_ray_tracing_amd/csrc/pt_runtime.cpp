@@ -276,6 +276,8 @@ int pt_create(pt_ctx** out, const pt_config* cfg) {
   return PT_OK;
 }
 
+static void freeRefit(pt_ctx* ctx);
+
 void pt_destroy(pt_ctx* ctx) {
   if (!ctx) return;
   destroyGroup(ctx);
@@ -284,6 +286,7 @@ void pt_destroy(pt_ctx* ctx) {
   dfree(ctx->d_geo); dfree(ctx->d_hit); dfree(ctx->d_mats); dfree(ctx->d_bvh); dfree(ctx->d_pairs);
   dfree(ctx->d_fbvh); dfree(ctx->d_fbvh4); dfree(ctx->d_fpairs); dfree(ctx->d_fastTri);
   dfree(ctx->d_refParent); dfree(ctx->d_refBox); dfree(ctx->d_leafBox);
+  freeRefit(ctx);
   dfree(ctx->d_hdr); dfree(ctx->d_cache); dfree(ctx->d_hdr8); dfree(ctx->d_cache4); dfree(ctx->d_shapes);
   dfree(ctx->d_cacheRow); dfree(ctx->d_cacheY); dfree(ctx->d_trig); dfree(ctx->d_light);
   dfree(ctx->d_basicImg); dfree(ctx->d_stream); dfree(ctx->d_offsets); dfree(ctx->d_overruns);
@@ -337,6 +340,7 @@ static inline void nrm3(const float* a, const float* b, const float* c, float N[
 // its boxes).
 struct WideTree {
   std::vector<float4> bvh;
+  std::vector<int> ids;  // device id -> node id
   int rootRef = REF_NONE, nDev = 0, depth = 0;
 };
 
@@ -438,6 +442,7 @@ static std::string encodeWideTree(const float* nodes, int nNodes, int nTri, floa
   if (!bad.empty()) return bad;
   out.nDev = (int)order.size();
   out.depth = depth;
+  out.ids = std::move(order);
   return "";
 }
 
@@ -584,6 +589,8 @@ struct SceneHost {
   std::vector<float4> geo, pairs;
   std::vector<float4> hit, mats;  // SceneView::hitRec / mats
   WideTree ref;
+  std::vector<int2> topo;         // the uploaded tree's topology (pt_kernels.h RefitTables::topo), reachable nodes
+  std::vector<float4> refBox;     // every reference node's box (lo, hi)
   // the runtime's own tree and the reference facts its results are checked against
   bool fast = false;
   bool deviceBuild = false;  // the tree itself is built on each device (pt_build.hip) by uploadScene
@@ -591,7 +598,7 @@ struct SceneHost {
   int accelNodes = 0;
   std::vector<float> accelRef;  // host build: its nodes in the reference encoding (encodeWide4)
   WideTree fastTree;
-  std::vector<float4> fpairs, refBox, leafBox;
+  std::vector<float4> fpairs, leafBox;
   std::vector<int> order, leafOf, parent;
 };
 
@@ -636,13 +643,7 @@ static void prepareAccel(const float* tris, int nTri, const float* nodes, int nN
       }
     }
   }
-  h.refBox.assign((size_t)nNodes * 2, make_float4(0, 0, 0, 0));
   h.leafBox.assign((size_t)nTri * 2, make_float4(0, 0, 0, 0));
-  for (int k = 0; k < nNodes; k++) {
-    const float* c = nodes + (size_t)k * 12;
-    h.refBox[2 * (size_t)k] = make_float4(c[6], c[7], c[8], 0.0f);
-    h.refBox[2 * (size_t)k + 1] = make_float4(c[9], c[10], c[11], 0.0f);
-  }
   const float inf = INFINITY;
   for (int i = 0; i < nTri; i++) {
     // lo.w holds the reference leaf's node id (int bits), so the reachability check reads one
@@ -732,6 +733,36 @@ static std::string prepareScene(const float* tris, int nTri, const float* nodes,
   std::string bad = encodeWideTree(nodes, nNodes, nTri, 0.0f, h.ref);
   if (!bad.empty()) return bad;
   buildPairs(h.geo, nullptr, nTri, h.pairs);
+  // what pt_update_geometry refits: every node's box, and the reachable tree's topology (a tree:
+  // encodeWideTree has rejected cycles)
+  h.refBox.assign((size_t)nNodes * 2, make_float4(0, 0, 0, 0));
+  for (int k = 0; k < nNodes; k++) {
+    const float* c = nodes + (size_t)k * 12;
+    h.refBox[2 * (size_t)k] = make_float4(c[6], c[7], c[8], 0.0f);
+    h.refBox[2 * (size_t)k + 1] = make_float4(c[9], c[10], c[11], 0.0f);
+  }
+  h.topo.assign(nNodes, make_int2(0, 0));
+  {
+    std::vector<int> st{1};
+    std::vector<char> seen(nNodes, 0);
+    while (!st.empty()) {
+      const int k = st.back();
+      st.pop_back();
+      if (seen[k]) continue;
+      seen[k] = 1;
+      const float* c = nodes + (size_t)k * 12;
+      if ((int)c[3] > 0) {
+        h.topo[k] = make_int2((int)c[4], -(int)c[3]);
+        continue;
+      }
+      int ch[2] = {(int)c[0], (int)c[1]};
+      for (int& x : ch) {
+        if (x <= 0 || x >= nNodes) x = 0;
+        if (x) st.push_back(x);
+      }
+      h.topo[k] = make_int2(ch[0], ch[1]);
+    }
+  }
   prepareAccel(tris, nTri, nodes, nNodes, h, hostBuild);
   return "";
 }
@@ -779,6 +810,67 @@ static int clearAdaptive(pt_ctx* ctx) {
   return PT_OK;
 }
 
+// The runtime's tree built on the device from the geometry records in d_geo (pt_build.hip) and collapsed
+// to 4-wide nodes there: pt_upload_scene's build and pt_update_geometry's rebuild. *built false: the
+// tree would have 2^24 nodes or more, and the context stays on the uploaded tree.
+static int buildRuntimeTree(pt_ctx* ctx, bool* built) {
+  *built = false;
+  const auto t0 = std::chrono::steady_clock::now();
+  AccelBuild ab;
+  hipError_t e = buildAccelDevice(ctx->d_geo, ctx->nTri, PT_ACCEL_LEAF, 1e-5f, 3e-5f, ab, ctx->stream);
+  if (e != hipSuccess) return fail(ctx, PT_E_HIP, std::string("device tree build: ") + hipGetErrorString(e));
+  if (ab.nNodes + 1 >= (1 << 24)) {  // as the host path: no runtime tree of 2^24 nodes or more
+    freeAccelBuild(ab);
+    return PT_OK;
+  }
+  // the 4-wide collapse, on the device too (the large-scene regen kernel's and the megakernel's tree)
+  float4* w4 = nullptr;
+  e = collapseWide4Device(ab.nodes, ab.nNodes, PT_ACCEL_LEAF, 1e-5f, 3e-5f, &w4, &ctx->f4Root, &ctx->f4nDev,
+                          &ctx->f4Depth, ctx->stream);
+  dfree(ab.nodes);
+  if (e != hipSuccess) {
+    freeAccelBuild(ab);
+    return fail(ctx, PT_E_HIP, std::string("device 4-wide collapse: ") + hipGetErrorString(e));
+  }
+  dfree(ctx->d_fbvh4);
+  ctx->d_fbvh4 = w4;
+  dfree(ctx->d_fbvh);
+  dfree(ctx->d_fpairs);
+  dfree(ctx->d_fastTri);
+  ctx->d_fbvh = ab.bvh;
+  ctx->d_fpairs = ab.pairs;
+  ctx->d_fastTri = ab.order;
+  ctx->fRoot = ab.rootRef;
+  ctx->fnDev = ab.nDev;
+  ctx->fDepth = ab.depth;
+  ctx->accelMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  ctx->accelDevice = 1;
+  ctx->accelNodes = ab.nNodes;
+  *built = true;
+  return PT_OK;
+}
+
+// the runtime tree and its 4-wide collapse are in place: the frames may walk them
+static void runtimeTreeReady(pt_ctx* ctx) {
+  ctx->fast4Ready = true;
+  // a visit pushes up to three children: the traversal stack needs 3 entries per wide level
+  ctx->maxStack = std::max(ctx->maxStack, 3 * ctx->f4Depth + 2);
+  ctx->sceneVersion++;  // camera-ray bins are rebuilt for the new triangles
+  ctx->maxStack = std::max(ctx->maxStack, ctx->fDepth + 1);
+  ctx->fastReady = true;
+}
+
+// pt_update_geometry's device tables and staging belong to one upload
+static void freeRefit(pt_ctx* ctx) {
+  dfree(ctx->refit.topo);
+  dfree(ctx->refit.byHeight);
+  dfree(ctx->refit.heightStart);
+  dfree(ctx->refit.devKids);
+  ctx->refit = RefitTables{};
+  ctx->refitStart.clear();
+  dfree(ctx->d_updVerts);
+}
+
 static int uploadScene(pt_ctx* ctx, const float* tris, const SceneHost& h) {
   if (int rc = syncStreams(ctx)) return rc;  // no frame in flight reads the buffers replaced here
   if (ctx->queryIssued) CK(hipEventSynchronize(ctx->queryDone));  // nor a ray query, whichever stream it is on
@@ -810,43 +902,17 @@ static int uploadScene(pt_ctx* ctx, const float* tris, const SceneHost& h) {
   ctx->accelDevice = -1;
   ctx->accelMs = 0.0f;
   ctx->accelNodes = ctx->accelDepth = 0;
+  // what pt_update_geometry starts from: the boxes on the device, the topology on the host
+  freeRefit(ctx);
+  ctx->refTopo = h.topo;
+  ctx->refOrder = h.ref.ids;
+  ctx->sceneFast = h.fast;
+  if ((rc = upload(ctx, &ctx->d_refBox, h.refBox))) return rc;
   if (!h.fast) return PT_OK;
-  if ((rc = upload(ctx, &ctx->d_refParent, h.parent)) ||
-      (rc = upload(ctx, &ctx->d_refBox, h.refBox)) || (rc = upload(ctx, &ctx->d_leafBox, h.leafBox)))
-    return rc;
+  if ((rc = upload(ctx, &ctx->d_refParent, h.parent)) || (rc = upload(ctx, &ctx->d_leafBox, h.leafBox))) return rc;
   if (h.deviceBuild) {
-    // the runtime's tree built here, from the geometry records just uploaded (pt_build.hip)
-    const auto t0 = std::chrono::steady_clock::now();
-    AccelBuild ab;
-    hipError_t e = buildAccelDevice(ctx->d_geo, h.nTri, PT_ACCEL_LEAF, 1e-5f, 3e-5f, ab, ctx->stream);
-    if (e != hipSuccess) return fail(ctx, PT_E_HIP, std::string("device tree build: ") + hipGetErrorString(e));
-    if (ab.nNodes + 1 >= (1 << 24)) {  // as the host path: no runtime tree of 2^24 nodes or more
-      freeAccelBuild(ab);
-      return PT_OK;
-    }
-    // the 4-wide collapse, on the device too (the large-scene regen kernel's and the megakernel's tree)
-    float4* w4 = nullptr;
-    e = collapseWide4Device(ab.nodes, ab.nNodes, PT_ACCEL_LEAF, 1e-5f, 3e-5f, &w4, &ctx->f4Root, &ctx->f4nDev,
-                            &ctx->f4Depth, ctx->stream);
-    dfree(ab.nodes);
-    if (e != hipSuccess) {
-      freeAccelBuild(ab);
-      return fail(ctx, PT_E_HIP, std::string("device 4-wide collapse: ") + hipGetErrorString(e));
-    }
-    dfree(ctx->d_fbvh4);
-    ctx->d_fbvh4 = w4;
-    dfree(ctx->d_fbvh);
-    dfree(ctx->d_fpairs);
-    dfree(ctx->d_fastTri);
-    ctx->d_fbvh = ab.bvh;
-    ctx->d_fpairs = ab.pairs;
-    ctx->d_fastTri = ab.order;
-    ctx->fRoot = ab.rootRef;
-    ctx->fnDev = ab.nDev;
-    ctx->fDepth = ab.depth;
-    ctx->accelMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    ctx->accelDevice = 1;
-    ctx->accelNodes = ab.nNodes;
+    bool built = false;
+    if ((rc = buildRuntimeTree(ctx, &built)) || !built) return rc;
   } else {
     if ((rc = upload(ctx, &ctx->d_fbvh, h.fastTree.bvh)) || (rc = upload(ctx, &ctx->d_fpairs, h.fpairs)) ||
         (rc = upload(ctx, &ctx->d_fastTri, h.order)))
@@ -869,12 +935,7 @@ static int uploadScene(pt_ctx* ctx, const float* tris, const SceneHost& h) {
     encodeWide4(an.data(), nn, h.nTri, 1e-5f, 3e-5f * scale, w4, ctx->f4Root, ctx->f4nDev, ctx->f4Depth);
     if ((rc = upload(ctx, &ctx->d_fbvh4, w4))) return rc;
   }
-  ctx->fast4Ready = true;
-  // a visit pushes up to three children: the traversal stack needs 3 entries per wide level
-  ctx->maxStack = std::max(ctx->maxStack, 3 * ctx->f4Depth + 2);
-  ctx->sceneVersion++;  // camera-ray bins are rebuilt for the new triangles
-  ctx->maxStack = std::max(ctx->maxStack, ctx->fDepth + 1);
-  ctx->fastReady = true;
+  runtimeTreeReady(ctx);
   return PT_OK;
 }
 
@@ -901,6 +962,172 @@ int pt_upload_scene(pt_ctx* ctx, const float* tris, int nTri, const float* nodes
   for (pt_ctx* m : members(ctx))
     if (int rc = uploadScene(m, tris, h)) return fromPeer(ctx, m, rc);
   ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PT_OK;
+}
+
+// ------------------------------------------------------------ geometry update (pt_refit.hip)
+// The device tables of the uploaded tree's topology, made at the scene's first update: the reachable
+// nodes sorted by height (a leaf 0, an internal node one more than its higher child), so that every
+// height is refitted after the ones below it, and each device wide node's children.
+static int makeRefit(pt_ctx* ctx) {
+  if (ctx->refit.ready) return PT_OK;
+  const std::vector<int2>& topo = ctx->refTopo;
+  const int nNodes = (int)topo.size();
+  std::vector<int> height(nNodes, -1), st{1};
+  int heights = 0;
+  while (!st.empty()) {
+    const int k = st.back();
+    const int2 tp = topo[k];
+    int below = -1;
+    bool wait = false;
+    if (tp.y >= 0)
+      for (int c : {tp.x, tp.y}) {
+        if (c <= 0) continue;
+        if (height[c] < 0) { st.push_back(c); wait = true; }
+        else below = std::max(below, height[c]);
+      }
+    if (wait) continue;
+    height[k] = below + 1;
+    heights = std::max(heights, height[k] + 1);
+    st.pop_back();
+  }
+  std::vector<int>& start = ctx->refitStart;
+  start.assign(heights + 1, 0);
+  for (int k = 1; k < nNodes; k++)
+    if (height[k] >= 0) start[height[k] + 1]++;
+  for (int h = 0; h < heights; h++) start[h + 1] += start[h];
+  std::vector<int> byHeight(start[heights]), at(start.begin(), start.end() - 1);
+  for (int k = 1; k < nNodes; k++)
+    if (height[k] >= 0) byHeight[at[height[k]]++] = k;
+  // launches while a height holds more nodes than the tail's block, then the tail
+  int tailFrom = heights;
+  while (tailFrom > 1 && start[tailFrom] - start[tailFrom - 1] <= REFIT_TAIL) tailFrom--;
+  std::vector<int2> kids(ctx->refOrder.size());
+  for (size_t id = 0; id < kids.size(); id++) kids[id] = topo[ctx->refOrder[id]];
+  RefitTables& t = ctx->refit;
+  int rc;
+  if ((rc = upload(ctx, &t.topo, topo)) || (rc = upload(ctx, &t.byHeight, byHeight)) ||
+      (rc = upload(ctx, &t.heightStart, start)) || (rc = upload(ctx, &t.devKids, kids)))
+    return rc;
+  t.heights = heights;
+  t.tailFrom = tailFrom;
+  t.ready = true;
+  return PT_OK;
+}
+
+// One context's update from nTri vertex records in its device memory; the caller has waited for the
+// frames and queries in flight. What uploadScene invalidates is invalidated here.
+static int updateOne(pt_ctx* ctx, const float* d_verts, int stride) {
+  ctx->policyKey++;
+  dropHistory(ctx);
+  if (int rc = dropMoments(ctx)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  if (int rc = makeRefit(ctx)) return rc;
+  RefitParams p;
+  p.verts = d_verts;
+  p.stride = stride;
+  p.nTri = ctx->nTri;
+  p.nDevNodes = ctx->nDevNodes;
+  p.geo = ctx->d_geo;
+  p.pairs = ctx->d_pairs;
+  p.hitRec = ctx->d_hit;
+  p.bvh = ctx->d_bvh;
+  p.refBox = ctx->d_refBox;
+  p.leafBox = ctx->sceneFast ? ctx->d_leafBox : nullptr;
+  // PT_UPDATE_TIMES (environment; tools/update_time.py): the device time of each step, on stderr
+  const bool timed = std::getenv("PT_UPDATE_TIMES") != nullptr;
+  struct StepEvents {  // destroyed on every way out
+    hipEvent_t ev[4] = {};
+    ~StepEvents() {
+      for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    }
+  } steps;
+  hipEvent_t* ev = steps.ev;
+  if (timed)
+    for (int k = 0; k < 4; k++) CK(hipEventCreate(&ev[k]));
+  CK(launchRefit(p, ctx->refit, ctx->refitStart.data(), timed ? ev : nullptr, ctx->stream));
+  ctx->maxStack = ctx->depth + 1;
+  ctx->fastReady = false;
+  ctx->fast4Ready = false;
+  ctx->accelDevice = -1;
+  ctx->accelMs = 0.0f;
+  ctx->accelNodes = ctx->accelDepth = 0;
+  ctx->sceneVersion++;  // guides and camera-ray bins of the old positions are stale, runtime tree or not
+  bool built = false;
+  if (ctx->sceneFast) {
+    if (int rc = buildRuntimeTree(ctx, &built)) return rc;
+  }
+  CK(hipStreamSynchronize(ctx->stream));
+  if (built) {
+    ctx->accelDepth = ctx->fDepth;
+    runtimeTreeReady(ctx);
+  }
+  if (timed) {
+    float ms[3] = {};
+    for (int k = 0; k < 3; k++) CK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+    std::fprintf(stderr, "pt_update_geometry: records %.4f refit %.4f reencode %.4f build %.4f ms, %d heights, tail from %d\n",
+                 ms[0], ms[1], ms[2], ctx->accelMs, ctx->refit.heights, ctx->refit.tailFrom);
+  }
+  return PT_OK;
+}
+
+static int updateArgs(pt_ctx* ctx, const void* verts, int nTri, int stride) {
+  if (!ctx || !verts) return PT_E_INVALID;
+  if (ctx->cfg.integrator == PT_BASIC_CPU_COMPAT || !ctx->d_bvh) return fail(ctx, PT_E_NOSCENE, "no scene");
+  if (nTri != ctx->nTri) return fail(ctx, PT_E_INVALID, "pt_update_geometry: nTriangles differs from the uploaded scene's");
+  if (stride < 18) return fail(ctx, PT_E_INVALID, "pt_update_geometry: stride < 18 floats");
+  if (ctx->cfg.flags & PT_FLAG_HOST_ACCEL)
+    return fail(ctx, PT_E_INVALID, "pt_update_geometry: not on a PT_FLAG_HOST_ACCEL context (the update builds on the GPU)");
+  return PT_OK;
+}
+
+static int updateWait(pt_ctx* ctx) {
+  if (int rc = syncStreams(ctx)) return rc;  // no frame in flight reads the buffers rewritten here
+  if (ctx->queryIssued) CK(hipEventSynchronize(ctx->queryDone));  // nor a ray query, whichever stream it is on
+  return PT_OK;
+}
+
+int pt_update_geometry(pt_ctx* ctx, const float* verts, int nTri, int stride) {
+  if (int rc = updateArgs(ctx, verts, nTri, stride)) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (pt_ctx* m : members(ctx)) {
+    if (int rc = updateWait(m)) return fromPeer(ctx, m, rc);
+    CK(hipSetDevice(m->cfg.device_id));
+    if (!m->d_updVerts) {
+      hipError_t e = hipMalloc(&m->d_updVerts, (size_t)nTri * 18 * sizeof(float));
+      if (e != hipSuccess) return fail(ctx, PT_E_NOMEM, "pt_update_geometry: vertex staging");
+    }
+    CK(hipMemcpy2DAsync(m->d_updVerts, 18 * sizeof(float), verts, (size_t)stride * sizeof(float), 18 * sizeof(float),
+                        (size_t)nTri, hipMemcpyHostToDevice, m->stream));
+    if (int rc = updateOne(m, m->d_updVerts, 18)) return fromPeer(ctx, m, rc);
+  }
+  ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PT_OK;
+}
+
+int pt_update_geometry_device(pt_ctx* ctx, const void* d_verts, int nTri, int stride) {
+  if (int rc = updateArgs(ctx, d_verts, nTri, stride)) return rc;
+  if (!ctx->peers.empty()) return fail(ctx, PT_E_INVALID, "pt_update_geometry_device: not on an n_devices > 1 context");
+  const auto t0 = std::chrono::steady_clock::now();
+  if (int rc = updateWait(ctx)) return rc;
+  if (int rc = updateOne(ctx, static_cast<const float*>(d_verts), stride)) return rc;
+  ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PT_OK;
+}
+
+int pt_download_node_boxes(pt_ctx* ctx, float* boxes) {
+  if (!ctx || !boxes) return PT_E_INVALID;
+  if (ctx->cfg.integrator == PT_BASIC_CPU_COMPAT || !ctx->d_refBox) return fail(ctx, PT_E_NOSCENE, "no scene");
+  CK(hipSetDevice(ctx->cfg.device_id));
+  std::vector<float4> b((size_t)ctx->nNodes * 2);
+  CK(hipMemcpyAsync(b.data(), ctx->d_refBox, b.size() * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < ctx->nNodes; k++) {
+    const float4 lo = b[2 * (size_t)k], hi = b[2 * (size_t)k + 1];
+    float* o = boxes + 6 * (size_t)k;
+    o[0] = lo.x; o[1] = lo.y; o[2] = lo.z; o[3] = hi.x; o[4] = hi.y; o[5] = hi.z;
+  }
   return PT_OK;
 }
 

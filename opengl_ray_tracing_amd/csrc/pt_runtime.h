@@ -95,6 +95,16 @@ struct pt_ctx {
   float uploadMs = 0.0f, accelMs = 0.0f;
   int accelDevice = -1, accelNodes = 0, accelDepth = 0;
   int rootRef = REF_NONE;
+  // pt_update_geometry: the uploaded tree's topology, kept on the host from the upload (8 bytes per
+  // node, 4 per device wide node); the device tables (pt_kernels.h RefitTables) and the staging of the
+  // host form's vertex records are made at the first update, so a context that never updates pays no
+  // device memory for them (d_refBox, the boxes the refit starts from, is uploaded with every scene)
+  std::vector<int2> refTopo;    // RefitTables::topo
+  std::vector<int> refOrder;    // device wide node id -> reference node id (encodeWideTree's order)
+  std::vector<int> refitStart;  // RefitTables::heightStart on the host
+  RefitTables refit;
+  float* d_updVerts = nullptr;  // nTri x 18 f32
+  bool sceneFast = false;       // the upload prepared a runtime tree (SceneHost::fast)
   int nTri = 0, nNodes = 0, depth = 0, maxStack = 0;
   size_t sceneBytes = 0;  // the scene's records on the device (pt_plan.h sceneBytes, largeScene)
   // env

@@ -159,6 +159,37 @@ class Renderer:
         t = np.ascontiguousarray(tris, np.float32).reshape(-1, 36)
         n = np.ascontiguousarray(nodes, np.float32).reshape(-1, 12)
         self._ck(self._lib.pt_upload_scene(self._h, _fp(t), t.shape[0], _fp(n), n.shape[0]), "pt_upload_scene")
+        self._n_nodes = n.shape[0]
+
+    def update_geometry(self, verts):
+        """New positions and shading normals for the uploaded triangles, in place (pt_update_geometry):
+        verts is (n, 18) -- p1 p2 p3 n1 n2 n3 per triangle -- or (n, 36), a whole Triangle_encoded array
+        whose materials are ignored; n the uploaded count, the uploaded order. The uploaded tree keeps its
+        topology and gets exact boxes, the runtime's tree is rebuilt on the GPU: the context is then what
+        upload_scene of the updated arrays would have made it. A numpy array is copied from the host; a
+        torch tensor -- float32, contiguous, on the context's device, else ValueError -- is read in place
+        in stream order on the context's stream (pt_update_geometry_device): hand the stream that
+        produced it to set_stream, or synchronise. Returns when the scene is ready; restart the
+        accumulation at frame_counter 0."""
+        what = "update_geometry"
+        if isinstance(verts, np.ndarray) or not hasattr(verts, "data_ptr"):
+            v = np.ascontiguousarray(verts, np.float32)
+            if v.ndim != 2 or v.shape[1] not in (18, 36):
+                raise ValueError(f"{what}: verts must be (n, 18) or (n, 36), not {v.shape}")
+            self._ck(self._lib.pt_update_geometry(self._h, _fp(v), v.shape[0], v.shape[1]), "pt_update_geometry")
+            return
+        if verts.dim() != 2 or verts.shape[1] not in (18, 36):
+            raise ValueError(f"{what}: verts must be (n, 18) or (n, 36), not {tuple(verts.shape)}")
+        n, stride = int(verts.shape[0]), int(verts.shape[1])
+        _, p, _ = self._query_args(what, n, [("verts", verts, "float32", stride, True)])
+        self._ck(self._lib.pt_update_geometry_device(self._h, p[0], n, stride), "pt_update_geometry_device")
+
+    def node_boxes(self) -> np.ndarray:
+        """Diagnostics (pt_download_node_boxes): the uploaded tree's current boxes, (nodes, 6) f32 -- lo,
+        hi by node id of the last upload_scene; entries of unreachable nodes are unspecified."""
+        out = np.empty((getattr(self, "_n_nodes", 0), 6), np.float32)
+        self._ck(self._lib.pt_download_node_boxes(self._h, _fp(out)), "pt_download_node_boxes")
+        return out
 
     def hdr_cache_device(self, hdr: np.ndarray) -> np.ndarray:
         """calculateHdrCache on this context's GPU, (h, w, 3) like scene.calculate_hdr_cache."""
