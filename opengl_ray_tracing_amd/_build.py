@@ -1,5 +1,7 @@
 """In-tree native build: libpt.so (HIP kernels + C-ABI runtime + host scene
-prep) for gfx950, and the test-only oracle (oracle/liboracle.so).
+prep) for gfx950, and the test-only oracle (oracle/liboracle.so). The host runtime
+is one g++ unit per subject (csrc/pt_runtime.h lists them; pt_scene_prep.cpp is the
+host-only scene preparation, which tests/native/scene_prep_check.cpp links too).
 
 The built shared objects stay in the source tree (git-ignored) so they travel
 to the GPU box with the repository snapshot.
@@ -43,6 +45,7 @@ CXX_FLAGS = ["-O2", "-fPIC", "-pthread", "-std=c++17", "-ffp-contract=off", "-fn
 _DEV = [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]
 _FRAME = [*_DEV, CSRC / "pt_frame.h", CSRC / "pt_trace.h"]  # pt_frame.h's device half includes pt_trace.h
 _HOST = [CSRC / "pt_runtime.h", CSRC / "pt_frame.h", CSRC / "pt_kernels.h", INCLUDE / "pt_abi.h", CSRC / "pt_rccl.h"]
+_PREP = [CSRC / "pt_scene_prep.h", CSRC / "pt_kernels.h"]  # the host-only scene preparation (no context, no HIP call)
 
 SOURCES = {
     "pt_kernels.o": ("hip", CSRC / "pt_kernels.hip", [*_FRAME, INCLUDE / "pt_scene.h"]),
@@ -60,8 +63,16 @@ SOURCES = {
     "pt_temporal.o": ("hip", CSRC / "pt_temporal.hip", _DEV),
     "pt_variance.o": ("hip", CSRC / "pt_variance.hip", [CSRC / "pt_atrous.h", *_DEV]),
     "pt_adaptive.o": ("hip", CSRC / "pt_adaptive.hip", _FRAME),
-    "pt_runtime.o": ("cxx", CSRC / "pt_runtime.cpp", [*_HOST, CSRC / "pt_plan.h", CSRC / "pt_accel.h", INCLUDE / "pt_scene.h",
-                                                       INCLUDE / "pt_fmath.h"]),
+    # the host runtime by subject (pt_runtime.h lists the files); the host-only scene preparation keeps
+    # -ffp-contract=off like the rest: its unit normal and plane offset round as the reference's do
+    "pt_context.o": ("cxx", CSRC / "pt_context.cpp", [*_HOST, CSRC / "pt_plan.h", INCLUDE / "pt_fmath.h"]),
+    "pt_scene_prep.o": ("cxx", CSRC / "pt_scene_prep.cpp", [*_PREP, CSRC / "pt_accel.h"]),
+    "pt_scene_upload.o": ("cxx", CSRC / "pt_scene_upload.cpp", [*_HOST, *_PREP, CSRC / "pt_plan.h"]),
+    "pt_env.o": ("cxx", CSRC / "pt_env.cpp", [*_HOST, INCLUDE / "pt_scene.h"]),
+    "pt_runtime.o": ("cxx", CSRC / "pt_runtime.cpp", [*_HOST, CSRC / "pt_plan.h"]),  # the frame path
+    "pt_queries.o": ("cxx", CSRC / "pt_queries.cpp", _HOST),
+    "pt_accum.o": ("cxx", CSRC / "pt_accum.cpp", [*_HOST, CSRC / "pt_plan.h"]),
+    "pt_group.o": ("cxx", CSRC / "pt_group.cpp", _HOST),
     "pt_post.o": ("cxx", CSRC / "pt_post.cpp", _HOST),
     "pt_rccl.o": ("cxx", CSRC / "pt_rccl.cpp", [CSRC / "pt_rccl.h"]),
     "scene.o": ("cxx", CSRC / "scene.cpp", [INCLUDE / "pt_scene.h", CSRC / "pt_accel.h", CSRC / "pt_introsort.h"]),
@@ -178,6 +189,22 @@ def build_share_table(force: bool = False) -> Path:
     return SHARE_TABLE
 
 
+SCENE_PREP_CHECK_SRC = ROOT / "tests" / "native" / "scene_prep_check.cpp"
+SCENE_PREP_CHECK = ROOT / "tests" / "native" / "scene_prep_check"
+
+
+def build_scene_prep_check(force: bool = False) -> Path:
+    """Test infrastructure: the host-only scene preparation (csrc/pt_scene_prep.cpp, with scene.cpp's host
+    builder) dumped for a scene read from a file (tests/native/scene_prep_check.cpp), host-only like
+    plan_table, compiled with the library's own CXX_FLAGS (the unit normal and plane offset round by them)."""
+    srcs = [SCENE_PREP_CHECK_SRC, CSRC / "pt_scene_prep.cpp", CSRC / "scene.cpp"]
+    deps = [*srcs, *_PREP, CSRC / "pt_accel.h", CSRC / "pt_introsort.h", INCLUDE / "pt_scene.h"]
+    if force or _stale(SCENE_PREP_CHECK, deps):
+        _run(["g++", *CXX_FLAGS, "-Wno-unused-function", f"-I{INCLUDE}", f"-I{CSRC}", *map(str, srcs),
+              "-o", str(SCENE_PREP_CHECK)])
+    return SCENE_PREP_CHECK
+
+
 def build_oracle(force: bool = False) -> Path:
     """Test infrastructure only (see oracle/pt_oracle.h)."""
     src = [ORACLE_DIR / "pt_oracle.c", ORACLE_DIR / "pt_oracle.h", ORACLE_DIR / "Makefile", INCLUDE / "pt_fmath.h"]
@@ -192,5 +219,6 @@ if __name__ == "__main__":
     build_abi_caller(force="--force" in sys.argv)
     build_plan_table(force="--force" in sys.argv)
     build_share_table(force="--force" in sys.argv)
+    build_scene_prep_check(force="--force" in sys.argv)
     print(LIB)
     print(ORACLE_LIB)

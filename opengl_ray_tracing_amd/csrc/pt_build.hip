@@ -21,7 +21,7 @@
 // children after its parents), so the first internal nodes in id order are
 // exactly the top of the tree the megakernel stages in LDS (pt_kernels.hip).
 // encodeKernel then writes the wide records (pt_trace.h visitNodeF: both
-// children's boxes, widened outward as pt_runtime.cpp encodeWideTree widens
+// children's boxes, widened outward as pt_scene_prep.cpp encodeWideTree widens
 // the host-built tree) and pairsKernel the leaf-order pair records.
 //
 // The SAH is scene.cpp splitBinned's: 32 bins per axis over the node's
@@ -549,7 +549,7 @@ __device__ __forceinline__ int childRef(const BuildNode* nodes, const int* devId
   if (cnt > leafSize) return devId[k];
   return (int)~(((uint32_t)nodeStart(c) << LEAF_CNT_BITS) | (uint32_t)(cnt - 1));
 }
-// pt_runtime.cpp encodeWideTree's widening of the host-built tree
+// pt_scene_prep.cpp encodeWideTree's widening of the host-built tree
 __device__ __forceinline__ void widen(float4& lo, float4& hi, float inflate, float inflateAbs) {
   const float ex = inflate * (fabsf(lo.x) + fabsf(hi.x) + (hi.x - lo.x)) + inflateAbs + 1e-30f;
   const float ey = inflate * (fabsf(lo.y) + fabsf(hi.y) + (hi.y - lo.y)) + inflateAbs + 1e-30f;
@@ -583,7 +583,7 @@ __global__ void encodeKernel(const BuildNode* nodes, int M, int leafSize, const 
                      __int_as_float(childRef(nodes, devId, R, leafSize)), 0.0f, 0.0f);
 }
 
-// pair records in the built order (pt_runtime.cpp buildPairs): position i holds
+// pair records in the built order (pt_scene_prep.cpp buildPairs): position i holds
 // triangles order[i] (x) and order[i + 1] (y; zeros past the last), and their uploaded
 // indices (the record's last two floats, as int bits; -1 past the last)
 __global__ void pairsKernel(const float4* geo, const int* order, int n, float4* pairs) {
@@ -606,7 +606,7 @@ __global__ void pairsKernel(const float4* geo, const int* order, int n, float4* 
 }
 
 // ------------------------------------------------------------ 4-wide collapse
-// pt_runtime.cpp encodeWide4 on the device, level by level: every wide node of a
+// pt_scene_prep.cpp encodeWide4 on the device, level by level: every wide node of a
 // level takes its binary node's two children and keeps replacing the internal
 // child of largest surface area (first one on ties, areas in double as on the
 // host) by that child's two children until it has four; the next level's wide

@@ -1,6 +1,6 @@
 // pt_guides.hip -- guide buffers of the camera's first hit (pt_abi.h pt_render_guides): for every
 // pixel of the frame the camera ray through the pixel centre (pt_frame.h cameraDir, the frame
-// kernels' ray with the jitter terms 0), the batch query's hit search (Tracer::trace: the runtime's tree,
+// kernels' ray with the jitter terms 0), the ray queries' hit search (Tracer::trace: the runtime's tree,
 // results checked against the reference's, reference tie rules) and the integrators' hit record
 // (finishHit). One lane per pixel, one wave per 8x8 tile; the waves of a resident grid walk the
 // tiles in a grid-stride loop, so the traversal stack's overflow area is bounded by the grid.
@@ -23,7 +23,7 @@ __global__ __launch_bounds__(BLOCK) void guidesKernel(GuideParams p) {
   Stack st;
   st.init(s_stack, p.ovf, p.ovfDepth);
   Counters C = {0, 0, 0, 0, 0};
-  SceneView S = p.scene;  // no LDS copy of the top of the tree (as the batch query)
+  SceneView S = p.scene;  // no LDS copy of the top of the tree (as the ray queries, pt_query.hip)
   S.nTop = 0;
   S.fnTop = 0;
   S.f4nTop = 0;

@@ -1,5 +1,5 @@
 // pt_kernels.h -- kernel parameter blocks and launchers shared by
-// the .hip files (device) and pt_runtime.cpp / pt_post.cpp (host).
+// the .hip files (device) and the host files of the runtime (pt_runtime.h lists them).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -95,7 +95,7 @@ static_assert((NUM_QUEUES & (NUM_QUEUES - 1)) == 0 && NUM_QUEUES <= 64, "NUM_QUE
 constexpr int RAY_SHARDS = 64;     // sharded ray counters (u64, one per 256-byte line)
 constexpr int RAY_SHARD_STRIDE = CTL_LINE_INTS / 2;  // in u64
 // control block layout (bytes)
-constexpr int MAX_SLOTS = 16;  // frames in flight the control block has queue counters for (pt_runtime.cpp PIPE)
+constexpr int MAX_SLOTS = 16;  // frames in flight the control block has queue counters for (pt_runtime.h PIPE)
 constexpr size_t CTL_QUEUES = 0;  // MAX_SLOTS x NUM_QUEUES padded int counters
 constexpr size_t CTL_STATS = (size_t)MAX_SLOTS * 64 * 256;            // 5 u64 cumulative fetch counters
 constexpr size_t CTL_RAYS = CTL_STATS + 256;                          // RAY_SHARDS padded u64 counters
@@ -129,7 +129,7 @@ constexpr int REF_NONE = (int)0x80000000;
 constexpr int MAX_LEAF = 1 << LEAF_CNT_BITS;
 constexpr int MAX_TRIS = (1 << (31 - LEAF_CNT_BITS)) - 1;
 
-// Device-resident scene (relaid out at upload, see pt_runtime.cpp)
+// Device-resident scene (relaid out at upload, see pt_scene_prep.cpp)
 struct SceneView {
   const float4* geo;   // 4 float4 per triangle: (p1, w=dot(Ng,p1)), (p2, 0), (p3, 0), (Ng, 0)
   const float4* pairs; // PAIR_F4 float4 per triangle i: triangles i and i+1 component-interleaved (pt_trace.h pairTest)
@@ -141,11 +141,11 @@ struct SceneView {
   const float4* hitRec;
   const float4* mats;
   int nMats;           // materials in mats
-  const float4* bvh;   // 4 float4 per device node id (pt_runtime.cpp: top of the tree first, breadth-first)
+  const float4* bvh;   // 4 float4 per device node id (pt_scene_prep.cpp: top of the tree first, breadth-first)
   int nTop;            // device ids [0, nTop) are the top of the tree, staged in LDS by the megakernel
   int rootRef;         // encoded reference to node 1
   int nTri;
-  // The runtime's own tree over the same triangles (pt_runtime.cpp uploadAccel;
+  // The runtime's own tree over the same triangles (pt_scene_prep.cpp prepareAccel;
   // pt_trace.h "Reference-exact results through the runtime's tree"): wide
   // nodes with conservative boxes, pair records in its leaf order, and for
   // every position the uploaded triangle index. fast = 0: not used this launch.
@@ -154,7 +154,7 @@ struct SceneView {
   const float4* fpairs;
   const int* fastTri;
   int fRoot, fnTop;
-  // the same tree collapsed to 4-wide nodes (pt_runtime.cpp encodeWide4; pt_trace.h
+  // the same tree collapsed to 4-wide nodes (pt_scene_prep.cpp encodeWide4; pt_trace.h
   // traceRay4): W4_F4 float4 per node, breadth-first ids, leaves as in fbvh; null = none
   const float4* fbvh4;
   int f4Root, f4nTop;
@@ -171,7 +171,7 @@ struct SceneView {
 struct Env {
   const float4* hdr;    // w x h: (r, g, b, calculateHdrCache pdf) (row 0 = first scanline); null = black
   const float2* cache;  // calculateHdrCache sample table (x, y); null exactly when hdr is null
-  // The same texels in half the bytes, used when non-null (pt_runtime.cpp envOne builds them when
+  // The same texels in half the bytes, used when non-null (pt_env.cpp envOne builds them when
   // every texel round-trips bit for bit, pt_envcache.hip envCompactKernel): hdr8 = {r | g << 8 |
   // b << 16 | E << 24, pdf bits}, each channel m * 2^(E - 136) -- the Radiance RGBE form the
   // reference's decoder expands (hdrloader.cpp:99-104) -- and cache4 = x | y << 16, the sample
@@ -229,7 +229,7 @@ struct RenderParams {
   float eye[3];
   float cam[16];
   float4* accum;
-  // Pipelined frames (pt_runtime.cpp "frames in flight"): non-null = write each pixel's
+  // Pipelined frames (pt_runtime.h "frames in flight"): non-null = write each pixel's
   // sample colour here (float4, w unused) and leave the running mean to mixKernel, which
   // runs in frame order; null = mix into accum in place (IS:868-871)
   float* col;  // COL_F floats per slot of the share
@@ -291,16 +291,6 @@ struct RenderParams {
   // (width + 7) / 8) the frame count at which the tile retired, 0 = active; null without the flag. Only
   // the camera-ray pass reads it: a retired tile gets mask 0, so no frame kernel touches it
   const uint32_t* retiredAt;
-};
-
-struct TraceParams {
-  SceneView scene;
-  const float* rays;
-  int n;
-  float* t;
-  int* tri;
-  int* ovf;
-  int ovfDepth;
 };
 
 // The ray queries on device memory (pt_query.hip queryKernel; pt_abi.h pt_trace_closest_device,
@@ -381,7 +371,7 @@ void freePrimaryBins(PrimaryBins& b);
 // The runtime's own tree built on the device (pt_build.hip): a binned-SAH tree
 // over the triangles of geo (SceneView::geo layout), its wide records with
 // every box widened by inflate of its own magnitude plus inflateRelAbs x the
-// scene's largest coordinate (pt_runtime.cpp encodeWideTree), the pair records
+// scene's largest coordinate (pt_scene_prep.cpp encodeWideTree), the pair records
 // in its leaf order and that order. Device buffers owned by the caller
 // (freeAccelBuild); the stream is synchronised on return.
 struct BuildNode {  // 64 B, breadth-first ids (root 0)
@@ -400,7 +390,7 @@ struct AccelBuild {
 hipError_t buildAccelDevice(const float4* geo, int nTri, int leafSize, float inflate, float inflateRelAbs,
                             AccelBuild& out, hipStream_t s);
 void freeAccelBuild(AccelBuild& a);
-// the build nodes collapsed to 4-wide records (SceneView::fbvh4, pt_runtime.cpp encodeWide4's
+// the build nodes collapsed to 4-wide records (SceneView::fbvh4, pt_scene_prep.cpp encodeWide4's
 // layout, ids and widening) on the device; *out allocated here (W4_F4 float4 per wide node)
 hipError_t collapseWide4Device(const BuildNode* nodes, int nNodes, int leafSize, float inflate, float inflateRelAbs,
                                float4** out, int* rootRef, int* nDev, int* depth, hipStream_t s);
@@ -408,7 +398,7 @@ hipError_t collapseWide4Device(const BuildNode* nodes, int nNodes, int leafSize,
 // New vertex positions in place (pt_refit.hip, pt_abi.h pt_update_geometry): the geometry, pair and
 // shading records rewritten from the caller's vertex records, the uploaded tree's boxes refitted
 // bottom-up into refBox, and the uploaded tree's wide records and the triangles' leaf boxes rewritten
-// from them. The topology comes from the upload (pt_runtime.cpp makeRefit): the tables below are
+// from them. The topology comes from the upload (pt_scene_upload.cpp makeRefit): the tables below are
 // device memory, made at the first update of a scene.
 struct RefitTables {
   int2* topo = nullptr;       // per reference node: internal (left, right), 0 = absent; leaf (first triangle, -count)
@@ -484,7 +474,6 @@ hipError_t launchRegen(const RenderParams& p, int integrator, int grid, hipStrea
 bool regenTakesLists(int integrator, const RegenShape& r);  // the variant claims from live-item lists after a pass
 int regenLdsStack();
 int regenTop4(const RegenShape& r, int integrator);  // 4-wide nodes the wide regen kernel stages in LDS
-hipError_t launchTrace(const TraceParams& p, int grid, hipStream_t s, bool cull);
 // occluded: the any-hit query into p.occ, else the closest hit into p.t / p.tri
 hipError_t launchQuery(const QueryParams& p, int grid, hipStream_t s, bool occluded, bool cull);
 // Guide buffers (pt_guides.hip): the camera's first hit of every pixel centre, one lane per pixel,

@@ -1,6 +1,6 @@
 // pt_kernels.hip -- the megakernel of the progressive path tracer on MI355X (gfx950): the
-// three pass1.fsh integrators, a tile's camera rays and paths, the tile reorder between
-// frames and the batch query. What it shares with the other frame kernels (the pixel's
+// three pass1.fsh integrators, a tile's camera rays and paths, and the tile reorder between
+// frames. What it shares with the other frame kernels (the pixel's
 // seed, camera ray and store, the share's tiles) is pt_frame.h; traversal is pt_trace.h.
 // Each launcher follows its kernel.
 //
@@ -467,7 +467,7 @@ __device__ __forceinline__ uint32_t waveSum(uint32_t v) {
 }
 
 // WAVES > 0: compiled for that many waves per SIMD (the latency-bound large
-// scenes' variant, pt_runtime.cpp renderFrame)
+// scenes' variant, pt_runtime.cpp renderOne)
 template <int INTEG, bool CULL, bool COUNT, int WAVES = 0>
 __global__ __launch_bounds__(BLOCK, WAVES > 0 ? WAVES
                                              : (INTEG == 0 ? PT_MIN_WAVES_LAMBERT
@@ -594,29 +594,6 @@ __global__ __launch_bounds__(BLOCK, WAVES > 0 ? WAVES
   }
 }
 
-// ------------------------------------------------------------ batch query
-template <bool CULL>
-__global__ __launch_bounds__(BLOCK) void traceKernel(TraceParams p) {
-  __shared__ int s_stack[LDS_STACK * BLOCK];
-  Stack st;
-  st.init(s_stack, p.ovf, p.ovfDepth);
-  const size_t gtid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  Counters C = {0, 0, 0, 0, 0};
-  SceneView S = p.scene;  // no LDS copy of the top of the tree here
-  S.nTop = 0;
-  S.fnTop = 0;
-  S.f4nTop = 0;
-  Tracer<CULL, false> tr{S, st, C, nullptr};  // the runtime's tree when S.fast (reference-exact)
-  for (size_t k = gtid; k < (size_t)p.n; k += (size_t)gridDim.x * BLOCK) {
-    const float* r = p.rays + 6 * k;
-    V3 o = v3(r[0], r[1], r[2]), d = v3(r[3], r[4], r[5]);
-    float t;
-    int tri = tr.trace(o, d, t);
-    p.t[k] = tri >= 0 ? t : PT_INF;
-    p.tri[k] = tri;
-  }
-}
-
 // ------------------------------------------------------------ launchers
 // The megakernel instantiation of a frame, for the occupancy query that sizes the grid and for the
 // launch alike: counting launches never cull; the wide (WIDE_WAVES) variant is the culling Disney / MIS one
@@ -641,12 +618,6 @@ hipError_t launchRender(const RenderParams& p, int integrator, int grid, hipStre
 
 hipError_t renderBlocksPerCU(int integrator, bool cull, bool count, bool wide, int* nb) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(nb, renderVariant(integrator, cull, count, wide), BLOCK, 0);
-}
-
-hipError_t launchTrace(const TraceParams& p, int grid, hipStream_t s, bool cull) {
-  if (cull) hipLaunchKernelGGL((traceKernel<true>), dim3(grid), dim3(BLOCK), 0, s, p);
-  else hipLaunchKernelGGL((traceKernel<false>), dim3(grid), dim3(BLOCK), 0, s, p);
-  return hipGetLastError();
 }
 
 }  // namespace pt

@@ -1,4 +1,4 @@
-// pt_plan.h -- the launch policy of the frame path (pt_runtime.cpp createOne, uploadScene, renderOne):
+// pt_plan.h -- the launch policy of the frame path (pt_context.cpp createOne, pt_scene_upload.cpp uploadScene, pt_runtime.cpp renderOne):
 // which kernel, tree, camera-ray pass, bins and table form a launch uses, how many frames a launch
 // takes and how many launches are in flight. Pure functions of the context and the configuration:
 // no HIP call, no environment, nothing written to the context (tests/native/plan_table.cpp calls

@@ -1,15 +1,15 @@
-// pt_query.hip -- the ray queries on device memory (pt_abi.h pt_trace_closest_device,
+// pt_query.hip -- the ray queries (pt_abi.h pt_trace_closest, pt_trace_closest_device,
 // pt_trace_occluded_device and their host forms): for ray k with bound b = tmax[k] (none: PT_INF) the
-// closest hit below b, or whether there is one. With (t*, tri*) the batch query's result for the ray
+// closest hit below b, or whether there is one. With (t*, tri*) the unbounded query's result for the ray
 // (pt_trace_closest: the reference traversal's winner under the reference tie rules), the answer is
 // (t*, tri*) / 1 when tri* >= 0 && t* < b and the miss values / 0 otherwise (tests/query_ref.py). A
 // walk whose closest-hit bound starts at b gives exactly that -- a triangle at or beyond b cannot win,
-// and among the others the same least-t, first-in-order one does -- so the kernel runs the batch
-// query's hit search (Tracer) with the walks' BOUNDED switch: the runtime's tree checked against the
+// and among the others the same least-t, first-in-order one does -- so the kernel runs the frames'
+// hit search (Tracer) with the walks' BOUNDED switch: the runtime's tree checked against the
 // reference's (refReachable), or the uploaded tree alone. A ray with !(b > 0.0005f) -- hitTriangle's
 // own lower bound, and a NaN -- is a miss without a walk. Nothing is counted: pt_frame_stats stays as it was.
 //
-// One lane per ray in the batch query's grid-stride loop. A loop that refills a wave's finished lanes with
+// One lane per ray in a grid-stride loop. A loop that refills a wave's finished lanes with
 // the next rays (the resumable 4-wide walk, walk4Run, a claim of 512 rays per wave and atomic) was tried
 // for the any-hit and short-range rays, which finish at very different times, and measured about half
 // the plain loop's rate on every case: not kept (profiles/r14/queries.json).
@@ -24,13 +24,13 @@
 namespace pt {
 
 __device__ __forceinline__ SceneView queryScene(const QueryParams& p) {
-  SceneView S = p.scene;  // no LDS copy of the top of the tree (as the batch query)
+  SceneView S = p.scene;  // no LDS copy of the top of the tree
   S.nTop = 0;
   S.fnTop = 0;
   S.f4nTop = 0;
   return S;
 }
-// ray k's bound: a bound past PT_INF admits nothing more (the batch query accepts only t < PT_INF); a
+// ray k's bound: a bound past PT_INF admits nothing more (the unbounded query accepts only t < PT_INF); a
 // NaN stays one (no fminf, which would drop it), and fails the callers' b > 0.0005f
 __device__ __forceinline__ float loadBound(const QueryParams& p, size_t k) {
   const float b = p.tmax ? p.tmax[k] : PT_INF;

@@ -1,5 +1,5 @@
 // pt_rccl.h -- RCCL entry points the in-process multi-GPU gather uses
-// (pt_runtime.cpp, pt_config.n_devices > 1), resolved at run time so libpt.so
+// (pt_group.cpp, pt_config.n_devices > 1), resolved at run time so libpt.so
 // has no link-time RCCL dependency and, inside a PyTorch process, shares the
 // RCCL PyTorch already loaded (one RCCL, one HIP runtime per process).
 #pragma once

@@ -2,7 +2,7 @@
 // caller's vertex records to every buffer pt_upload_scene derives from the positions, without the host.
 //
 //   recordsKernel   one thread per triangle: the geometry record (the unit normal and plane offset in
-//                   pt_runtime.cpp nrm3's operation order: this file is built like every device file,
+//                   pt_scene_prep.cpp nrm3's operation order: this file is built like every device file,
 //                   without FMA contraction and with IEEE division and sqrt), the pair record of
 //                   triangles i and i + 1, the three shading normals of the hit record (its material id
 //                   stays)
@@ -40,7 +40,7 @@ struct Geo {
   float4 p1, p2, p3, n;  // SceneView::geo
 };
 
-// pt_runtime.cpp prepareScene / nrm3
+// pt_scene_prep.cpp prepareScene / nrm3
 __device__ __forceinline__ Geo geoOf(const float* t) {
   const float e1x = t[3] - t[0], e1y = t[4] - t[1], e1z = t[5] - t[2];
   const float e2x = t[6] - t[0], e2y = t[7] - t[1], e2z = t[8] - t[2];
@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(BT) recordsKernel(RefitParams p) {
   h[0] = make_float4(t[9], t[10], t[11], t[12]);
   h[1] = make_float4(t[13], t[14], t[15], t[16]);
   h[2] = make_float4(t[17], fid, 0.0f, 0.0f);
-  // pt_runtime.cpp buildPairs: triangle i + 1's record computed here again (zeros past the last)
+  // pt_scene_prep.cpp buildPairs: triangle i + 1's record computed here again (zeros past the last)
   Geo B;
   B.p1 = B.p2 = B.p3 = B.n = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   const bool more = i + 1 < p.nTri;
@@ -152,7 +152,7 @@ __global__ void __launch_bounds__(REFIT_TAIL) tailKernel(const int2* topo, const
   }
 }
 
-// pt_runtime.cpp encodeWideTree's box layout, its boxes not widened (the uploaded tree's are exact)
+// pt_scene_prep.cpp encodeWideTree's box layout, its boxes not widened (the uploaded tree's are exact)
 __global__ void __launch_bounds__(BT) wideKernel(const int2* devKids, int nDev, const float4* refBox, float4* bvh) {
   const int id = blockIdx.x * BT + threadIdx.x;
   if (id >= nDev) return;

@@ -1,7 +1,11 @@
-// pt_runtime.h -- what the host files of the C-ABI share (pt_runtime.cpp: contexts, uploads, the
-// frame path, gather, stats; pt_post.cpp: the display post-processing): the context, the error
-// helpers, and the few functions of pt_runtime.cpp the post-processing calls. Internal: not installed.
-// (The launch policy of the frame path -- pure functions of this context -- is pt_plan.h.)
+// pt_runtime.h -- what the host files of the C-ABI share: the context, the error helpers, and the
+// functions one file defines and another calls. The files, by subject: pt_context.cpp (context life,
+// streams, stats), pt_scene_upload.cpp (scene upload, geometry update), pt_env.cpp (environment, BASIC
+// state), pt_runtime.cpp (the frame path), pt_queries.cpp (ray queries), pt_accum.cpp (accumulation
+// access, adaptive sampling, pack and unpack), pt_group.cpp (the in-process device group) and
+// pt_post.cpp (the display post-processing). Internal: not installed.
+// (The launch policy of the frame path -- pure functions of this context -- is pt_plan.h; the
+// host-only scene preparation, which does not know the context, is pt_scene_prep.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -191,11 +195,7 @@ struct pt_ctx {
   size_t ovfInts = 0;
   // shards
   int shardSize = 32, shardsX = 0, shardsY = 0, numItems = 0, perQueue = 0;
-  // scratch for queries / tonemap / pack
-  float* d_rays = nullptr;
-  float* d_t = nullptr;
-  int* d_tri = nullptr;
-  size_t traceCap = 0;
+  // scratch for tonemap
   float* d_rgb = nullptr;
   // The ray queries on device memory (pt_trace_closest_device, pt_trace_occluded_device and their host
   // forms): their own stack overflow area, sized at first use for the largest grid a query launches and
@@ -313,12 +313,39 @@ static void dfree(T*& p) {
   p = nullptr;
 }
 
-// defined in pt_runtime.cpp; the library exports only pt_abi.h's names
+// every context of a device group (rank 0 first), or just ctx
+static inline std::vector<pt_ctx*> members(pt_ctx* ctx) {
+  std::vector<pt_ctx*> m{ctx};
+  m.insert(m.end(), ctx->peers.begin(), ctx->peers.end());
+  return m;
+}
+
+static inline int fromPeer(pt_ctx* ctx, pt_ctx* p, int rc) {
+  if (rc && p != ctx) ctx->err = "device " + std::to_string(p->cfg.device_id) + ": " + p->err;
+  return rc;
+}
+
+// What one host file defines and another calls; the library exports only pt_abi.h's names
 #pragma GCC visibility push(hidden)
-int joinGather(pt_ctx* ctx);  // the device group's gather of the last frame has landed in the accumulation
-int joinPipe(pt_ctx* ctx);    // the caller's stream waits for the last pipelined frame's running-mean update
-SceneView sceneView(const pt_ctx* ctx);
-Share shareOf(const pt_ctx* ctx, int rank, int world);
-PackParams packParams(const pt_ctx* ctx, int rank, int world);
+// pt_runtime.cpp
+int joinPipe(pt_ctx* ctx);     // the caller's stream waits for the last pipelined frame's running-mean update
+int syncStreams(pt_ctx* ctx);  // every stream the context renders on, then its own: all work done
+SceneView sceneView(const pt_ctx* ctx);  // the uploaded scene as the kernels read it (fast is set per launch)
+Share shareOf(const pt_ctx* ctx, int rank, int world);  // rank's share of a world-way screen-tile split of the image
+PackParams packParams(const pt_ctx* ctx, int rank, int world);  // that share and its pixel slots
+int dropMoments(pt_ctx* ctx);   // the sample moments (and what adaptive sampling decided from them) are no longer valid
+int joinAdaptive(pt_ctx* ctx);  // the caller's stream waits for the last update or clear of the adaptive tile planes
+void foldLaunches(pt_ctx* ctx);  // every launch's device time folded into the totals, waiting for them
+// pt_scene_upload.cpp
 void dropHistory(pt_ctx* ctx);  // the temporal history shows another scene or another light after an upload
+void freeRefit(pt_ctx* ctx);    // pt_update_geometry's device tables and staging belong to one upload
+// pt_env.cpp
+int ensureBasicImage(pt_ctx* ctx);  // the BASIC double image, allocated and zeroed on first use
+// pt_group.cpp
+int createGroup(pt_ctx* ctx);    // the gather's streams, events, buffers and communicators of a device group
+void destroyGroup(pt_ctx* ctx);  // ... released, and the other ranks' contexts destroyed
+int groupGather(pt_ctx* ctx);    // the ranks' tiles of the frame just enqueued packed, sent and unpacked into rank 0's accumulation
+int syncGroup(pt_ctx* ctx);      // every device's render stream, the gather's streams, then rank 0's stream
+int joinGather(pt_ctx* ctx);     // the device group's gather of the last frame has landed in the accumulation
 #pragma GCC visibility pop
+

@@ -1,0 +1,353 @@
+// pt_scene_upload.cpp -- pt_upload_scene and pt_update_geometry of the C-ABI in include/pt_abi.h:
+// what pt_scene_prep.cpp prepared on the host uploaded to every device of a context, the runtime's
+// own tree built there (pt_build.hip), and the geometry update that refits the uploaded tree in place
+// (pt_refit.hip); with them pt_download_node_boxes and pt_build_bvh_device.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "pt_abi.h"
+#include "pt_kernels.h"
+#include "pt_plan.h"
+#include "pt_runtime.h"
+#include "pt_scene_prep.h"
+
+using namespace pt;
+
+template <class T>
+static int upload(pt_ctx* ctx, T** dst, const std::vector<T>& src) {
+  dfree(*dst);
+  if (src.empty()) return PT_OK;
+  CK(hipMalloc(dst, src.size() * sizeof(T)));
+  CK(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return PT_OK;
+}
+
+// the temporal history shows another scene or another light after an upload
+void dropHistory(pt_ctx* ctx) {
+  ctx->histValid = false;
+  ctx->resolvedFresh = false;
+}
+
+// What new geometry invalidates, for an upload and an update alike: the tree / split policies are
+// measured again at the next restart, the temporal history and the sample moments saw the old scene,
+// the runtime tree is not in place until it is built again (runtimeTreeReady), and the traversal stack
+// starts over from the uploaded tree's depth. (sceneVersion stays with the callers: an update bumps
+// it whether it has a runtime tree or not, an upload only with one -- runtimeTreeReady.)
+// On success each caller's sequence is what it was. On a failure they differ from before in one way:
+// the flags and figures are reset here, ahead of the uploads (uploadScene) and of makeRefit and the
+// refit launch (updateOne), where both callers used to reset them after those steps -- so a call that
+// fails there no longer leaves the old runtime tree marked ready over geometry half replaced.
+static int invalidateScene(pt_ctx* ctx, int depth) {
+  ctx->policyKey++;
+  dropHistory(ctx);
+  if (int rc = dropMoments(ctx)) return rc;
+  ctx->maxStack = depth + 1;
+  ctx->fastReady = false;
+  ctx->fast4Ready = false;
+  ctx->accelDevice = -1;
+  ctx->accelMs = 0.0f;
+  ctx->accelNodes = ctx->accelDepth = 0;
+  return PT_OK;
+}
+
+// The runtime's tree built on the device from the geometry records in d_geo (pt_build.hip) and collapsed
+// to 4-wide nodes there: pt_upload_scene's build and pt_update_geometry's rebuild. *built false: the
+// tree would have 2^24 nodes or more, and the context stays on the uploaded tree.
+static int buildRuntimeTree(pt_ctx* ctx, bool* built) {
+  *built = false;
+  const auto t0 = std::chrono::steady_clock::now();
+  AccelBuild ab;
+  hipError_t e = buildAccelDevice(ctx->d_geo, ctx->nTri, PT_ACCEL_LEAF, 1e-5f, 3e-5f, ab, ctx->stream);
+  if (e != hipSuccess) return fail(ctx, PT_E_HIP, std::string("device tree build: ") + hipGetErrorString(e));
+  if (ab.nNodes + 1 >= (1 << 24)) {  // as the host path: no runtime tree of 2^24 nodes or more
+    freeAccelBuild(ab);
+    return PT_OK;
+  }
+  // the 4-wide collapse, on the device too (the large-scene regen kernel's and the megakernel's tree)
+  float4* w4 = nullptr;
+  e = collapseWide4Device(ab.nodes, ab.nNodes, PT_ACCEL_LEAF, 1e-5f, 3e-5f, &w4, &ctx->f4Root, &ctx->f4nDev,
+                          &ctx->f4Depth, ctx->stream);
+  dfree(ab.nodes);
+  if (e != hipSuccess) {
+    freeAccelBuild(ab);
+    return fail(ctx, PT_E_HIP, std::string("device 4-wide collapse: ") + hipGetErrorString(e));
+  }
+  dfree(ctx->d_fbvh4);
+  ctx->d_fbvh4 = w4;
+  dfree(ctx->d_fbvh);
+  dfree(ctx->d_fpairs);
+  dfree(ctx->d_fastTri);
+  ctx->d_fbvh = ab.bvh;
+  ctx->d_fpairs = ab.pairs;
+  ctx->d_fastTri = ab.order;
+  ctx->fRoot = ab.rootRef;
+  ctx->fnDev = ab.nDev;
+  ctx->fDepth = ab.depth;
+  ctx->accelMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  ctx->accelDevice = 1;
+  ctx->accelNodes = ab.nNodes;
+  *built = true;
+  return PT_OK;
+}
+
+// the runtime tree and its 4-wide collapse are in place: the frames may walk them
+static void runtimeTreeReady(pt_ctx* ctx) {
+  ctx->fast4Ready = true;
+  // a visit pushes up to three children: the traversal stack needs 3 entries per wide level
+  ctx->maxStack = std::max(ctx->maxStack, 3 * ctx->f4Depth + 2);
+  ctx->sceneVersion++;  // camera-ray bins are rebuilt for the new triangles
+  ctx->maxStack = std::max(ctx->maxStack, ctx->fDepth + 1);
+  ctx->fastReady = true;
+}
+
+// pt_update_geometry's device tables and staging belong to one upload
+void freeRefit(pt_ctx* ctx) {
+  dfree(ctx->refit.topo);
+  dfree(ctx->refit.byHeight);
+  dfree(ctx->refit.heightStart);
+  dfree(ctx->refit.devKids);
+  ctx->refit = RefitTables{};
+  ctx->refitStart.clear();
+  dfree(ctx->d_updVerts);
+}
+
+static int uploadScene(pt_ctx* ctx, const float* tris, const SceneHost& h) {
+  if (int rc = syncStreams(ctx)) return rc;  // no frame in flight reads the buffers replaced here
+  if (ctx->queryIssued) CK(hipEventSynchronize(ctx->queryDone));  // nor a ray query, whichever stream it is on
+  if (int rc = invalidateScene(ctx, h.ref.depth)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  int rc;
+  if ((rc = upload(ctx, &ctx->d_pairs, h.pairs)) || (rc = upload(ctx, &ctx->d_geo, h.geo)) ||
+      (rc = upload(ctx, &ctx->d_bvh, h.ref.bvh)))
+    return rc;
+  if ((rc = upload(ctx, &ctx->d_hit, h.hit)) || (rc = upload(ctx, &ctx->d_mats, h.mats))) return rc;
+  ctx->nMats = (int)(h.mats.size() / MAT_F4);
+  ctx->nTri = h.nTri;
+  ctx->nNodes = h.nNodes;
+  ctx->nDevNodes = h.ref.nDev;
+  ctx->sceneBytes = sceneBytes(ctx->nTri, ctx->nDevNodes);
+  // Large Disney/MIS scenes (the regen kernel's, pt_plan.h wideScene) run 4 frames in flight:
+  // c5's frames last ~6 ms, and 8 in flight spend more on the pipeline's fill and drain than
+  // they gain (bench line, 20 frames from idle: 5.60-5.66 ms per frame at 4 vs 5.88 at 8, 6.00 at 6)
+  if (ctx->pipe && !ctx->pipeDepthFixed) ctx->pipeDepth = wideScene(ctx) ? std::min(ctx->pipeDepthBase, 4) : ctx->pipeDepthBase;
+  // (the batch's large-scene guard, unlike wideScene, holds under PT_FLAG_NO_CULL too)
+  if (ctx->pipe) ctx->batchCap = batchFor(ctx, ctx->cfg.integrator != 0 && largeScene(ctx));
+  ctx->rootRef = h.ref.rootRef;
+  ctx->depth = h.ref.depth;
+  // what pt_update_geometry starts from: the boxes on the device, the topology on the host
+  freeRefit(ctx);
+  ctx->refTopo = h.topo;
+  ctx->refOrder = h.ref.ids;
+  ctx->sceneFast = h.fast;
+  if ((rc = upload(ctx, &ctx->d_refBox, h.refBox))) return rc;
+  if (!h.fast) return PT_OK;
+  if ((rc = upload(ctx, &ctx->d_refParent, h.parent)) || (rc = upload(ctx, &ctx->d_leafBox, h.leafBox))) return rc;
+  if (h.deviceBuild) {
+    bool built = false;
+    if ((rc = buildRuntimeTree(ctx, &built)) || !built) return rc;
+  } else {
+    if ((rc = upload(ctx, &ctx->d_fbvh, h.fastTree.bvh)) || (rc = upload(ctx, &ctx->d_fpairs, h.fpairs)) ||
+        (rc = upload(ctx, &ctx->d_fastTri, h.order)))
+      return rc;
+    ctx->fRoot = h.fastTree.rootRef;
+    ctx->fnDev = h.fastTree.nDev;
+    ctx->fDepth = h.fastTree.depth;
+    ctx->accelMs = h.accelMs;
+    ctx->accelDevice = 0;
+    ctx->accelNodes = h.accelNodes;
+  }
+  ctx->accelDepth = ctx->fDepth;
+  // the host-built tree's 4-wide collapse (the device build collapsed on the device above)
+  if (!h.deviceBuild) {
+    const std::vector<float>& an = h.accelRef;
+    const int nn = (int)(an.size() / 12);
+    float scale = 0.0f;  // the scene's largest coordinate magnitude: the root box's
+    for (int k = 6; k < 12 && nn > 1; k++) scale = std::max(scale, std::fabs(an[12 + k]));
+    std::vector<float4> w4;
+    encodeWide4(an.data(), nn, h.nTri, 1e-5f, 3e-5f * scale, w4, ctx->f4Root, ctx->f4nDev, ctx->f4Depth);
+    if ((rc = upload(ctx, &ctx->d_fbvh4, w4))) return rc;
+  }
+  runtimeTreeReady(ctx);
+  return PT_OK;
+}
+
+int pt_upload_scene(pt_ctx* ctx, const float* tris, int nTri, const float* nodes, int nNodes) {
+  if (!ctx || !tris || !nodes) return PT_E_INVALID;
+  if (nTri < 1 || nNodes < 2) return fail(ctx, PT_E_BADSCENE, "need >= 1 triangle and >= 2 nodes (dummy 0, root 1)");
+  if (nTri > MAX_TRIS) return fail(ctx, PT_E_BADSCENE, "too many triangles for the leaf encoding");
+  const auto t0 = std::chrono::steady_clock::now();
+  SceneHost h;
+  std::string bad = prepareScene(tris, nTri, nodes, nNodes, h, (ctx->cfg.flags & PT_FLAG_HOST_ACCEL) != 0);
+  if (!bad.empty()) return fail(ctx, PT_E_BADSCENE, bad);
+  for (pt_ctx* m : members(ctx))
+    if (int rc = uploadScene(m, tris, h)) return fromPeer(ctx, m, rc);
+  ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PT_OK;
+}
+
+// ------------------------------------------------------------ geometry update (pt_refit.hip)
+// The device tables of the uploaded tree's topology, made at the scene's first update
+// (pt_scene_prep.cpp refitTables computes them on the host).
+static int makeRefit(pt_ctx* ctx) {
+  if (ctx->refit.ready) return PT_OK;
+  const RefitHost r = refitTables(ctx->refTopo, ctx->refOrder);
+  ctx->refitStart = r.heightStart;
+  RefitTables& t = ctx->refit;
+  int rc;
+  if ((rc = upload(ctx, &t.topo, ctx->refTopo)) || (rc = upload(ctx, &t.byHeight, r.byHeight)) ||
+      (rc = upload(ctx, &t.heightStart, r.heightStart)) || (rc = upload(ctx, &t.devKids, r.devKids)))
+    return rc;
+  t.heights = r.heights;
+  t.tailFrom = r.tailFrom;
+  t.ready = true;
+  return PT_OK;
+}
+
+// One context's update from nTri vertex records in its device memory; the caller has waited for the
+// frames and queries in flight. What uploadScene invalidates is invalidated here (invalidateScene).
+static int updateOne(pt_ctx* ctx, const float* d_verts, int stride) {
+  if (int rc = invalidateScene(ctx, ctx->depth)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  if (int rc = makeRefit(ctx)) return rc;
+  RefitParams p;
+  p.verts = d_verts;
+  p.stride = stride;
+  p.nTri = ctx->nTri;
+  p.nDevNodes = ctx->nDevNodes;
+  p.geo = ctx->d_geo;
+  p.pairs = ctx->d_pairs;
+  p.hitRec = ctx->d_hit;
+  p.bvh = ctx->d_bvh;
+  p.refBox = ctx->d_refBox;
+  p.leafBox = ctx->sceneFast ? ctx->d_leafBox : nullptr;
+  // PT_UPDATE_TIMES (environment; tools/update_time.py): the device time of each step, on stderr
+  const bool timed = std::getenv("PT_UPDATE_TIMES") != nullptr;
+  struct StepEvents {  // destroyed on every way out
+    hipEvent_t ev[4] = {};
+    ~StepEvents() {
+      for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    }
+  } steps;
+  hipEvent_t* ev = steps.ev;
+  if (timed)
+    for (int k = 0; k < 4; k++) CK(hipEventCreate(&ev[k]));
+  CK(launchRefit(p, ctx->refit, ctx->refitStart.data(), timed ? ev : nullptr, ctx->stream));
+  ctx->sceneVersion++;  // guides and camera-ray bins of the old positions are stale, runtime tree or not
+  bool built = false;
+  if (ctx->sceneFast) {
+    if (int rc = buildRuntimeTree(ctx, &built)) return rc;
+  }
+  CK(hipStreamSynchronize(ctx->stream));
+  if (built) {
+    ctx->accelDepth = ctx->fDepth;
+    runtimeTreeReady(ctx);
+  }
+  if (timed) {
+    float ms[3] = {};
+    for (int k = 0; k < 3; k++) CK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+    std::fprintf(stderr, "pt_update_geometry: records %.4f refit %.4f reencode %.4f build %.4f ms, %d heights, tail from %d\n",
+                 ms[0], ms[1], ms[2], ctx->accelMs, ctx->refit.heights, ctx->refit.tailFrom);
+  }
+  return PT_OK;
+}
+
+static int updateArgs(pt_ctx* ctx, const void* verts, int nTri, int stride) {
+  if (!ctx || !verts) return PT_E_INVALID;
+  if (ctx->cfg.integrator == PT_BASIC_CPU_COMPAT || !ctx->d_bvh) return fail(ctx, PT_E_NOSCENE, "no scene");
+  if (nTri != ctx->nTri) return fail(ctx, PT_E_INVALID, "pt_update_geometry: nTriangles differs from the uploaded scene's");
+  if (stride < 18) return fail(ctx, PT_E_INVALID, "pt_update_geometry: stride < 18 floats");
+  if (ctx->cfg.flags & PT_FLAG_HOST_ACCEL)
+    return fail(ctx, PT_E_INVALID, "pt_update_geometry: not on a PT_FLAG_HOST_ACCEL context (the update builds on the GPU)");
+  return PT_OK;
+}
+
+static int updateWait(pt_ctx* ctx) {
+  if (int rc = syncStreams(ctx)) return rc;  // no frame in flight reads the buffers rewritten here
+  if (ctx->queryIssued) CK(hipEventSynchronize(ctx->queryDone));  // nor a ray query, whichever stream it is on
+  return PT_OK;
+}
+
+int pt_update_geometry(pt_ctx* ctx, const float* verts, int nTri, int stride) {
+  if (int rc = updateArgs(ctx, verts, nTri, stride)) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (pt_ctx* m : members(ctx)) {
+    if (int rc = updateWait(m)) return fromPeer(ctx, m, rc);
+    CK(hipSetDevice(m->cfg.device_id));
+    if (!m->d_updVerts) {
+      hipError_t e = hipMalloc(&m->d_updVerts, (size_t)nTri * 18 * sizeof(float));
+      if (e != hipSuccess) return fail(ctx, PT_E_NOMEM, "pt_update_geometry: vertex staging");
+    }
+    CK(hipMemcpy2DAsync(m->d_updVerts, 18 * sizeof(float), verts, (size_t)stride * sizeof(float), 18 * sizeof(float),
+                        (size_t)nTri, hipMemcpyHostToDevice, m->stream));
+    if (int rc = updateOne(m, m->d_updVerts, 18)) return fromPeer(ctx, m, rc);
+  }
+  ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PT_OK;
+}
+
+int pt_update_geometry_device(pt_ctx* ctx, const void* d_verts, int nTri, int stride) {
+  if (int rc = updateArgs(ctx, d_verts, nTri, stride)) return rc;
+  if (!ctx->peers.empty()) return fail(ctx, PT_E_INVALID, "pt_update_geometry_device: not on an n_devices > 1 context");
+  const auto t0 = std::chrono::steady_clock::now();
+  if (int rc = updateWait(ctx)) return rc;
+  if (int rc = updateOne(ctx, static_cast<const float*>(d_verts), stride)) return rc;
+  ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PT_OK;
+}
+
+int pt_download_node_boxes(pt_ctx* ctx, float* boxes) {
+  if (!ctx || !boxes) return PT_E_INVALID;
+  if (ctx->cfg.integrator == PT_BASIC_CPU_COMPAT || !ctx->d_refBox) return fail(ctx, PT_E_NOSCENE, "no scene");
+  CK(hipSetDevice(ctx->cfg.device_id));
+  std::vector<float4> b((size_t)ctx->nNodes * 2);
+  CK(hipMemcpyAsync(b.data(), ctx->d_refBox, b.size() * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < ctx->nNodes; k++) {
+    const float4 lo = b[2 * (size_t)k], hi = b[2 * (size_t)k + 1];
+    float* o = boxes + 6 * (size_t)k;
+    o[0] = lo.x; o[1] = lo.y; o[2] = lo.z; o[3] = hi.x; o[4] = hi.y; o[5] = hi.z;
+  }
+  return PT_OK;
+}
+
+int pt_build_bvh_device(pt_ctx* ctx, const float* tris, int nTri, int leafSize, float* nodes_out, int maxNodes,
+                        int* nNodesOut, int* orderOut) {
+  if (!ctx || !tris || !nodes_out || !nNodesOut || !orderOut || nTri < 1 || leafSize < 1 || leafSize > MAX_LEAF)
+    return PT_E_INVALID;
+  if (nTri > MAX_TRIS) return fail(ctx, PT_E_BADSCENE, "too many triangles for the leaf encoding");
+  if (int rc = syncStreams(ctx)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  // the builder reads p1..p3 of the geometry records (the normal and plane offset only feed the pair records)
+  std::vector<float4> geo((size_t)nTri * 4, make_float4(0, 0, 0, 0));
+  for (int i = 0; i < nTri; i++)
+    for (int k = 0; k < 3; k++) {
+      const float* v = tris + (size_t)i * 36 + 3 * k;
+      geo[4 * (size_t)i + k] = make_float4(v[0], v[1], v[2], 0.0f);
+    }
+  float4* dgeo = nullptr;
+  if (int rc = upload(ctx, &dgeo, geo)) return rc;
+  AccelBuild ab;
+  hipError_t e = buildAccelDevice(dgeo, nTri, leafSize, 0.0f, 0.0f, ab, ctx->stream);
+  dfree(dgeo);
+  if (e != hipSuccess) return fail(ctx, PT_E_HIP, std::string("device tree build: ") + hipGetErrorString(e));
+  const int M = ab.nNodes;
+  *nNodesOut = M + 1;
+  std::vector<BuildNode> bn(M);
+  e = hipMemcpy(bn.data(), ab.nodes, (size_t)M * sizeof(BuildNode), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(orderOut, ab.order, (size_t)nTri * sizeof(int), hipMemcpyDeviceToHost);
+  freeAccelBuild(ab);
+  if (e != hipSuccess) return fail(ctx, PT_E_HIP, std::string("device tree download: ") + hipGetErrorString(e));
+  if (M + 1 > maxNodes) return fail(ctx, PT_E_INVALID, "nodes_out holds fewer than *nNodes_out nodes");
+  const std::vector<float> ref = refNodes(bn, leafSize);
+  std::memcpy(nodes_out, ref.data(), ref.size() * sizeof(float));
+  return PT_OK;
+}

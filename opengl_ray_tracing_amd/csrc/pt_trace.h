@@ -84,7 +84,7 @@ __device__ __forceinline__ float hitAABB(V3 o, V3 inv, float4 lo, float4 hi, flo
   return (t1 >= t0) ? ((t0 > 0.0f) ? t0 : t1) : -1.0f;
 }
 
-// Both children's hitAABB of one wide node. Node record (pt_runtime.cpp):
+// Both children's hitAABB of one wide node. Node record (pt_scene_prep.cpp encodeWideTree):
 // {L.lo.x, R.lo.x, L.lo.y, R.lo.y}, {L.lo.z, R.lo.z, L.hi.x, R.hi.x},
 // {L.hi.y, R.hi.y, L.hi.z, R.hi.z}, {left ref, right ref, -, -}: the slab
 // differences and products of the two boxes run as packed pairs
@@ -123,8 +123,8 @@ __device__ __forceinline__ void visitNode(const float4* nd, V3 o, V3 inv, NodeHi
 // The runtime tree's slab tests fused: (plane - o) * inv as fma(plane, inv,
 // -o * inv), one packed FMA per axis and child pair instead of a subtract and a
 // multiply. The rounding differs from hitAABB's by about |o| * 2^-23 along each
-// axis, far inside the widening of the runtime tree's boxes (pt_runtime.cpp
-// uploadAccel), so the walk still meets every triangle the ray hits; results
+// axis, far inside the widening of the runtime tree's boxes (pt_scene_prep.cpp
+// prepareAccel), so the walk still meets every triangle the ray hits; results
 // found through it are checked against the reference tree as before. Never
 // used on the reference tree, whose d must be hitAABB's bit for bit.
 __device__ __forceinline__ void visitNodeF(const float4* nd, V3 inv, V3 noi, NodeHit& h) {
@@ -211,7 +211,7 @@ __device__ __forceinline__ bool triTest(float4 A, float4 B, float4 C, float4 Nn,
   t = tt;
   return !(fabsf(dn) < 0.00001f) && !(tt < 0.0005f) && (tt < tmax) && (r1 || r2);
 }
-// triTest of triangles i and i+1 from their pair record (pt_runtime.cpp): the two triangles'
+// triTest of triangles i and i+1 from their pair record (pt_scene_prep.cpp buildPairs): the two triangles'
 // data arrive in one memory round trip, component-interleaved. Every operation of triTest per
 // triangle, in scalar VALU. (Until round 4 the pair ran as packed v_pk_mul/v_pk_add math, half
 // the VALU, but with o and d broadcast into six register pairs that the compiler hoists out of
@@ -405,7 +405,7 @@ __device__ __forceinline__ int traceRay(const SceneView& S, V3 o, V3 d, float& t
 }
 
 // ----------------------------------------------------------------- 4-wide runtime tree
-// The runtime tree collapsed to 4-wide nodes (pt_runtime.cpp encodeWide4): per
+// The runtime tree collapsed to 4-wide nodes (pt_scene_prep.cpp encodeWide4): per
 // node {lo.x of children 0..3}, {lo.y}, {lo.z}, {hi.x}, {hi.y}, {hi.z}, {refs},
 // {-}: 128 bytes, one line. A visit tests the four (widened) child boxes with
 // fused slabs, visits the nearest hit child next and pushes the others far to
@@ -753,7 +753,7 @@ __device__ __forceinline__ bool refReachableBox(const SceneView& S, const float4
   }
   // up the reference path: each box by hitAABB itself -- UP: until one holds P by the margin (that box
   // and every box enclosing it pass, as for the leaf box above; the boxes of a reference tree nest,
-  // pt_runtime.cpp prepareAccel)
+  // pt_scene_prep.cpp prepareAccel)
   for (int c = leaf; c != 1; c = S.refParent[c]) {
     if (c <= 0) return false;
     const float4 blo = S.refBox[2 * (size_t)c], bhi = S.refBox[2 * (size_t)c + 1];
@@ -1059,8 +1059,8 @@ __device__ __forceinline__ void finishHit(const SceneView& S, int tri, V3 o, V3 
 
 // ------------------------------------------------------------ queries
 // Closest-hit and shadow queries of one lane over the scene, with the reference's results whichever
-// tree is walked: the megakernel's integrators, the batch query (pt_trace_closest), the guide
-// buffers (pt_guides.hip) and the ray queries (pt_query.hip) share it.
+// tree is walked: the megakernel's integrators, the guide buffers (pt_guides.hip) and the ray
+// queries (pt_query.hip: pt_trace_closest and the ranged forms) share it.
 template <bool CULL, bool COUNT>
 struct Tracer {
   const SceneView& S;

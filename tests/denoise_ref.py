@@ -82,7 +82,7 @@ def finish_hit(tris, rays, t, tri, w: int, h: int):
     p1, p2, p3 = R[:, 0:3], R[:, 3:6], R[:, 6:9]
     n1, n2, n3 = R[:, 9:12], R[:, 12:15], R[:, 15:18]
     with np.errstate(all="ignore"):
-        # the geometric normal: normalize(cross(p2 - p1, p3 - p1)) (pt_runtime.cpp nrm3)
+        # the geometric normal: normalize(cross(p2 - p1, p3 - p1)) (pt_scene_prep.cpp nrm3)
         e1, e2 = p2 - p1, p3 - p1
         cx = e1[:, 1] * e2[:, 2] - e2[:, 1] * e1[:, 2]
         cy = e1[:, 2] * e2[:, 0] - e2[:, 2] * e1[:, 0]

@@ -13,7 +13,7 @@ recur non-adjacently and neighbouring triangles differ):
   * fixed slots (SLOTS): metallic 1 with clearcoat 0, roughness 0, clearcoatGloss 1, and four pairs
     that differ only in emissive, only in IOR (not shaded), by one ulp of roughness, and only in
     the sign of a zero sheen -- all distinct keys for the runtime's material table
-    (pt_runtime.cpp prepareScene compares floats 18..35 bit for bit).
+    (pt_scene_prep.cpp prepareScene compares floats 18..35 bit for bit).
 
 Used by tests/test_material_scene.py (the oracle alone: the inputs exercise what they claim),
 tests/test_gpu_materials.py (the frame kernels against the oracle, bit for bit) and
@@ -84,7 +84,7 @@ def with_materials(geometry: np.ndarray, palette: np.ndarray, ids: np.ndarray) -
 
 
 def table_ids(tris: np.ndarray) -> np.ndarray:
-    """The material id the runtime gives each triangle (pt_runtime.cpp prepareScene): distinct keys
+    """The material id the runtime gives each triangle (pt_scene_prep.cpp prepareScene): distinct keys
     (floats 18..35, bit for bit) numbered by their first appearance in triangle order."""
     keys = np.ascontiguousarray(np.asarray(tris, np.float32).reshape(-1, 36)[:, 18:36]).view(np.uint32)
     seen, out = {}, np.empty(keys.shape[0], np.int64)

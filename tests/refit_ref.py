@@ -9,7 +9,7 @@ glm's). That is what every builder of the reference and of scene.cpp stores for 
 (test_refit_ref.py: bit for bit), so the contract of an update is equality with a fresh upload of
 (updated_tris, refit_nodes), and with the oracle on those arrays.
 
-A child id <= 0 or >= nNodes is absent (pt_runtime.cpp encodeWideTree); an internal node without
+A child id <= 0 or >= nNodes is absent (pt_scene_prep.cpp encodeWideTree); an internal node without
 children keeps its box; unreachable nodes keep theirs.
 """
 import functools

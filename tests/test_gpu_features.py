@@ -293,6 +293,14 @@ def test_error_paths():
         bad[1, 3], bad[1, 4] = 4, 10  # leaf range past the triangle array
         with pytest.raises(_native.PtError):
             r.upload_scene(np.zeros((3, 36), np.float32), bad)
+        cycle = np.zeros((2, 12), np.float32)
+        cycle[1, 0] = 1  # the root is its own left child
+        with pytest.raises(_native.PtError, match=r"not a tree \(cycle\)"):
+            r.upload_scene(np.zeros((3, 36), np.float32), cycle)
+        large = np.zeros((2, 12), np.float32)
+        large[1, 3], large[1, 4] = 33, 0  # a leaf of 33 triangles
+        with pytest.raises(_native.PtError, match="leaf larger than 32 triangles at node 1"):
+            r.upload_scene(np.zeros((40, 36), np.float32), large)
     with pytest.raises(_native.PtError):
         Renderer(16, 16, device=99)
 

@@ -5,7 +5,7 @@ the oracle, bit for bit on the whole 96x64 image.
 Every other scene of the GPU suite has one or two materials whose subsurface, specularTint,
 anisotropic, sheen and sheenTint are 0 and, under Disney and MIS, no emitter: there a wrong term
 of pt_device.h's BRDF is multiplied by 0, the camera hit's emission (pt_regen.hip camEmission,
-pt_kernels.hip Le0) is 0 + Lo, and the material table (pt_runtime.cpp prepareScene, pt_trace.h
+pt_kernels.hip Le0) is 0 + Lo, and the material table (pt_scene_prep.cpp prepareScene, pt_trace.h
 finishHit) has ids 0 and 1. Here every parameter, the emission terms and ids up to 399 decide the
 bits of the image (tests/test_material_scene.py measures that on the oracle).
 
