@@ -53,7 +53,9 @@ extern "C" {
                                 (pt_trace_closest_range, pt_trace_occluded, pt_trace_closest_device,
                                 pt_trace_occluded_device): new symbols only, the version stays;
                              13, additive: geometry updated in place (pt_update_geometry,
-                                pt_update_geometry_device, pt_download_node_boxes): new symbols only */
+                                pt_update_geometry_device, pt_download_node_boxes): new symbols only;
+                             13, additive: the integrators as a ray query (pt_radiance_device, pt_radiance) and
+                                the frames' camera rays as such rays (pt_camera_rays_device): new symbols only */
 
 /* error codes */
 #define PT_OK 0
@@ -338,6 +340,44 @@ int pt_trace_occluded(pt_ctx* ctx, const float* rays, const float* tmax, int n, 
 int pt_trace_closest_device(pt_ctx* ctx, const void* d_rays /* n x 6 f32 */, const void* d_tmax /* n f32 or NULL */, int n,
                             void* d_t /* n f32 */, void* d_tri /* n i32 */);
 int pt_trace_occluded_device(pt_ctx* ctx, const void* d_rays, const void* d_tmax, int n, void* d_occ /* n u8: 0 / 1 */);
+
+/* Radiance along caller-supplied rays: one sample of the context's integrator (PT_LAMBERT_O, PT_DISNEY_UNIFORM_D
+ * or PT_DISNEY_MIS_SOBOL_IS, with the context's max_bounce) along each ray, for cameras the frame kernels do
+ * not have (panorama, fisheye, thin lens), radiance probes, light-map bakes and a caller's own secondary
+ * rays. For ray k = (o, d) with id (px, py) = d_ids[k] and sample index s = sampleIndex:
+ *   - d_ids NULL: the id is (k & 4095, k >> 12), which gives every k < 2^23 its own seed
+ *     (px * 1973 + py * 9277 is injective for px < 9277, py < 1973);
+ *   - d is used as given: the caller normalises it, and t is in units of |d|;
+ *   - (t, tri) is pt_trace_closest's result for the ray. A miss: out = (SampleHdr of the environment
+ *     along d, 2147483648.f), black without an environment. A hit: the hit record the frame kernels
+ *     compute for a camera hit, then the integrator;
+ *   - the path's RNG state is that of seed (px * 1973 + py * 9277 + s * 26699) | 1 (pass1.fsh main) after
+ *     two discarded rand() draws: what a frame's pixel (px, py) of sample s holds once its jittered
+ *     camera ray exists. For PT_DISNEY_MIS_SOBOL_IS the Sobol index is s and the Cranley-Patterson shift
+ *     that of (px, py);
+ *   - out.rgb = Le(first hit) + Li, the sum a frame adds to its running mean; out.w = t.
+ * The contract: if ray k is bit for bit the ray pt_camera_rays_device writes for (px, py, s) of some
+ * camera and image size, out[k].rgb is bit for bit the sample a frame with sample index s (frameCounter *
+ * sample_world + sample_rank) gives that pixel -- whatever k, n, the other rays and this context's own
+ * width and height are.
+ * One sample per call: fold several calls with the running-mean weights 1 / (i + 1). The context's flags
+ * apply as they do to the ray queries (PT_FLAG_NO_CULL, PT_FLAG_REFERENCE_TREE, PT_FLAG_COUNT_FETCHES; the
+ * default is the runtime's tree with the reference check). pt_frame_stats is not touched. With
+ * n_devices > 1 the call runs on device_ids[0]. PT_E_NOSCENE before pt_upload_scene and on a
+ * PT_BASIC_CPU_COMPAT context; PT_E_INVALID for n < 0 or a NULL required pointer (rays, out) with n > 0;
+ * n == 0 is PT_OK and reads and writes nothing.
+ * The device form is asynchronous, in stream order on the context's stream as the device ray queries
+ * are (after any pt_upload_scene or pt_update_geometry issued before it), allocates nothing in the steady
+ * state and may overlap frames in flight; it shares the ray queries' stack overflow area, so it takes its
+ * turn among them. d_out must be 16-byte aligned. The host form stages in and out and is synchronous. */
+int pt_radiance_device(pt_ctx* ctx, const void* d_rays /* n x 6 f32 */, const void* d_ids /* n x 2 i32 or NULL */,
+                       int n, uint32_t sampleIndex, void* d_out /* n x 4 f32: r, g, b, t */);
+int pt_radiance(pt_ctx* ctx, const float* rays, const int* ids, int n, uint32_t sampleIndex, float* out);
+/* The frame kernels' camera rays of sample sampleIndex, jitter included, for every pixel of the context's
+ * width x height: ray py * width + px = (eye, the pixel's jittered direction), id = (px, py). Asynchronous on
+ * the context's stream. PT_E_INVALID on a PT_BASIC_CPU_COMPAT context or for a NULL d_rays. */
+int pt_camera_rays_device(pt_ctx* ctx, const float eye[3], const float cameraRotate[16], uint32_t sampleIndex,
+                          void* d_rays /* width*height x 6 f32 */, void* d_ids /* width*height x 2 i32, nullable */);
 
 /* Accumulation buffer access (lastFrame texture, main.cpp:763-764). */
 int pt_download_accum(pt_ctx* ctx, float* accum_rgba);   /* host or device memory, width*height*4 f32 */

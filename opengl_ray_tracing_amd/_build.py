@@ -48,7 +48,8 @@ _HOST = [CSRC / "pt_runtime.h", CSRC / "pt_frame.h", CSRC / "pt_kernels.h", INCL
 _PREP = [CSRC / "pt_scene_prep.h", CSRC / "pt_kernels.h"]  # the host-only scene preparation (no context, no HIP call)
 
 SOURCES = {
-    "pt_kernels.o": ("hip", CSRC / "pt_kernels.hip", [*_FRAME, INCLUDE / "pt_scene.h"]),
+    "pt_kernels.o": ("hip", CSRC / "pt_kernels.hip", [*_FRAME, CSRC / "pt_paths.h", INCLUDE / "pt_scene.h"]),
+    "pt_radiance.o": ("hip", CSRC / "pt_radiance.hip", [*_FRAME, CSRC / "pt_paths.h"]),
     "pt_regen.o": ("hip", CSRC / "pt_regen.hip", _FRAME),
     "pt_primary.o": ("hip", CSRC / "pt_primary.hip", _FRAME),
     "pt_guides.o": ("hip", CSRC / "pt_guides.hip", _FRAME),

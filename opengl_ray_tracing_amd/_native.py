@@ -13,7 +13,7 @@ from . import _build
 
 _lib = None
 
-ABI_VERSION = 13  # include/pt_abi.h PT_ABI_VERSION (the ranged ray queries are additive symbols: still 13)
+ABI_VERSION = 13  # include/pt_abi.h PT_ABI_VERSION (the ranged ray queries, the geometry update and the radiance query are additive symbols: still 13)
 # an older tuning build (tools/tune.py A/B against a previous round's library) loads when its structs
 # match: ABI 7 only added pt_unpack_ranks, ABI 8 the guide buffers and the denoiser, ABI 9 the
 # temporal resolve, ABI 10 the sample moments and the variance-guided filter, ABI 11 the
@@ -116,6 +116,9 @@ SIGNATURES = {
     "pt_trace_occluded": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_int, C.POINTER(C.c_uint8)]),
     "pt_trace_closest_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "pt_trace_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "pt_radiance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]),
+    "pt_radiance": (C.c_int, [C.c_void_p, c_float_p, c_int_p, C.c_int, C.c_uint32, c_float_p]),
+    "pt_camera_rays_device": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pt_build_bvh_device": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, c_float_p, C.c_int, c_int_p, c_int_p]),
     "pt_download_accum": (C.c_int, [C.c_void_p, c_float_p]),
     "pt_upload_accum": (C.c_int, [C.c_void_p, c_float_p]),

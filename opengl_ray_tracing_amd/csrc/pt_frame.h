@@ -104,12 +104,23 @@ __device__ __forceinline__ V3 cameraDir(const float* M, int W, int H, int px, in
   return normalize(dir);
 }
 // seed and jittered camera ray of a frame's sample of pixel (px, py); seed is left as the path needs it
-__device__ __forceinline__ V3 cameraRay(const RenderParams& p, uint32_t sampleIndex, int px, int py, uint32_t& seed) {
-  const int W = p.width, H = p.height;
+__device__ __forceinline__ V3 cameraRay(const float* M, int W, int H, uint32_t sampleIndex, int px, int py,
+                                        uint32_t& seed) {
   seed = pixelSeed(px, py, sampleIndex);
   float ax = (randf(seed) - 0.5f) / (float)W;
   float ay = (randf(seed) - 0.5f) / (float)H;
-  return cameraDir(p.cam, W, H, px, py, ax, ay);
+  return cameraDir(M, W, H, px, py, ax, ay);
+}
+__device__ __forceinline__ V3 cameraRay(const RenderParams& p, uint32_t sampleIndex, int px, int py, uint32_t& seed) {
+  return cameraRay(p.cam, p.width, p.height, sampleIndex, px, py, seed);
+}
+// the path's RNG state of a ray taken as pixel (px, py)'s camera ray of that sample: cameraRay's seed after
+// its two jitter draws (the radiance query, pt_radiance.hip)
+__device__ __forceinline__ uint32_t pathSeed(int px, int py, uint32_t sampleIndex) {
+  uint32_t seed = pixelSeed(px, py, sampleIndex);
+  (void)randf(seed);
+  (void)randf(seed);
+  return seed;
 }
 
 // ------------------------------------------------------------ frame and store

@@ -307,6 +307,43 @@ struct QueryParams {
   int ovfDepth;
 };
 
+// Radiance along caller-supplied rays (pt_radiance.hip radianceKernel; pt_abi.h pt_radiance_device): one
+// sample of the context's integrator along ray k, seeded as pixel ids[k] of sample sampleIndex
+struct RadianceParams {
+  SceneView scene;
+  Env env;
+  const float* rays;   // n x 6 (origin, direction)
+  const int* ids;      // n x 2 (px, py); null: (k & 4095, k >> 12)
+  int n;
+  uint32_t sampleIndex;
+  int maxBounce;
+  float4* out;         // n x (r, g, b, t); a miss (sky, PT_INF)
+  int* ovf;            // the queries' traversal stack overflow (per thread ovfDepth ints), may be null
+  int ovfDepth;
+};
+// waves per SIMD the radiance kernel is compiled for, per integrator
+#ifndef PT_RADIANCE_WAVES_LAMBERT
+#define PT_RADIANCE_WAVES_LAMBERT 4
+#endif
+#ifndef PT_RADIANCE_WAVES_DISNEY
+#define PT_RADIANCE_WAVES_DISNEY 3
+#endif
+#ifndef PT_RADIANCE_WAVES_MIS
+#define PT_RADIANCE_WAVES_MIS 3
+#endif
+hipError_t launchRadiance(const RadianceParams& p, int integrator, int grid, hipStream_t s, bool cull);
+// The frame kernels' camera rays of one sample (pt_frame.h cameraRay) for every pixel of a width x height
+// image: ray py * width + px = (eye, direction) into rays (6 floats each), (px, py) into ids (may be null)
+struct CameraRaysParams {
+  int width, height;
+  uint32_t sampleIndex;
+  float eye[3];
+  float cam[16];
+  float* rays;
+  int* ids;
+};
+hipError_t launchCameraRays(const CameraRaysParams& p, hipStream_t s);
+
 // BasicRayTracingWithC++ (pt_basic.hip basicKernel): one sample k of every pixel
 constexpr int BASIC_MAX_DEPTH = 31;  // pathTracing vertices kept for the fold (the reference's cutoff is 8)
 struct BasicParams {

@@ -57,6 +57,13 @@ static inline size_t sceneBytes(int nTri, int nDevNodes) {
 // the scene's records outgrow the L2s by far (pt_kernels.h PT_WIDE_SCENE_MB)
 static inline bool largeScene(const pt_ctx* ctx) { return ctx->sceneBytes > ((size_t)PT_WIDE_SCENE_MB << 20); }
 
+// the env sample table by rows (PT_ROW_TABLE) for a launch of the regen kernel or of a lock-step one (the
+// megakernel, the radiance query)
+static inline bool rowTable(const pt_ctx* ctx, bool regen) {
+  return PT_ROW_TABLE > 0 && (PT_ROW_TABLE == 2 || !regen) &&
+         (size_t)ctx->hdrW * ctx->hdrH * sizeof(uint32_t) > ((size_t)4 << 20);
+}
+
 static inline int defaultBounce(int integ) {
   switch (integ) {
     case PT_LAMBERT_O: return 2;           // O:385
@@ -173,8 +180,7 @@ static inline FramePlan planFrame(const pt_ctx* ctx, bool solo, int want) {
   // fetch and camera-ray pass; on small trees with the whole tree in LDS)
   f.wide = f.wideScene || (f.regen && f.regenAll);
   f.walk4 = f.wide && ctx->fast4Ready && !(c.flags & PT_FLAG_REFERENCE_TREE);
-  f.rowTable = PT_ROW_TABLE > 0 && (PT_ROW_TABLE == 2 || !f.regen) &&
-               (size_t)ctx->hdrW * ctx->hdrH * sizeof(uint32_t) > ((size_t)4 << 20);
+  f.rowTable = rowTable(ctx, f.regen);
   f.envNt = largeScene(ctx) ? 1 : 0;
   const int group = std::max(1, PT_TILE_GROUP);
   f.ordered = !f.regen && !f.count && !(c.flags & PT_FLAG_NO_TILE_ORDER) &&

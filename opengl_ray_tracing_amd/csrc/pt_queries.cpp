@@ -1,12 +1,17 @@
 // pt_queries.cpp -- the ray queries of the C-ABI in include/pt_abi.h: closest hit and occlusion, with or
 // without a bound per ray, on device memory in stream order or on host arrays. One kernel
-// (pt_query.hip queryKernel) and one host path (queryHost) serve every entry point.
+// (pt_query.hip queryKernel) and one host path (queryHost) serve every entry point. And the radiance
+// query (pt_radiance_device, pt_radiance: pt_radiance.hip radianceKernel), which shares the queries'
+// overflow area and their one-at-a-time ordering, with the camera rays it is specified against
+// (pt_camera_rays_device).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 
 #include "pt_abi.h"
 #include "pt_kernels.h"
+#include "pt_plan.h"
 #include "pt_runtime.h"
 
 using namespace pt;
@@ -31,17 +36,38 @@ static int ensureQuery(pt_ctx* ctx, int* ovfDepth) {
   return PT_OK;
 }
 
+// What every launch of a query does before its kernel: the device, the overflow area (*ovfDepth entries per
+// thread, 0: none), and its turn -- the area is one query's at a time, so behind the last one on another stream
+static int beginQuery(pt_ctx* ctx, int* ovfDepth) {
+  CK(hipSetDevice(ctx->cfg.device_id));
+  if (int rc = ensureQuery(ctx, ovfDepth)) return rc;
+  if (ctx->queryIssued && ctx->queryStream != ctx->stream) CK(hipStreamWaitEvent(ctx->stream, ctx->queryDone, 0));
+  return PT_OK;
+}
+// ... and after it
+static int endQuery(pt_ctx* ctx) {
+  CK(hipEventRecord(ctx->queryDone, ctx->stream));
+  ctx->queryStream = ctx->stream;
+  ctx->queryIssued = true;
+  return PT_OK;
+}
+// the scene as a query walks it: the runtime's own tree, results reference-exact (pt_trace.h refReachable)
+static SceneView queryScene(const pt_ctx* ctx) {
+  SceneView s = sceneView(ctx);
+  s.fast = ctx->fastReady && !(ctx->cfg.flags & (PT_FLAG_REFERENCE_TREE | PT_FLAG_COUNT_FETCHES)) ? 1 : 0;
+  return s;
+}
+static bool queryCull(const pt_ctx* ctx) { return !(ctx->cfg.flags & (PT_FLAG_NO_CULL | PT_FLAG_COUNT_FETCHES)); }
+static int queryGrid(const pt_ctx* ctx, int n) {
+  return (int)std::min<long>(((long)n + BLOCK - 1) / BLOCK, (long)queryGridCap(ctx));
+}
+
 // One query of n > 0 rays in device memory, enqueued on the context's stream
 static int queryOne(pt_ctx* ctx, const void* d_rays, const void* d_tmax, int n, void* d_t, void* d_tri, void* d_occ) {
-  CK(hipSetDevice(ctx->cfg.device_id));
   int ovfDepth = 0;
-  if (int rc = ensureQuery(ctx, &ovfDepth)) return rc;
-  // the overflow area is one query's at a time: behind the last one on another stream
-  if (ctx->queryIssued && ctx->queryStream != ctx->stream) CK(hipStreamWaitEvent(ctx->stream, ctx->queryDone, 0));
+  if (int rc = beginQuery(ctx, &ovfDepth)) return rc;
   QueryParams p;
-  p.scene = sceneView(ctx);
-  // the runtime's own tree, results reference-exact (pt_trace.h refReachable)
-  p.scene.fast = ctx->fastReady && !(ctx->cfg.flags & (PT_FLAG_REFERENCE_TREE | PT_FLAG_COUNT_FETCHES)) ? 1 : 0;
+  p.scene = queryScene(ctx);
   p.rays = static_cast<const float*>(d_rays);
   p.tmax = static_cast<const float*>(d_tmax);
   p.n = n;
@@ -50,13 +76,8 @@ static int queryOne(pt_ctx* ctx, const void* d_rays, const void* d_tmax, int n, 
   p.occ = static_cast<uint8_t*>(d_occ);
   p.ovf = ovfDepth ? ctx->d_queryOvf : nullptr;
   p.ovfDepth = ovfDepth;
-  const bool cull = !(ctx->cfg.flags & (PT_FLAG_NO_CULL | PT_FLAG_COUNT_FETCHES));
-  const int grid = (int)std::min<long>(((long)n + BLOCK - 1) / BLOCK, (long)queryGridCap(ctx));
-  CK(launchQuery(p, grid, ctx->stream, d_occ != nullptr, cull));
-  CK(hipEventRecord(ctx->queryDone, ctx->stream));
-  ctx->queryStream = ctx->stream;
-  ctx->queryIssued = true;
-  return PT_OK;
+  CK(launchQuery(p, queryGrid(ctx, n), ctx->stream, d_occ != nullptr, queryCull(ctx)));
+  return endQuery(ctx);
 }
 
 // the argument checks the entry points share: PT_OK with *run = false when there is nothing to do
@@ -80,18 +101,25 @@ int pt_trace_occluded_device(pt_ctx* ctx, const void* d_rays, const void* d_tmax
   return run ? queryOne(ctx, d_rays, d_tmax, n, nullptr, nullptr, d_occ) : PT_OK;
 }
 
+// the host forms' staging of at least `floats` floats; the stream is synchronised when a host form returns,
+// so a staging that grows is not in use
+static int ensureStage(pt_ctx* ctx, size_t floats) {
+  if (floats > ctx->queryStageFloats) {
+    dfree(ctx->d_queryStage);
+    ctx->queryStageFloats = 0;
+    CK(hipMalloc(&ctx->d_queryStage, floats * sizeof(float)));
+    ctx->queryStageFloats = floats;
+  }
+  return PT_OK;
+}
+
 // The host forms: the rays (and bounds) staged in, the device query, the results staged out, all on the
 // context's stream, which is synchronised on return -- the staging is never in flight between calls.
 // Staging per ray: 6 floats of ray, the bound, t, the triangle (the occlusion bytes take t's place).
 static int queryHost(pt_ctx* ctx, const float* rays, const float* tmax, int n, float* t_out, int* tri_out,
                      uint8_t* occ_out) {
   CK(hipSetDevice(ctx->cfg.device_id));
-  if ((size_t)n > ctx->queryStageRays) {
-    dfree(ctx->d_queryStage);
-    ctx->queryStageRays = 0;
-    CK(hipMalloc(&ctx->d_queryStage, (size_t)n * 9 * sizeof(float)));
-    ctx->queryStageRays = (size_t)n;
-  }
+  if (int rc = ensureStage(ctx, (size_t)n * 9)) return rc;
   float* dRays = ctx->d_queryStage;
   float* dTmax = dRays + (size_t)n * 6;
   float* dT = dTmax + n;
@@ -131,4 +159,65 @@ int pt_trace_occluded(pt_ctx* ctx, const float* rays, const float* tmax, int n, 
   bool run;
   if (int rc = queryArgs(ctx, n, rays && occ_out, &run)) return rc;
   return run ? queryHost(ctx, rays, tmax, n, nullptr, nullptr, occ_out) : PT_OK;
+}
+
+// ------------------------------------------------------------ radiance along caller-supplied rays
+// One sample of the context's integrator along n > 0 rays in device memory, enqueued on the context's stream
+static int radianceOne(pt_ctx* ctx, const void* d_rays, const void* d_ids, int n, uint32_t sampleIndex, void* d_out) {
+  int ovfDepth = 0;
+  if (int rc = beginQuery(ctx, &ovfDepth)) return rc;
+  RadianceParams p;
+  p.scene = queryScene(ctx);
+  p.env = envView(ctx, rowTable(ctx, false), largeScene(ctx) ? 1 : 0);  // as a megakernel frame reads it
+  p.rays = static_cast<const float*>(d_rays);
+  p.ids = static_cast<const int*>(d_ids);
+  p.n = n;
+  p.sampleIndex = sampleIndex;
+  p.maxBounce = maxBounce(ctx->cfg);
+  p.out = static_cast<float4*>(d_out);
+  p.ovf = ovfDepth ? ctx->d_queryOvf : nullptr;
+  p.ovfDepth = ovfDepth;
+  CK(launchRadiance(p, ctx->cfg.integrator, queryGrid(ctx, n), ctx->stream, queryCull(ctx)));
+  return endQuery(ctx);
+}
+
+int pt_radiance_device(pt_ctx* ctx, const void* d_rays, const void* d_ids, int n, uint32_t sampleIndex, void* d_out) {
+  bool run;
+  if (int rc = queryArgs(ctx, n, d_rays && d_out, &run)) return rc;
+  return run ? radianceOne(ctx, d_rays, d_ids, n, sampleIndex, d_out) : PT_OK;
+}
+
+// The host form, staged like queryHost: per ray 6 floats of ray, 2 ints of id and 4 floats of result
+int pt_radiance(pt_ctx* ctx, const float* rays, const int* ids, int n, uint32_t sampleIndex, float* out) {
+  bool run;
+  if (int rc = queryArgs(ctx, n, rays && out, &run)) return rc;
+  if (!run) return PT_OK;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  if (int rc = ensureStage(ctx, (size_t)n * 12)) return rc;
+  float* dRays = ctx->d_queryStage;
+  int* dIds = reinterpret_cast<int*>(dRays + (size_t)n * 6);
+  float* dOut = dRays + (size_t)n * 8;
+  CK(hipMemcpyAsync(dRays, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (ids) CK(hipMemcpyAsync(dIds, ids, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  if (int rc = radianceOne(ctx, dRays, ids ? dIds : nullptr, n, sampleIndex, dOut)) return rc;
+  CK(hipMemcpyAsync(out, dOut, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipStreamSynchronize(ctx->stream));
+  return PT_OK;
+}
+
+int pt_camera_rays_device(pt_ctx* ctx, const float eye[3], const float cameraRotate[16], uint32_t sampleIndex,
+                          void* d_rays, void* d_ids) {
+  if (!ctx || !eye || !cameraRotate || !d_rays) return PT_E_INVALID;
+  if (ctx->cfg.integrator == PT_BASIC_CPU_COMPAT) return fail(ctx, PT_E_INVALID, "not a GL integrator's context");
+  CK(hipSetDevice(ctx->cfg.device_id));
+  CameraRaysParams p;
+  p.width = ctx->cfg.width;
+  p.height = ctx->cfg.height;
+  p.sampleIndex = sampleIndex;
+  std::memcpy(p.eye, eye, sizeof(p.eye));
+  std::memcpy(p.cam, cameraRotate, sizeof(p.cam));
+  p.rays = static_cast<float*>(d_rays);
+  p.ids = static_cast<int*>(d_ids);
+  CK(launchCameraRays(p, ctx->stream));
+  return PT_OK;
 }

@@ -144,6 +144,24 @@ SceneView sceneView(const pt_ctx* ctx) {
   return s;
 }
 
+// the uploaded environment as the kernels read it (rowTable: the sample table by rows, nt: Env::nt -- pt_plan.h)
+Env envView(const pt_ctx* ctx, bool rowTable, int nt) {
+  Env e;
+  e.hdr = ctx->d_hdr;
+  e.cache = ctx->d_cache;
+  e.hdr8 = ctx->d_hdr8;
+  e.cache4 = ctx->d_cache4;
+  e.cacheRow = rowTable ? ctx->d_cacheRow : nullptr;
+  e.cacheY = rowTable ? ctx->d_cacheY : nullptr;
+  e.trig = ctx->d_trig;
+  e.light = ctx->d_light;  // every scene: c5 too (4.25 vs 4.49 ms without the table, round 6)
+  e.w = ctx->hdrW;
+  e.h = ctx->hdrH;
+  e.res = ctx->hdrW;
+  e.nt = nt;
+  return e;
+}
+
 // rank's share of a world-way screen-tile split of the context's image (the one place a Share is filled)
 Share shareOf(const pt_ctx* ctx, int rank, int world) {
   return makeShare(ctx->cfg.width, ctx->cfg.height, ctx->shardSize, rank, world);
@@ -436,18 +454,7 @@ static RenderParams fillParams(const pt_ctx* ctx, const FramePlan& pl, const Fra
   RenderParams p;
   std::memset(&p, 0, sizeof(p));
   p.scene = sceneView(ctx);
-  p.env.hdr = ctx->d_hdr;
-  p.env.cache = ctx->d_cache;
-  p.env.hdr8 = ctx->d_hdr8;
-  p.env.cache4 = ctx->d_cache4;
-  p.env.cacheRow = pl.rowTable ? ctx->d_cacheRow : nullptr;
-  p.env.cacheY = pl.rowTable ? ctx->d_cacheY : nullptr;
-  p.env.trig = ctx->d_trig;
-  p.env.light = ctx->d_light;  // every scene: c5 too (4.25 vs 4.49 ms without the table, round 6)
-  p.env.w = ctx->hdrW;
-  p.env.h = ctx->hdrH;
-  p.env.res = ctx->hdrW;
-  p.env.nt = pl.envNt;
+  p.env = envView(ctx, pl.rowTable, pl.envNt);
   // the share's six fields, the rank's wave tiles (== ctx->numItems) and colStride: per-frame buffers are indexed
   // by the pixel's slot in this context's share (pt_frame.h slotOf), so a 1/N share's colour and camera-ray
   // buffers are 1/N of a frame (c5 at N = 8, 16 frames per launch: ~2.4 GB of colour buffers instead of ~19 GB)

@@ -1,7 +1,7 @@
 // pt_runtime.h -- what the host files of the C-ABI share: the context, the error helpers, and the
 // functions one file defines and another calls. The files, by subject: pt_context.cpp (context life,
 // streams, stats), pt_scene_upload.cpp (scene upload, geometry update), pt_env.cpp (environment, BASIC
-// state), pt_runtime.cpp (the frame path), pt_queries.cpp (ray queries), pt_accum.cpp (accumulation
+// state), pt_runtime.cpp (the frame path), pt_queries.cpp (ray and radiance queries), pt_accum.cpp (accumulation
 // access, adaptive sampling, pack and unpack), pt_group.cpp (the in-process device group) and
 // pt_post.cpp (the display post-processing). Internal: not installed.
 // (The launch policy of the frame path -- pure functions of this context -- is pt_plan.h; the
@@ -197,8 +197,8 @@ struct pt_ctx {
   int shardSize = 32, shardsX = 0, shardsY = 0, numItems = 0, perQueue = 0;
   // scratch for tonemap
   float* d_rgb = nullptr;
-  // The ray queries on device memory (pt_trace_closest_device, pt_trace_occluded_device and their host
-  // forms): their own stack overflow area, sized at first use for the largest grid a query launches and
+  // The ray queries on device memory (pt_trace_closest_device, pt_trace_occluded_device, pt_radiance_device and
+  // their host forms): their own stack overflow area, sized at first use for the largest grid a query launches and
   // for the tree depth of the scene (again after an upload that deepens it), so a query
   // never aliases a frame in flight (d_ovf) and allocates nothing in the steady state. queryDone is
   // recorded behind every query: a query on another stream (pt_set_stream since) waits for it -- the
@@ -208,8 +208,8 @@ struct pt_ctx {
   hipEvent_t queryDone = nullptr;
   hipStream_t queryStream = nullptr;  // the stream queryDone was last recorded on
   bool queryIssued = false;
-  float* d_queryStage = nullptr;      // the host forms' staging: rays, bounds and results of one call
-  size_t queryStageRays = 0;
+  float* d_queryStage = nullptr;      // the host forms' staging: rays, bounds (or ids) and results of one call
+  size_t queryStageFloats = 0;
   // guide buffers of the last pt_render_guides (valid for the scene version they were traced in) and
   // the denoiser's images: two ping-pong colour planes, their tone-mapped planes, and the
   // image the last pt_denoise wrote (one of the two, or the caller's)
@@ -331,6 +331,7 @@ static inline int fromPeer(pt_ctx* ctx, pt_ctx* p, int rc) {
 int joinPipe(pt_ctx* ctx);     // the caller's stream waits for the last pipelined frame's running-mean update
 int syncStreams(pt_ctx* ctx);  // every stream the context renders on, then its own: all work done
 SceneView sceneView(const pt_ctx* ctx);  // the uploaded scene as the kernels read it (fast is set per launch)
+Env envView(const pt_ctx* ctx, bool rowTable, int nt);  // the uploaded environment as the kernels read it
 Share shareOf(const pt_ctx* ctx, int rank, int world);  // rank's share of a world-way screen-tile split of the image
 PackParams packParams(const pt_ctx* ctx, int rank, int world);  // that share and its pixel slots
 int dropMoments(pt_ctx* ctx);   // the sample moments (and what adaptive sampling decided from them) are no longer valid

@@ -381,6 +381,59 @@ class Renderer:
         self._ck(self._lib.pt_trace_occluded_device(self._h, p[0], p[1], n, p[2]), "pt_trace_occluded_device")
         return out
 
+    def camera_rays_device(self, eye, camera_rotate, sample_index: int = 0, out_rays=None, out_ids=None):
+        """The frame kernels' camera rays of sample sample_index, jitter included, for every pixel of this
+        context's width x height (pt_camera_rays_device): ray py * width + px = (eye, direction), id =
+        (px, py). out_rays (w*h x 6 float32) and out_ids (w*h x 2 int32) are torch tensors or raw device
+        pointers as in trace_closest_device; not given, they are allocated as torch tensors on the context's
+        device. Asynchronous on the context's stream. Returns (out_rays, out_ids)."""
+        what = "camera_rays_device"
+        n = self.width * self.height
+        if out_rays is None or out_ids is None:
+            import torch
+            dev = f"cuda:{self.device}"
+            if out_rays is None:
+                out_rays = torch.empty((n, 6), dtype=torch.float32, device=dev)
+            if out_ids is None:
+                out_ids = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        _, p, _ = self._query_args(what, n, [("out_rays", out_rays, "float32", 6, True),
+                                             ("out_ids", out_ids, "int32", 2, True)])
+        e = np.ascontiguousarray(eye, np.float32)
+        r = np.ascontiguousarray(camera_rotate, np.float32).reshape(16)
+        self._ck(self._lib.pt_camera_rays_device(self._h, _fp(e), _fp(r), int(sample_index) & 0xFFFFFFFF, p[0], p[1]),
+                 "pt_camera_rays_device")
+        return out_rays, out_ids
+
+    def radiance_device(self, rays, ids=None, sample_index: int = 0, out=None, n=None):
+        """One sample of this context's integrator along each ray, on device memory (pt_radiance_device):
+        out[k] = (r, g, b, t) of ray k taken as the camera ray of pixel ids[k] = (px, py) of sample
+        sample_index (ids None: (k & 4095, k >> 12)); a ray equal to a frame's camera ray yields that frame's
+        sample bit for bit (include/pt_abi.h). rays (n x 6 float32), ids (n x 2 int32 or None) and out (n x 4
+        float32) are torch tensors or raw device pointers (ints, with n) as in trace_closest_device; out not
+        given is allocated with tensor rays. Asynchronous, in stream order on the context's stream. Returns out."""
+        what = "radiance_device"
+        specs = [("rays", rays, "float32", 6, True), ("ids", ids, "int32", 2, False)]
+        n, _, torch = self._query_args(what, n, specs)
+        if out is None and torch is not None and torch.is_tensor(rays):
+            out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        specs += [("out", out, "float32", 4, True)]
+        n, p, _ = self._query_args(what, n, specs)
+        self._ck(self._lib.pt_radiance_device(self._h, p[0], p[1], n, int(sample_index) & 0xFFFFFFFF, p[2]),
+                 "pt_radiance_device")
+        return out
+
+    def radiance(self, rays: np.ndarray, ids=None, sample_index: int = 0) -> np.ndarray:
+        """radiance_device on host arrays (pt_radiance): (n, 4) f32 -- r, g, b, t. Synchronous."""
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        i = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(-1, 2)
+        if i is not None and i.shape[0] != n:
+            raise ValueError(f"ids has {i.shape[0]} entries for {n} rays")
+        out = np.empty((n, 4), np.float32)
+        self._ck(self._lib.pt_radiance(self._h, _fp(r), None if i is None else i.ctypes.data_as(_native.c_int_p), n,
+                                       int(sample_index) & 0xFFFFFFFF, _fp(out)), "pt_radiance")
+        return out
+
     def build_bvh_device(self, tris: np.ndarray, leaf_size: int = 4):
         """pt_build_bvh_device: the GPU binned-SAH tree over tris (n x 36 f32) in the reference's
         node encoding. Returns (nodes (m x 12 f32, dummy node 0, root 1), order (n int32: input
