@@ -55,7 +55,10 @@ extern "C" {
                              13, additive: geometry updated in place (pt_update_geometry,
                                 pt_update_geometry_device, pt_download_node_boxes): new symbols only;
                              13, additive: the integrators as a ray query (pt_radiance_device, pt_radiance) and
-                                the frames' camera rays as such rays (pt_camera_rays_device): new symbols only */
+                                the frames' camera rays as such rays (pt_camera_rays_device): new symbols only;
+                             13, additive: materials updated in place (pt_update_materials,
+                                pt_update_materials_device, pt_material_count, pt_download_materials): new
+                                symbols only */
 
 /* error codes */
 #define PT_OK 0
@@ -229,7 +232,8 @@ int pt_upload_scene(pt_ctx* ctx, const float* tris, int nTriangles, const float*
  * PT_E_NOSCENE before pt_upload_scene and on a PT_BASIC_CPU_COMPAT context; PT_E_INVALID for a NULL
  * pointer, nTriangles != the uploaded count, stride < 18, a PT_FLAG_HOST_ACCEL context (that flag keeps
  * the GPU builder out) and the device form with n_devices > 1 (the host form updates every device).
- * Not part of this: adding, removing or re-sorting triangles, and material changes (pt_upload_scene). */
+ * Not part of this: adding, removing or re-sorting triangles (pt_upload_scene), and material changes
+ * (pt_update_materials). */
 int pt_update_geometry(pt_ctx* ctx, const float* verts, int nTriangles, int stride);
 /* the same from device memory of the context's device, read in stream order on the context's stream
  * (pt_set_stream): vertices animated on the GPU need no trip through the host */
@@ -237,6 +241,48 @@ int pt_update_geometry_device(pt_ctx* ctx, const void* d_verts, int nTriangles, 
 /* diagnostic: the uploaded tree's current boxes, nNodes x 6 f32 (lo, hi) by reference node id; entries
  * of unreachable nodes are unspecified. Synchronous. */
 int pt_download_node_boxes(pt_ctx* ctx, float* boxes);
+
+/* Materials updated in place: roughness, base colour, a light's emission, a whole new look, while the
+ * geometry stands still -- without a new pt_upload_scene, none of whose triangle re-layout, tree encode,
+ * copies, runtime-tree build, camera-ray bins and measured launch policies depends on materials. Record i
+ * = the 18 floats at mats + i * stride = Triangle_encoded floats 18..35 of triangle i of the last
+ * pt_upload_scene, same count, same order; stride >= 18 (a caller holding a whole Triangle_encoded array
+ * passes tris + 18 with stride 36); 4-byte alignment is all that is required. The context is then what
+ * pt_upload_scene(tris', nodes) would have made it, tris' = the current records with floats 18..35
+ * replaced: images of every integrator through every launch form, ray counts, PT_FLAG_COUNT_FETCHES
+ * counters, pt_radiance* and guide buffers are bit for bit a fresh upload's. So is the material table:
+ * distinct keys -- compared as 18 uint32, never as floats: +0 and -0 differ, two NaNs of the same bits
+ * are one key -- numbered by their first appearance in triangle order, whatever order the GPU's atomics
+ * land in (pt_materials.hip). Two floats are unspecified: a table entry is stored as floats 16..35 of
+ * its first triangle; no kernel reads the first two, pt_update_geometry leaves them stale, this update
+ * zeroes them, and pt_download_materials does not return them.
+ * Invalidated: the guides (their albedo is stale: pt_denoise* and pt_temporal_resolve return
+ * PT_E_INVALID until the next pt_render_guides), the temporal history, the moments and adaptive state:
+ * restart at frameCounter 0. Kept: the uploaded tree, the runtime tree and its 4-wide collapse, the
+ * traversal stack bound, the camera-ray bins and the measured launch policies -- no tree build runs.
+ * (The guides are invalidated by their own flag: the scene version that the guides and the camera-ray
+ * bins both compare against is not bumped, since the bins hold geometry only.) pt_frame_stats.upload_ms
+ * describes the update; accel_*, max_stack, tree4_nodes and runtime_tree are unchanged. Returns when the
+ * scene is ready; waits for the frames and queries in flight first.
+ * Memory, allocated at a scene's first material update and freed with the scene (a scene that never
+ * updates pays nothing): a material table with room for one material per triangle (80 bytes per
+ * triangle, in place of the upload's) and the update's own tables (12 bytes per triangle, 4 bytes per
+ * slot of a probe table of the next power of two >= 2 x nTriangles slots: 8 to 16 bytes per triangle,
+ * and the scan's scratch); the host form also stages its records (72 bytes per triangle).
+ * PT_E_NOSCENE before pt_upload_scene and on a PT_BASIC_CPU_COMPAT context; PT_E_INVALID for a NULL
+ * pointer, nTriangles != the uploaded count, stride < 18 and the device form with n_devices > 1 (the
+ * host form updates every device). PT_FLAG_HOST_ACCEL contexts are allowed: nothing is built. A failed
+ * call leaves the context usable. */
+int pt_update_materials(pt_ctx* ctx, const float* mats, int nTriangles, int stride);
+/* the same from device memory of the context's device, read in stream order on the context's stream
+ * (pt_set_stream): materials animated on the GPU need no trip through the host */
+int pt_update_materials_device(pt_ctx* ctx, const void* d_mats, int nTriangles, int stride);
+/* the number of distinct materials of the scene (the table's entries) */
+int pt_material_count(pt_ctx* ctx, int* nMats);
+/* diagnostic: the material table -- min(nMats, maxMats) entries of 18 f32 (Triangle_encoded floats
+ * 18..35) in table order -- and every triangle's id (nTriangles i32); either may be NULL, not both.
+ * Also on a scene that was never updated: the upload's table. Synchronous. */
+int pt_download_materials(pt_ctx* ctx, float* table, int maxMats, int* ids);
 
 /* Upload the HDR environment (replaces hdrMap/hdrCache textures,
  * ImportanceSampling_LowDiscrepancySequence/main.cpp:843-853). hdr = w x h x 3

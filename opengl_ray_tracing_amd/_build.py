@@ -60,6 +60,7 @@ SOURCES = {
     "pt_envcache.o": ("hip", CSRC / "pt_envcache.hip", _DEV),
     "pt_build.o": ("hip", CSRC / "pt_build.hip", [CSRC / "pt_kernels.h"]),
     "pt_refit.o": ("hip", CSRC / "pt_refit.hip", [CSRC / "pt_kernels.h"]),
+    "pt_materials.o": ("hip", CSRC / "pt_materials.hip", [CSRC / "pt_kernels.h"]),
     "pt_denoise.o": ("hip", CSRC / "pt_denoise.hip", [CSRC / "pt_atrous.h", *_DEV]),
     "pt_temporal.o": ("hip", CSRC / "pt_temporal.hip", _DEV),
     "pt_variance.o": ("hip", CSRC / "pt_variance.hip", [CSRC / "pt_atrous.h", *_DEV]),
@@ -206,6 +207,24 @@ def build_scene_prep_check(force: bool = False) -> Path:
     return SCENE_PREP_CHECK
 
 
+MATERIAL_TABLE_CHECK_SRC = ROOT / "tests" / "native" / "material_table_check.cpp"
+MATERIAL_TABLE_CHECK = ROOT / "tests" / "native" / "material_table_check"
+
+
+def build_material_table_check(force: bool = False, sanitize: bool = False) -> Path:
+    """Test infrastructure: the material-table function of the host-only scene preparation
+    (csrc/pt_scene_prep.cpp materialTable) on records read from a file (tests/native/material_table_check.cpp),
+    host-only like scene_prep_check. sanitize: a second program, built with -fsanitize=address,undefined,
+    whose self check runs without arguments."""
+    srcs = [MATERIAL_TABLE_CHECK_SRC, CSRC / "pt_scene_prep.cpp", CSRC / "scene.cpp"]
+    deps = [*srcs, *_PREP, CSRC / "pt_accel.h", CSRC / "pt_introsort.h", INCLUDE / "pt_scene.h"]
+    out = MATERIAL_TABLE_CHECK.with_name("material_table_check_san") if sanitize else MATERIAL_TABLE_CHECK
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"] if sanitize else []
+    if force or _stale(out, deps):
+        _run(["g++", *CXX_FLAGS, *san, "-Wno-unused-function", f"-I{INCLUDE}", f"-I{CSRC}", *map(str, srcs), "-o", str(out)])
+    return out
+
+
 def build_oracle(force: bool = False) -> Path:
     """Test infrastructure only (see oracle/pt_oracle.h)."""
     src = [ORACLE_DIR / "pt_oracle.c", ORACLE_DIR / "pt_oracle.h", ORACLE_DIR / "Makefile", INCLUDE / "pt_fmath.h"]
@@ -221,5 +240,6 @@ if __name__ == "__main__":
     build_plan_table(force="--force" in sys.argv)
     build_share_table(force="--force" in sys.argv)
     build_scene_prep_check(force="--force" in sys.argv)
+    build_material_table_check(force="--force" in sys.argv)
     print(LIB)
     print(ORACLE_LIB)

@@ -462,6 +462,33 @@ struct RefitParams {
 // before the records, the refit, the re-encode and after it
 hipError_t launchRefit(const RefitParams& p, const RefitTables& t, const int* hostStart, hipEvent_t* ev, hipStream_t s);
 
+// New materials in place (pt_materials.hip; pt_abi.h pt_update_materials): the table of distinct
+// materials and every triangle's id rewritten from the caller's material records. The tables below are
+// device memory, made at the first material update of a scene (pt_scene_upload.cpp makeMaterialTables).
+constexpr int MAT_KEY = 18;  // words of a material key: Triangle_encoded floats 18..35
+struct MaterialTables {
+  int* slots = nullptr;    // nSlots triangle indices, -1 = empty: the open-addressed table of the insert
+  int* slotOf = nullptr;   // per triangle: the slot its key ended in
+  int* flag = nullptr;     // per triangle: 1 = the first appearance of its key
+  int* rank = nullptr;     // per triangle: first appearances before it (the exclusive scan of flag)
+  int* count = nullptr;    // the number of distinct keys
+  void* scanTmp = nullptr; // hipcub scan scratch
+  size_t scanBytes = 0;
+  int nSlots = 0;          // a power of two >= 2 * nTri (materialSlots)
+  bool ready = false;
+};
+struct MaterialParams {
+  const float* mats;  // record i: the MAT_KEY floats at mats + i * stride
+  int stride;
+  int nTri;
+  float4* hitRec;     // [i][2].y takes triangle i's id; nothing else of the record is written
+  float4* table;      // room for nTri entries of MAT_F4 float4
+};
+int materialSlots(int nTri);
+hipError_t materialScanBytes(int nTri, size_t* bytes);
+// ev (nullable): 4 events recorded before the insert, the flags and scan, the scatter and after it
+hipError_t launchMaterials(const MaterialParams& p, const MaterialTables& t, hipEvent_t* ev, hipStream_t s);
+
 // calculateHdrCache on the device (pt_envcache.hip); scratch: 2*w*h + 2*w + 1 floats
 hipError_t launchHdrCache(const float* hdr, int w, int h, float4* cache, float* scratch, hipStream_t s);
 // hdr[k].w = cache[k].z, samp[k] = cache[k].xy (the Env render layout)

@@ -1,7 +1,7 @@
 // pt_runtime.h -- what the host files of the C-ABI share: the context, the error helpers, and the
 // functions one file defines and another calls. The files, by subject: pt_context.cpp (context life,
-// streams, stats), pt_scene_upload.cpp (scene upload, geometry update), pt_env.cpp (environment, BASIC
-// state), pt_runtime.cpp (the frame path), pt_queries.cpp (ray and radiance queries), pt_accum.cpp (accumulation
+// streams, stats), pt_scene_upload.cpp (scene upload, geometry and material updates), pt_env.cpp
+// (environment, BASIC state), pt_runtime.cpp (the frame path), pt_queries.cpp (ray and radiance queries), pt_accum.cpp (accumulation
 // access, adaptive sampling, pack and unpack), pt_group.cpp (the in-process device group) and
 // pt_post.cpp (the display post-processing). Internal: not installed.
 // (The launch policy of the frame path -- pure functions of this context -- is pt_plan.h; the
@@ -109,6 +109,11 @@ struct pt_ctx {
   RefitTables refit;
   float* d_updVerts = nullptr;  // nTri x 18 f32
   bool sceneFast = false;       // the upload prepared a runtime tree (SceneHost::fast)
+  // pt_update_materials: the update's device tables (pt_kernels.h MaterialTables) and, in place of the
+  // upload's d_mats, a table with room for one material per triangle, both made at the scene's first
+  // material update; the host form's staging of the records at its first use
+  MaterialTables matTab;
+  float* d_updMats = nullptr;   // nTri x 18 f32
   int nTri = 0, nNodes = 0, depth = 0, maxStack = 0;
   size_t sceneBytes = 0;  // the scene's records on the device (pt_plan.h sceneBytes, largeScene)
   // env
@@ -340,6 +345,7 @@ void foldLaunches(pt_ctx* ctx);  // every launch's device time folded into the t
 // pt_scene_upload.cpp
 void dropHistory(pt_ctx* ctx);  // the temporal history shows another scene or another light after an upload
 void freeRefit(pt_ctx* ctx);    // pt_update_geometry's device tables and staging belong to one upload
+void freeMaterialTables(pt_ctx* ctx);  // ... and so do pt_update_materials'
 // pt_env.cpp
 int ensureBasicImage(pt_ctx* ctx);  // the BASIC double image, allocated and zeroed on first use
 // pt_group.cpp

@@ -356,6 +356,34 @@ static void prepareAccel(const float* tris, int nTri, const float* nodes, int nN
   h.fast = true;
 }
 
+// The material table's numbering (pt_scene_prep.h): record i is the 18 floats at mats + i * stride,
+// compared as 18 uint32, never as floats
+int materialTable(const float* mats, int n, int stride, std::vector<int>& ids, std::vector<int>& first) {
+  ids.assign(std::max(n, 0), 0);
+  first.clear();
+  std::map<std::array<uint32_t, 18>, int> seen;
+  std::array<uint32_t, 18> lastKey{};
+  int lastId = 0;
+  for (int i = 0; i < n; i++) {
+    std::array<uint32_t, 18> key;
+    std::memcpy(key.data(), mats + (size_t)i * stride, sizeof(key));
+    int id;
+    if (i > 0 && key == lastKey) {  // meshes share one material: most lookups are this one
+      id = lastId;
+    } else if (auto it = seen.find(key); it == seen.end()) {
+      id = (int)seen.size();
+      seen.emplace(key, id);
+      first.push_back(i);
+    } else {
+      id = it->second;
+    }
+    lastKey = key;
+    lastId = id;
+    ids[i] = id;
+  }
+  return (int)first.size();
+}
+
 // host-side re-layout of the caller's arrays (pt_upload_scene); "" or the reason they are malformed
 std::string prepareScene(const float* tris, int nTri, const float* nodes, int nNodes, SceneHost& h, bool hostBuild) {
   h.nTri = nTri;
@@ -376,27 +404,16 @@ std::string prepareScene(const float* tris, int nTri, const float* nodes, int nN
   // material (Triangle_encoded floats 18..35, compared bit for bit) stored once
   h.hit.assign((size_t)nTri * HIT_F4, make_float4(0, 0, 0, 0));
   {
-    std::map<std::array<uint32_t, 18>, int> ids;
-    std::array<uint32_t, 18> lastKey{};
-    int lastId = 0;
+    std::vector<int> ids, first;
+    materialTable(tris + 18, nTri, 36, ids, first);
+    for (int i : first) {
+      const float* t = tris + (size_t)i * 36;
+      for (int k = 0; k < MAT_F4; k++) h.mats.push_back(make_float4(t[16 + 4 * k], t[17 + 4 * k], t[18 + 4 * k], t[19 + 4 * k]));
+    }
     for (int i = 0; i < nTri; i++) {
       const float* t = tris + (size_t)i * 36;
-      std::array<uint32_t, 18> key;
-      std::memcpy(key.data(), t + 18, sizeof(key));
-      int id;
-      if (i > 0 && key == lastKey) {  // meshes share one material: most lookups are this one
-        id = lastId;
-      } else if (auto it = ids.find(key); it == ids.end()) {
-        id = (int)ids.size();
-        ids.emplace(key, id);
-        for (int k = 0; k < MAT_F4; k++) h.mats.push_back(make_float4(t[16 + 4 * k], t[17 + 4 * k], t[18 + 4 * k], t[19 + 4 * k]));
-      } else {
-        id = it->second;
-      }
-      lastKey = key;
-      lastId = id;
       float fid;
-      std::memcpy(&fid, &id, 4);
+      std::memcpy(&fid, &ids[i], 4);
       float4* r = &h.hit[(size_t)i * HIT_F4];
       r[0] = make_float4(t[9], t[10], t[11], t[12]);
       r[1] = make_float4(t[13], t[14], t[15], t[16]);

@@ -62,6 +62,13 @@ struct SceneHost {
 // host-side re-layout of the caller's arrays (pt_upload_scene); "" or the reason they are malformed
 std::string prepareScene(const float* tris, int nTri, const float* nodes, int nNodes, SceneHost& h, bool hostBuild);
 
+// The material table of n material records (record i: the 18 floats at mats + i * stride, Triangle_encoded
+// floats 18..35): distinct keys, compared bit for bit as 18 uint32 (+0 and -0 differ, two NaNs of the same
+// bits are one key), numbered by their first appearance in triangle order. ids: each triangle's id;
+// first: per id the triangle it first appears at. Returns the number of distinct keys. prepareScene's
+// table, and what pt_update_materials must reproduce on the device (pt_materials.hip).
+int materialTable(const float* mats, int n, int stride, std::vector<int>& ids, std::vector<int>& first);
+
 // The runtime tree (reference encoding, root 1) collapsed to 4-wide nodes (pt_trace.h traceRay4).
 // Precondition: nodes is a builder's own tree (buildAccel's, or refNodes of the device builder's), never
 // the caller's array: children in range, every count and index a whole number below 2^31 -- a count in

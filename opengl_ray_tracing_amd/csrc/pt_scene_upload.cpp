@@ -1,7 +1,8 @@
-// pt_scene_upload.cpp -- pt_upload_scene and pt_update_geometry of the C-ABI in include/pt_abi.h:
-// what pt_scene_prep.cpp prepared on the host uploaded to every device of a context, the runtime's
-// own tree built there (pt_build.hip), and the geometry update that refits the uploaded tree in place
-// (pt_refit.hip); with them pt_download_node_boxes and pt_build_bvh_device.
+// pt_scene_upload.cpp -- pt_upload_scene, pt_update_geometry and pt_update_materials of the C-ABI in
+// include/pt_abi.h: what pt_scene_prep.cpp prepared on the host uploaded to every device of a context, the
+// runtime's own tree built there (pt_build.hip), the geometry update that refits the uploaded tree in place
+// (pt_refit.hip) and the material update that rebuilds the material table in place (pt_materials.hip);
+// with them pt_download_node_boxes, pt_download_materials and pt_build_bvh_device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -144,6 +145,7 @@ static int uploadScene(pt_ctx* ctx, const float* tris, const SceneHost& h) {
   ctx->depth = h.ref.depth;
   // what pt_update_geometry starts from: the boxes on the device, the topology on the host
   freeRefit(ctx);
+  freeMaterialTables(ctx);  // d_mats is the upload's exact table again
   ctx->refTopo = h.topo;
   ctx->refOrder = h.ref.ids;
   ctx->sceneFast = h.fast;
@@ -301,6 +303,148 @@ int pt_update_geometry_device(pt_ctx* ctx, const void* d_verts, int nTri, int st
   if (int rc = updateWait(ctx)) return rc;
   if (int rc = updateOne(ctx, static_cast<const float*>(d_verts), stride)) return rc;
   ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PT_OK;
+}
+
+// ------------------------------------------------------------ material update (pt_materials.hip)
+void freeMaterialTables(pt_ctx* ctx) {
+  MaterialTables& t = ctx->matTab;
+  dfree(t.slots);
+  dfree(t.slotOf);
+  dfree(t.flag);
+  dfree(t.rank);
+  dfree(t.count);
+  dfree(t.scanTmp);
+  t = MaterialTables{};
+  dfree(ctx->d_updMats);
+}
+
+// The update's device tables and a material table with room for one material per triangle, made at the
+// scene's first material update. The upload's table stays in place until all of them exist.
+static int makeMaterialTables(pt_ctx* ctx) {
+  if (ctx->matTab.ready) return PT_OK;
+  MaterialTables t;
+  const size_t n = (size_t)ctx->nTri;
+  t.nSlots = materialSlots(ctx->nTri);
+  float4* table = nullptr;
+  hipError_t e = materialScanBytes(ctx->nTri, &t.scanBytes);
+  if (e == hipSuccess) e = hipMalloc(&t.slots, (size_t)t.nSlots * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&t.slotOf, n * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&t.flag, n * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&t.rank, n * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&t.count, sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&t.scanTmp, std::max<size_t>(t.scanBytes, 16));
+  if (e == hipSuccess) e = hipMalloc(&table, n * MAT_F4 * sizeof(float4));
+  if (e != hipSuccess) {
+    dfree(t.slots); dfree(t.slotOf); dfree(t.flag); dfree(t.rank); dfree(t.count); dfree(t.scanTmp); dfree(table);
+    return fail(ctx, PT_E_NOMEM, std::string("pt_update_materials: tables: ") + hipGetErrorString(e));
+  }
+  dfree(ctx->d_mats);  // the update rewrites every entry in use
+  ctx->d_mats = table;
+  t.ready = true;
+  ctx->matTab = t;
+  return PT_OK;
+}
+
+// One context's update from nTri material records in its device memory; the caller has waited for the
+// frames and queries in flight. Invalidated: the temporal history, the moments and adaptive state
+// (as an upload does), and the guides -- by guidesValid alone: sceneVersion, which also makes the
+// camera-ray bins rebuild, stays, since the bins hold geometry only. The trees, the traversal stack
+// bound, the bins and the measured launch policies stay.
+static int updateMaterialsOne(pt_ctx* ctx, const float* d_mats, int stride) {
+  dropHistory(ctx);
+  if (int rc = dropMoments(ctx)) return rc;
+  ctx->guidesValid = false;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  if (int rc = makeMaterialTables(ctx)) return rc;
+  MaterialParams p;
+  p.mats = d_mats;
+  p.stride = stride;
+  p.nTri = ctx->nTri;
+  p.hitRec = ctx->d_hit;
+  p.table = ctx->d_mats;
+  // PT_MATERIAL_TIMES (environment; tools/material_time.py): the device time of each step, on stderr
+  const bool timed = std::getenv("PT_MATERIAL_TIMES") != nullptr;
+  struct StepEvents {  // destroyed on every way out
+    hipEvent_t ev[4] = {};
+    ~StepEvents() {
+      for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    }
+  } steps;
+  hipEvent_t* ev = steps.ev;
+  if (timed)
+    for (int k = 0; k < 4; k++) CK(hipEventCreate(&ev[k]));
+  CK(launchMaterials(p, ctx->matTab, timed ? ev : nullptr, ctx->stream));
+  int nMats = 0;
+  CK(hipMemcpyAsync(&nMats, ctx->matTab.count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipStreamSynchronize(ctx->stream));
+  ctx->nMats = nMats;
+  if (timed) {
+    float ms[3] = {};
+    for (int k = 0; k < 3; k++) CK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+    std::fprintf(stderr, "pt_update_materials: insert %.4f scan %.4f scatter %.4f ms, %d materials, %d slots\n", ms[0], ms[1],
+                 ms[2], nMats, ctx->matTab.nSlots);
+  }
+  return PT_OK;
+}
+
+static int materialArgs(pt_ctx* ctx, const void* mats, int nTri, int stride) {
+  if (!ctx || !mats) return PT_E_INVALID;
+  if (ctx->cfg.integrator == PT_BASIC_CPU_COMPAT || !ctx->d_bvh) return fail(ctx, PT_E_NOSCENE, "no scene");
+  if (nTri != ctx->nTri) return fail(ctx, PT_E_INVALID, "pt_update_materials: nTriangles differs from the uploaded scene's");
+  if (stride < MAT_KEY) return fail(ctx, PT_E_INVALID, "pt_update_materials: stride < 18 floats");
+  return PT_OK;
+}
+
+int pt_update_materials(pt_ctx* ctx, const float* mats, int nTri, int stride) {
+  if (int rc = materialArgs(ctx, mats, nTri, stride)) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (pt_ctx* m : members(ctx)) {
+    if (int rc = updateWait(m)) return fromPeer(ctx, m, rc);
+    CK(hipSetDevice(m->cfg.device_id));
+    if (!m->d_updMats) {
+      hipError_t e = hipMalloc(&m->d_updMats, (size_t)nTri * MAT_KEY * sizeof(float));
+      if (e != hipSuccess) return fail(ctx, PT_E_NOMEM, "pt_update_materials: record staging");
+    }
+    CK(hipMemcpy2DAsync(m->d_updMats, MAT_KEY * sizeof(float), mats, (size_t)stride * sizeof(float), MAT_KEY * sizeof(float),
+                        (size_t)nTri, hipMemcpyHostToDevice, m->stream));
+    if (int rc = updateMaterialsOne(m, m->d_updMats, MAT_KEY)) return fromPeer(ctx, m, rc);
+  }
+  ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PT_OK;
+}
+
+int pt_update_materials_device(pt_ctx* ctx, const void* d_mats, int nTri, int stride) {
+  if (int rc = materialArgs(ctx, d_mats, nTri, stride)) return rc;
+  if (!ctx->peers.empty()) return fail(ctx, PT_E_INVALID, "pt_update_materials_device: not on an n_devices > 1 context");
+  const auto t0 = std::chrono::steady_clock::now();
+  if (int rc = updateWait(ctx)) return rc;
+  if (int rc = updateMaterialsOne(ctx, static_cast<const float*>(d_mats), stride)) return rc;
+  ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PT_OK;
+}
+
+int pt_material_count(pt_ctx* ctx, int* nMats) {
+  if (!ctx || !nMats) return PT_E_INVALID;
+  if (ctx->cfg.integrator == PT_BASIC_CPU_COMPAT || !ctx->d_bvh) return fail(ctx, PT_E_NOSCENE, "no scene");
+  *nMats = ctx->nMats;
+  return PT_OK;
+}
+
+int pt_download_materials(pt_ctx* ctx, float* table, int maxMats, int* ids) {
+  if (!ctx || (!table && !ids) || maxMats < 0) return PT_E_INVALID;
+  if (ctx->cfg.integrator == PT_BASIC_CPU_COMPAT || !ctx->d_bvh) return fail(ctx, PT_E_NOSCENE, "no scene");
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const int n = table ? std::min(ctx->nMats, maxMats) : 0;
+  std::vector<float4> m((size_t)n * MAT_F4), h(ids ? (size_t)ctx->nTri * HIT_F4 : 0);
+  if (n) CK(hipMemcpyAsync(m.data(), ctx->d_mats, m.size() * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  if (ids) CK(hipMemcpyAsync(h.data(), ctx->d_hit, h.size() * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < n; k++)  // an entry holds Triangle_encoded floats 16..35: the material is its floats 2..19
+    std::memcpy(table + (size_t)k * MAT_KEY, reinterpret_cast<const float*>(&m[(size_t)k * MAT_F4]) + 2, MAT_KEY * sizeof(float));
+  if (ids)
+    for (int i = 0; i < ctx->nTri; i++) std::memcpy(&ids[i], &h[(size_t)i * HIT_F4 + 2].y, sizeof(int));
   return PT_OK;
 }
 

@@ -160,6 +160,7 @@ class Renderer:
         n = np.ascontiguousarray(nodes, np.float32).reshape(-1, 12)
         self._ck(self._lib.pt_upload_scene(self._h, _fp(t), t.shape[0], _fp(n), n.shape[0]), "pt_upload_scene")
         self._n_nodes = n.shape[0]
+        self._n_tris = t.shape[0]
 
     def update_geometry(self, verts):
         """New positions and shading normals for the uploaded triangles, in place (pt_update_geometry):
@@ -183,6 +184,47 @@ class Renderer:
         n, stride = int(verts.shape[0]), int(verts.shape[1])
         _, p, _ = self._query_args(what, n, [("verts", verts, "float32", stride, True)])
         self._ck(self._lib.pt_update_geometry_device(self._h, p[0], n, stride), "pt_update_geometry_device")
+
+    def update_materials(self, mats):
+        """New materials for the uploaded triangles, in place (pt_update_materials): mats is (n, 18) --
+        Triangle_encoded floats 18..35 per triangle -- or (n, 36), a whole Triangle_encoded array whose
+        floats 0..17 are ignored; n the uploaded count, the uploaded order. The material table is rebuilt
+        on the GPU and no tree is: the context is then what upload_scene of the records with the new
+        materials would have made it. A numpy array is copied from the host; a torch tensor -- float32,
+        contiguous, on the context's device, else ValueError -- is read in place in stream order on the
+        context's stream (pt_update_materials_device): hand the stream that produced it to set_stream,
+        or synchronise. Returns when the scene is ready; the guides are stale until the next
+        render_guides; restart the accumulation at frame_counter 0."""
+        what = "update_materials"
+        if isinstance(mats, np.ndarray) or not hasattr(mats, "data_ptr"):
+            m = np.ascontiguousarray(mats, np.float32)
+            if m.ndim != 2 or m.shape[1] not in (18, 36):
+                raise ValueError(f"{what}: mats must be (n, 18) or (n, 36), not {m.shape}")
+            p = m.ctypes.data + (72 if m.shape[1] == 36 else 0)  # floats 18..35 of a whole record
+            self._ck(self._lib.pt_update_materials(self._h, C.cast(p, _native.c_float_p), m.shape[0], m.shape[1]),
+                     "pt_update_materials")
+            return
+        if mats.dim() != 2 or mats.shape[1] not in (18, 36):
+            raise ValueError(f"{what}: mats must be (n, 18) or (n, 36), not {tuple(mats.shape)}")
+        n, stride = int(mats.shape[0]), int(mats.shape[1])
+        self._query_args(what, n, [("mats", mats, "float32", stride, True)])
+        p = C.c_void_p(mats.data_ptr() + (72 if stride == 36 else 0))
+        self._ck(self._lib.pt_update_materials_device(self._h, p, n, stride), "pt_update_materials_device")
+
+    def material_count(self) -> int:
+        """The number of distinct materials of the scene (pt_material_count)."""
+        n = C.c_int(0)
+        self._ck(self._lib.pt_material_count(self._h, C.byref(n)), "pt_material_count")
+        return n.value
+
+    def materials(self):
+        """Diagnostics (pt_download_materials) -> (table (material_count, 18) f32, ids (triangles,) i32):
+        the distinct materials in the order of their first appearance, and every triangle's id."""
+        table = np.empty((self.material_count(), 18), np.float32)
+        ids = np.empty(getattr(self, "_n_tris", 0), np.int32)
+        self._ck(self._lib.pt_download_materials(self._h, _fp(table), table.shape[0],
+                                                 ids.ctypes.data_as(_native.c_int_p)), "pt_download_materials")
+        return table, ids
 
     def node_boxes(self) -> np.ndarray:
         """Diagnostics (pt_download_node_boxes): the uploaded tree's current boxes, (nodes, 6) f32 -- lo,
