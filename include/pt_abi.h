@@ -58,7 +58,9 @@ extern "C" {
                                 the frames' camera rays as such rays (pt_camera_rays_device): new symbols only;
                              13, additive: materials updated in place (pt_update_materials,
                                 pt_update_materials_device, pt_material_count, pt_download_materials): new
-                                symbols only */
+                                symbols only;
+                             13, additive: the environment updated in place (pt_update_env, pt_update_env_device,
+                                pt_download_env, pt_env_size, PT_ENV_RGBE): new symbols only */
 
 /* error codes */
 #define PT_OK 0
@@ -289,6 +291,55 @@ int pt_download_materials(pt_ctx* ctx, float* table, int maxMats, int* ids);
  * f32, row 0 = first scanline; cache = calculateHdrCache output (nullable: the
  * library computes it). hdrResolution := w. hdr == NULL clears the env (black). */
 int pt_upload_env(pt_ctx* ctx, const float* hdr, int w, int h, const float* cache);
+
+/* A new environment in place: after the call the context is what pt_upload_env(ctx, hdr', w, h, cache)
+ * would have made it, where hdr' is hdr -- or, with PT_ENV_RGBE, hdr with every texel rounded to the RGBE
+ * texel a Radiance file would hold (include/pt_rgbe.h: negative values, -0 and NaN become 0, values above
+ * 255 * 2^119 that value, a texel whose largest channel would be stored below 1e-32f black), so that a map computed in
+ * floats is kept in the compact forms a decoded file's is. cache == NULL: the library's table, computed on
+ * the device from hdr'; a caller's table is used as given, also with PT_ENV_RGBE. Images of every
+ * integrator through every launch form, ray counts, PT_FLAG_COUNT_FETCHES counters, pt_radiance*,
+ * pt_frame_stats.env_compact and what pt_download_env returns are bit for bit a fresh upload's.
+ * hdr == NULL clears the environment, as pt_upload_env(NULL) does.
+ * The work runs on the GPU on the context's stream: the texels are packed, the library's table computed,
+ * the compact forms, Env::light and the table by rows built (pt_envupdate.hip), and three ints come back
+ * in the call's one host synchronisation -- texels and table compact, rows in row form, distinct rows --
+ * from which the forms that serve are chosen. It waits for the frames and queries in flight first and
+ * returns when the environment is ready.
+ * Invalidated, as pt_upload_env does: the temporal history, the moments and adaptive state: restart at
+ * frameCounter 0. Kept: the scene, both trees, the camera-ray bins and the guides (they hold no
+ * environment data), and the measured launch policies while w, h and the resulting env_compact are what
+ * they were before the call (otherwise they are measured again, as after pt_upload_env).
+ * Memory: the buffers belong to the map's size. The first update of a w x h map allocates them -- 24 bytes
+ * per texel for the float texels and table; with w, h <= 65535 another 12 for the compact forms, 2 for the
+ * rows' y's, about 8 for Env::light, and 4 (h + 65536) + 8 (w + h + 2) bytes of row and angle tables,
+ * whether or not that map is compact -- and every later update of the same size reuses them and allocates
+ * and frees nothing; Env::trig is computed once per size. A map that is not compact leaves the compact
+ * buffers allocated and unused. At its first use each kind of update adds what it needs: without a caller's
+ * table 24 bytes per texel for the library's table and its scratch (12 more with PT_ENV_RGBE); the host
+ * form 12 bytes per texel of staging, 24 with a table. Another size, pt_upload_env or pt_destroy frees
+ * them all; on another size the previous environment stays in place until the new one is complete.
+ * PT_E_INVALID for a NULL context, w <= 0 or h <= 0 with a map, a map whose 3 * w * h, (w + 1)(h + 1) or
+ * table scratch count does not fit an int, unknown flag bits and a PT_BASIC_CPU_COMPAT context; PT_E_NOMEM
+ * when the float texels, the library table's scratch or the staging cannot be allocated. Every other
+ * table (the compact forms, trig, light, rows) falls back to the form before it instead. A failed call
+ * leaves the previous environment in place and the context usable. PT_UPDATE_TIMES (environment
+ * variable): the device time of each step on stderr. */
+#define PT_ENV_RGBE 0x1u /* round every texel to the RGBE texel a Radiance file would hold, first */
+int pt_update_env(pt_ctx* ctx, const float* hdr, int w, int h, const float* cache, uint32_t flags);
+/* the same from device memory of the context's device (w*h*3 f32, row 0 = first scanline; d_cache
+ * w*h*3 f32 as pt_hdr_cache writes it, or NULL), read in stream order on the context's stream
+ * (pt_set_stream): a sky computed or edited on the GPU needs no trip through the host. PT_E_INVALID with
+ * n_devices > 1 (the host form updates every device). */
+int pt_update_env_device(pt_ctx* ctx, const void* d_hdr, int w, int h, const void* d_cache, uint32_t flags);
+/* diagnostic, synchronous: the environment as the kernels read it -- texels w*h*4 f32 (r, g, b, pdf) and
+ * the sample table w*h*2 f32 (x, y); either may be NULL, not both. form 0: the float texels and table.
+ * form 1: the same values decoded from the compact texels and the compact table by the frame kernels'
+ * decoders; PT_E_INVALID when env_compact < 1. form 2: the table read through the row form by the frame
+ * kernels' lookup; PT_E_INVALID when env_compact < 2 or texels != NULL (the rows hold no texels). Forms 1
+ * and 2 equal form 0 bit for bit. Also after pt_upload_env. PT_E_INVALID without an environment. */
+int pt_download_env(pt_ctx* ctx, int form, float* texels, float* table);
+int pt_env_size(pt_ctx* ctx, int* w, int* h); /* the environment's size; 0, 0 without one */
 
 /* PT_BASIC_CPU_COMPAT shape list (the vector<Shape*> of BasicRayTracingWithC++/main.cpp:306-353):
  * n x 24 f64 records (layout in pt_scene.h; the reference's Material rates and sphere radius

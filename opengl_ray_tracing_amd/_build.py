@@ -44,7 +44,8 @@ CXX_FLAGS = ["-O2", "-fPIC", "-pthread", "-std=c++17", "-ffp-contract=off", "-fn
 # what every device file sees: pt_device.h and pt_trace.h include pt_kernels.h and pt_fmath.h
 _DEV = [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]
 _FRAME = [*_DEV, CSRC / "pt_frame.h", CSRC / "pt_trace.h"]  # pt_frame.h's device half includes pt_trace.h
-_HOST = [CSRC / "pt_runtime.h", CSRC / "pt_frame.h", CSRC / "pt_kernels.h", INCLUDE / "pt_abi.h", CSRC / "pt_rccl.h"]
+_HOST = [CSRC / "pt_runtime.h", CSRC / "pt_frame.h", CSRC / "pt_kernels.h", INCLUDE / "pt_abi.h", CSRC / "pt_rccl.h",
+         CSRC / "pt_envupdate.h"]
 _PREP = [CSRC / "pt_scene_prep.h", CSRC / "pt_kernels.h"]  # the host-only scene preparation (no context, no HIP call)
 
 SOURCES = {
@@ -58,6 +59,7 @@ SOURCES = {
     "pt_basic.o": ("hip", CSRC / "pt_basic.hip", [*_DEV, INCLUDE / "pt_scene.h"]),
     "pt_diag.o": ("hip", CSRC / "pt_diag.hip", _DEV),
     "pt_envcache.o": ("hip", CSRC / "pt_envcache.hip", _DEV),
+    "pt_envupdate.o": ("hip", CSRC / "pt_envupdate.hip", [*_DEV, CSRC / "pt_envupdate.h", INCLUDE / "pt_rgbe.h"]),
     "pt_build.o": ("hip", CSRC / "pt_build.hip", [CSRC / "pt_kernels.h"]),
     "pt_refit.o": ("hip", CSRC / "pt_refit.hip", [CSRC / "pt_kernels.h"]),
     "pt_materials.o": ("hip", CSRC / "pt_materials.hip", [CSRC / "pt_kernels.h"]),
@@ -225,6 +227,22 @@ def build_material_table_check(force: bool = False, sanitize: bool = False) -> P
     return out
 
 
+ENV_QUANTISE_CHECK_SRC = ROOT / "tests" / "native" / "env_quantise_check.cpp"
+ENV_QUANTISE_CHECK = ROOT / "tests" / "native" / "env_quantise_check"
+
+
+def build_env_quantise_check(force: bool = False, sanitize: bool = False) -> Path:
+    """Test infrastructure: the RGBE quantiser of pt_update_env (include/pt_rgbe.h, the function the kernel
+    calls) on texels read from a file (tests/native/env_quantise_check.cpp), host-only, compiled with the
+    library's own CXX_FLAGS. sanitize: a second program built with -fsanitize=address,undefined."""
+    deps = [ENV_QUANTISE_CHECK_SRC, INCLUDE / "pt_rgbe.h"]
+    out = ENV_QUANTISE_CHECK.with_name("env_quantise_check_san") if sanitize else ENV_QUANTISE_CHECK
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g", "-O1"] if sanitize else []
+    if force or _stale(out, deps):
+        _run(["g++", *CXX_FLAGS, *san, f"-I{INCLUDE}", str(ENV_QUANTISE_CHECK_SRC), "-o", str(out)])
+    return out
+
+
 def build_oracle(force: bool = False) -> Path:
     """Test infrastructure only (see oracle/pt_oracle.h)."""
     src = [ORACLE_DIR / "pt_oracle.c", ORACLE_DIR / "pt_oracle.h", ORACLE_DIR / "Makefile", INCLUDE / "pt_fmath.h"]
@@ -241,5 +259,6 @@ if __name__ == "__main__":
     build_share_table(force="--force" in sys.argv)
     build_scene_prep_check(force="--force" in sys.argv)
     build_material_table_check(force="--force" in sys.argv)
+    build_env_quantise_check(force="--force" in sys.argv)
     print(LIB)
     print(ORACLE_LIB)

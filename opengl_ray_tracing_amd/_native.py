@@ -13,7 +13,7 @@ from . import _build
 
 _lib = None
 
-ABI_VERSION = 13  # include/pt_abi.h PT_ABI_VERSION (the ranged ray queries, the geometry and material updates and the radiance query are additive symbols: still 13)
+ABI_VERSION = 13  # include/pt_abi.h PT_ABI_VERSION (the ranged ray queries, the geometry, material and environment updates and the radiance query are additive symbols: still 13)
 # an older tuning build (tools/tune.py A/B against a previous round's library) loads when its structs
 # match: ABI 7 only added pt_unpack_ranks, ABI 8 the guide buffers and the denoiser, ABI 9 the
 # temporal resolve, ABI 10 the sample moments and the variance-guided filter, ABI 11 the
@@ -107,6 +107,10 @@ SIGNATURES = {
     "pt_material_count": (C.c_int, [C.c_void_p, c_int_p]),
     "pt_download_materials": (C.c_int, [C.c_void_p, c_float_p, C.c_int, c_int_p]),
     "pt_upload_env": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, c_float_p]),
+    "pt_update_env": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, c_float_p, C.c_uint32]),
+    "pt_update_env_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32]),
+    "pt_download_env": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p]),
+    "pt_env_size": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
     "pt_upload_shapes": (C.c_int, [C.c_void_p, c_double_p, C.c_int]),
     "pt_download_basic_image": (C.c_int, [C.c_void_p, c_double_p]),
     "pt_upload_basic_image": (C.c_int, [C.c_void_p, c_double_p]),

@@ -228,6 +228,7 @@ void pt_destroy(pt_ctx* ctx) {
   dfree(ctx->d_refParent); dfree(ctx->d_refBox); dfree(ctx->d_leafBox);
   freeRefit(ctx);
   freeMaterialTables(ctx);
+  releaseEnvStore(ctx);  // pt_update_env's buffers, which the env pointers are then views of
   dfree(ctx->d_hdr); dfree(ctx->d_cache); dfree(ctx->d_hdr8); dfree(ctx->d_cache4); dfree(ctx->d_shapes);
   dfree(ctx->d_cacheRow); dfree(ctx->d_cacheY); dfree(ctx->d_trig); dfree(ctx->d_light);
   dfree(ctx->d_basicImg); dfree(ctx->d_stream); dfree(ctx->d_offsets); dfree(ctx->d_overruns);

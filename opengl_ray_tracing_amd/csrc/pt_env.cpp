@@ -1,8 +1,9 @@
 // pt_env.cpp -- the environment map of the C-ABI in include/pt_abi.h (pt_upload_env and the forms it
-// keeps on the device, pt_hdr_cache_device), and the state of the BASIC integrator: its shapes, its
-// replayed random stream and its double image.
+// keeps on the device, pt_hdr_cache_device, pt_update_env and pt_download_env), and the state of the
+// BASIC integrator: its shapes, its replayed random stream and its double image.
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -38,6 +39,7 @@ static int envOne(pt_ctx* ctx, const float* hdr, int w, int h, const float* cach
   if (!ctx) return PT_E_INVALID;
   if (int rc = syncStreams(ctx)) return rc;
   CK(hipSetDevice(ctx->cfg.device_id));
+  releaseEnvStore(ctx);  // an env pt_update_env made: its buffers go, and the pointers below are null
   dfree(ctx->d_hdr);
   dfree(ctx->d_cache);
   dfree(ctx->d_hdr8);
@@ -210,6 +212,259 @@ int pt_upload_env(pt_ctx* ctx, const float* hdr, int w, int h, const float* cach
   }
   for (pt_ctx* m : members(ctx))
     if (int rc = envOne(m, hdr, w, h, cache)) return fromPeer(ctx, m, rc);
+  return PT_OK;
+}
+
+// ------------------------------------------------------------ environment update (pt_envupdate.hip)
+static void freeStore(EnvStore& s) {
+  dfree(s.hdr); dfree(s.cache); dfree(s.hdr8); dfree(s.cache4); dfree(s.cacheRow); dfree(s.cacheY); dfree(s.rowTmp);
+  dfree(s.trig); dfree(s.light); dfree(s.flags); dfree(s.full); dfree(s.scratch); dfree(s.quant); dfree(s.stageHdr);
+  dfree(s.stageCache);
+  s = EnvStore{};
+}
+
+void releaseEnvStore(pt_ctx* ctx) {
+  if (!ctx->envStore.w) return;
+  freeStore(ctx->envStore);
+  ctx->d_hdr = nullptr;
+  ctx->d_cache = nullptr;
+  ctx->d_hdr8 = nullptr;
+  ctx->d_cache4 = nullptr;
+  ctx->d_cacheRow = nullptr;
+  ctx->d_cacheY = nullptr;
+  ctx->d_trig = nullptr;
+  ctx->d_light = nullptr;
+}
+
+static int envCompactLevel(const pt_ctx* ctx) { return ctx->d_hdr8 ? (ctx->d_cacheRow ? 2 : 1) : 0; }  // pt_frame_stats.env_compact
+
+template <class T>
+static bool tryAlloc(T** p, size_t count) {  // an optional table: false, and no error left behind, when it does not fit
+  if (hipMalloc(p, count * sizeof(T)) == hipSuccess) return true;
+  *p = nullptr;
+  (void)hipGetLastError();
+  return false;
+}
+
+// The buffers of a w x h map, every form's: the compact forms are allocated whether or not the first map
+// is compact, so that a later one of the same size allocates nothing. The float texels, the float table
+// and the flag words are required; every other table falls back when it cannot be allocated (the compact
+// forms to the float ones, trig and light to the kernels' own arithmetic, the rows to the compact table).
+static int makeStore(pt_ctx* ctx, int w, int h, EnvStore& s) {
+  const size_t n = (size_t)w * h;
+  if (!tryAlloc(&s.hdr, n) || !tryAlloc(&s.cache, n) || !tryAlloc(&s.flags, (size_t)ENV_FLAGS)) {
+    freeStore(s);
+    return fail(ctx, PT_E_NOMEM, "pt_update_env: texels");
+  }
+  s.w = w;
+  s.h = h;
+  const char* c = std::getenv("PT_ENV_COMPACT");  // as pt_upload_env: 0 keeps the float texels
+  if ((c && std::atoi(c) == 0) || w > 65535 || h > 65535) return PT_OK;
+  if (!tryAlloc(&s.hdr8, n) || !tryAlloc(&s.cache4, n)) {
+    dfree(s.hdr8);
+    dfree(s.cache4);
+    return PT_OK;
+  }
+  if (!tryAlloc(&s.cacheRow, (size_t)h) || !tryAlloc(&s.cacheY, n) || !tryAlloc(&s.rowTmp, (size_t)ENV_X_SLOTS + h)) {
+    dfree(s.cacheRow);
+    dfree(s.cacheY);
+    dfree(s.rowTmp);
+  }
+  if (tryAlloc(&s.trig, (size_t)(w + h + 2))) tryAlloc(&s.light, (size_t)(w + 1) * (h + 1));
+  return PT_OK;
+}
+
+// One context's update. The map is w*h*3 floats in host memory (hdr, cache: staged here) or in the
+// context's device memory (d_hdr, d_cache), read in stream order on its stream; the caller has waited
+// for the frames and queries in flight. A map of the current store's size is written into the store's
+// buffers; any other size gets a new store, and the old environment -- the previous store, or
+// pt_upload_env's allocations -- is released only once the new one is complete.
+static int updateEnvOne(pt_ctx* ctx, const float* hdr, const float* cache, const float* d_hdr, const float* d_cache, int w,
+                        int h, uint32_t flags) {
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const size_t n = (size_t)w * h;
+  const bool rgbe = (flags & PT_ENV_RGBE) != 0, hasTable = hdr ? cache != nullptr : d_cache != nullptr;
+  const bool fresh = ctx->envStore.w != w || ctx->envStore.h != h;
+  EnvStore made;
+  if (fresh)
+    if (int rc = makeStore(ctx, w, h, made)) return rc;
+  EnvStore& st = fresh ? made : ctx->envStore;
+  // what this kind of update needs beside the forms, made at its first use
+  bool got = true;
+  if (!hasTable) got = (st.full || tryAlloc(&st.full, n)) && (st.scratch || tryAlloc(&st.scratch, 2 * n + 2 * (size_t)w + 1));
+  if (got && !hasTable && rgbe) got = st.quant || tryAlloc(&st.quant, 3 * n);
+  if (got && hdr) got = st.stageHdr || tryAlloc(&st.stageHdr, 3 * n);
+  if (got && hdr && cache) got = st.stageCache || tryAlloc(&st.stageCache, 3 * n);
+  if (!got) {
+    if (fresh) freeStore(made);
+    return fail(ctx, PT_E_NOMEM, "pt_update_env: table scratch or staging");
+  }
+  // PT_UPDATE_TIMES (environment; tools/env_time.py): the device time of each step, on stderr
+  const bool timed = std::getenv("PT_UPDATE_TIMES") != nullptr;
+  constexpr int NEV = 6;
+  struct StepEvents {  // destroyed on every way out
+    hipEvent_t ev[NEV] = {};
+    ~StepEvents() {
+      for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    }
+  } steps;
+  hipError_t e = hipSuccess;
+  if (timed)
+    for (int k = 0; k < NEV && e == hipSuccess; k++) e = hipEventCreate(&steps.ev[k]);
+  auto mark = [&](int k) {
+    if (timed && e == hipSuccess) e = hipEventRecord(steps.ev[k], ctx->stream);
+  };
+  hipStream_t s = ctx->stream;
+  if (e == hipSuccess && hdr) {
+    e = hipMemcpyAsync(st.stageHdr, hdr, 3 * n * sizeof(float), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && cache) e = hipMemcpyAsync(st.stageCache, cache, 3 * n * sizeof(float), hipMemcpyHostToDevice, s);
+    d_hdr = st.stageHdr;
+    d_cache = cache ? st.stageCache : nullptr;
+  }
+  if (e == hipSuccess) e = hipMemsetAsync(st.flags, 0, ENV_FLAGS * sizeof(int), s);
+  mark(0);
+  float* quant = rgbe && !hasTable ? st.quant : nullptr;
+  if (e == hipSuccess) e = launchEnvTexels(d_hdr, d_cache, rgbe ? 1 : 0, st.hdr, st.cache, quant, (int)n, s);
+  mark(1);
+  if (e == hipSuccess && !hasTable) {  // calculateHdrCache of the texels as stored, packed into the render layout
+    e = launchHdrCache(quant ? quant : d_hdr, w, h, st.full, st.scratch, s);
+    if (e == hipSuccess) e = launchEnvPack(st.hdr, st.full, st.cache, (int)n, s);
+  }
+  mark(2);
+  if (e == hipSuccess && st.hdr8) e = launchEnvCompact(st.hdr, st.cache, w, h, st.hdr8, st.cache4, st.flags + ENV_BAD, s);
+  mark(3);
+  // Env::trig once per (w, h); Env::light and the rows from whatever the compact forms hold -- whether they
+  // serve is known only after the one read-back below, and any contents keep both kernels in bounds
+  if (e == hipSuccess && st.hdr8 && st.trig && !st.trigReady) {
+    e = launchEnvTrig(st.trig, w, h, s);
+    st.trigReady = e == hipSuccess;
+  }
+  if (e == hipSuccess && st.hdr8 && st.trig && st.light) {
+    Env v;
+    std::memset(&v, 0, sizeof(v));
+    v.hdr = st.hdr;
+    v.hdr8 = st.hdr8;
+    v.trig = st.trig;
+    v.w = v.res = w;
+    v.h = h;
+    e = launchEnvLight(v, st.light, s);
+  }
+  mark(4);
+  if (e == hipSuccess && st.hdr8 && st.cacheRow) e = launchEnvRows(st, s);
+  mark(5);
+  int f[ENV_FLAGS] = {1, 1, 0, 0};
+  if (e == hipSuccess) e = hipMemcpyAsync(f, st.flags, sizeof(f), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);  // the one host synchronisation
+  if (e != hipSuccess) {
+    if (fresh) freeStore(made);
+    return fail(ctx, PT_E_HIP, std::string("pt_update_env: ") + hipGetErrorString(e));
+  }
+  // the hand-over: the Env the kernels get, chosen from the three ints
+  const int wasW = ctx->hdrW, wasH = ctx->hdrH, wasCompact = envCompactLevel(ctx);
+  if (fresh) {
+    releaseEnvStore(ctx);
+    dfree(ctx->d_hdr); dfree(ctx->d_cache); dfree(ctx->d_hdr8); dfree(ctx->d_cache4);
+    dfree(ctx->d_cacheRow); dfree(ctx->d_cacheY); dfree(ctx->d_trig); dfree(ctx->d_light);
+    ctx->envStore = made;
+  }
+  const EnvStore& k = ctx->envStore;
+  const bool compact = k.hdr8 && !f[ENV_BAD], rows = compact && k.cacheRow && !f[ENV_ROWS_BAD];
+  ctx->d_hdr = k.hdr;
+  ctx->d_cache = k.cache;
+  ctx->d_hdr8 = compact ? k.hdr8 : nullptr;
+  ctx->d_cache4 = compact ? k.cache4 : nullptr;
+  ctx->d_trig = compact ? k.trig : nullptr;
+  ctx->d_light = compact && k.trig ? k.light : nullptr;
+  ctx->d_cacheRow = rows ? k.cacheRow : nullptr;
+  ctx->d_cacheY = rows ? k.cacheY : nullptr;
+  ctx->hdrW = w;
+  ctx->hdrH = h;
+  // the measured launch policies were measured for a map of this size in this form: they stay while both do
+  if (wasW != w || wasH != h || wasCompact != envCompactLevel(ctx)) ctx->policyKey++;
+  if (timed) {
+    float ms[NEV - 1] = {};
+    for (int j = 0; j + 1 < NEV; j++) CK(hipEventElapsedTime(&ms[j], steps.ev[j], steps.ev[j + 1]));
+    std::fprintf(stderr, "pt_update_env: texels %.4f table %.4f compact %.4f light %.4f rows %.4f ms, env_compact %d, %d rows\n",
+                 ms[0], ms[1], ms[2], ms[3], ms[4], envCompactLevel(ctx), rows ? f[ENV_ROW_IDS] : 0);
+  }
+  return PT_OK;
+}
+
+static int envUpdateArgs(pt_ctx* ctx, const void* hdr, int w, int h, uint32_t flags) {
+  if (!ctx) return PT_E_INVALID;
+  if (flags & ~(uint32_t)PT_ENV_RGBE) return fail(ctx, PT_E_INVALID, "pt_update_env: unknown flag bits");
+  if (ctx->cfg.integrator == PT_BASIC_CPU_COMPAT) return fail(ctx, PT_E_INVALID, "pt_update_env: not on a BASIC context");
+  if (!hdr) return PT_OK;
+  if (w <= 0 || h <= 0) return fail(ctx, PT_E_INVALID, "pt_update_env: w and h must be positive");
+  // every element count of the pipeline as an int: 3 floats per texel, Env::light's (w + 1)(h + 1), the table scratch
+  const long long n = (long long)w * h, most = 2147483647LL;
+  if (3 * n > most || (long long)(w + 1LL) * (h + 1LL) > most || 2 * n + 2LL * w + 1 > most)
+    return fail(ctx, PT_E_INVALID, "pt_update_env: map too large");
+  return PT_OK;
+}
+
+static int envWait(pt_ctx* ctx) {
+  if (int rc = syncStreams(ctx)) return rc;  // no frame in flight reads the buffers rewritten here
+  if (ctx->queryIssued) CK(hipEventSynchronize(ctx->queryDone));  // nor a ray query, whichever stream it is on
+  return PT_OK;
+}
+
+int pt_update_env(pt_ctx* ctx, const float* hdr, int w, int h, const float* cache, uint32_t flags) {
+  if (int rc = envUpdateArgs(ctx, hdr, w, h, flags)) return rc;
+  if (!hdr) return pt_upload_env(ctx, nullptr, 0, 0, nullptr);
+  for (pt_ctx* m : members(ctx)) {
+    if (int rc = envWait(m)) return fromPeer(ctx, m, rc);
+    dropHistory(m);
+    if (int rc = dropMoments(m)) return fromPeer(ctx, m, rc);
+    if (int rc = updateEnvOne(m, hdr, cache, nullptr, nullptr, w, h, flags)) return fromPeer(ctx, m, rc);
+  }
+  return PT_OK;
+}
+
+int pt_update_env_device(pt_ctx* ctx, const void* d_hdr, int w, int h, const void* d_cache, uint32_t flags) {
+  if (int rc = envUpdateArgs(ctx, d_hdr, w, h, flags)) return rc;
+  if (!ctx->peers.empty()) return fail(ctx, PT_E_INVALID, "pt_update_env_device: not on an n_devices > 1 context");
+  if (!d_hdr) return pt_upload_env(ctx, nullptr, 0, 0, nullptr);
+  if (int rc = envWait(ctx)) return rc;
+  dropHistory(ctx);
+  if (int rc = dropMoments(ctx)) return rc;
+  return updateEnvOne(ctx, nullptr, nullptr, static_cast<const float*>(d_hdr), static_cast<const float*>(d_cache), w, h, flags);
+}
+
+int pt_env_size(pt_ctx* ctx, int* w, int* h) {
+  if (!ctx || !w || !h) return PT_E_INVALID;
+  *w = ctx->d_hdr ? ctx->hdrW : 0;
+  *h = ctx->d_hdr ? ctx->hdrH : 0;
+  return PT_OK;
+}
+
+int pt_download_env(pt_ctx* ctx, int form, float* texels, float* table) {
+  if (!ctx || (!texels && !table)) return PT_E_INVALID;
+  if (form < 0 || form > 2) return fail(ctx, PT_E_INVALID, "pt_download_env: form must be 0, 1 or 2");
+  if (!ctx->d_hdr) return fail(ctx, PT_E_INVALID, "pt_download_env: no environment");
+  if (form > envCompactLevel(ctx)) return fail(ctx, PT_E_INVALID, "pt_download_env: the environment is not kept in that form");
+  if (form == 2 && texels) return fail(ctx, PT_E_INVALID, "pt_download_env: the row form holds no texels");
+  if (int rc = syncStreams(ctx)) return rc;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const size_t n = (size_t)ctx->hdrW * ctx->hdrH;
+  if (form == 0) {
+    if (texels) CK(hipMemcpy(texels, ctx->d_hdr, n * sizeof(float4), hipMemcpyDeviceToHost));
+    if (table) CK(hipMemcpy(table, ctx->d_cache, n * sizeof(float2), hipMemcpyDeviceToHost));
+    return PT_OK;
+  }
+  float4* t4 = nullptr;
+  float2* t2 = nullptr;
+  hipError_t e = hipSuccess;
+  if (texels) e = hipMalloc(&t4, n * sizeof(float4));
+  if (e == hipSuccess && table) e = hipMalloc(&t2, n * sizeof(float2));
+  if (e == hipSuccess) e = launchEnvDecode(envView(ctx, form == 2, 0), form, t4, t2, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && texels) e = hipMemcpy(texels, t4, n * sizeof(float4), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && table) e = hipMemcpy(table, t2, n * sizeof(float2), hipMemcpyDeviceToHost);
+  dfree(t4);
+  dfree(t2);
+  if (e != hipSuccess) return fail(ctx, PT_E_HIP, std::string("pt_download_env: ") + hipGetErrorString(e));
   return PT_OK;
 }
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "pt_abi.h"
+#include "pt_envupdate.h"
 #include "pt_frame.h"
 #include "pt_kernels.h"
 #include "pt_rccl.h"
@@ -126,6 +127,10 @@ struct pt_ctx {
   float2* d_trig = nullptr;                  // SampleHdr's sines and cosines (Env::trig)
   uint2* d_light = nullptr;                  // each sample-table entry's light-sample color and pdf (Env::light)
   int hdrW = 0, hdrH = 0;
+  // pt_update_env: the buffers it keeps for maps of the current size (pt_envupdate.h). While envStore.w != 0
+  // it owns every env buffer and the pointers above are views of it (null where a form does not serve the
+  // current map); otherwise they are pt_upload_env's own allocations. releaseEnvStore ends the first state.
+  EnvStore envStore;
   // BASIC shapes, the double image, the replayed random stream
   double* d_shapes = nullptr;
   int nShapes = 0;
@@ -347,6 +352,7 @@ void dropHistory(pt_ctx* ctx);  // the temporal history shows another scene or a
 void freeRefit(pt_ctx* ctx);    // pt_update_geometry's device tables and staging belong to one upload
 void freeMaterialTables(pt_ctx* ctx);  // ... and so do pt_update_materials'
 // pt_env.cpp
+void releaseEnvStore(pt_ctx* ctx);  // pt_update_env's buffers freed and the env pointers nulled (no-op without a store)
 int ensureBasicImage(pt_ctx* ctx);  // the BASIC double image, allocated and zeroed on first use
 // pt_group.cpp
 int createGroup(pt_ctx* ctx);    // the gather's streams, events, buffers and communicators of a device group

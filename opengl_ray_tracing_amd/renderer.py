@@ -40,7 +40,8 @@ FLAG_PRIMARY_PASS = 0x800
 FLAG_MOMENTS = 0x1000
 FLAG_ADAPTIVE = 0x2000
 FLAG_SHARE_MOMENTS = 0x4000
-PACK_STATS_F = 5  # f32 per packed slot of pack_owned_stats: r, g, b, m1, m2
+ENV_RGBE = 0x1  # pt_update_env's PT_ENV_RGBE (update_env(rgbe=True))
+PACK_STATS_F = 5 # f32 per packed slot of pack_owned_stats: r, g, b, m1, m2
 GATHER = {"auto": 0, "copy": 1, "rccl": 2}
 
 
@@ -249,6 +250,58 @@ class Renderer:
         hh, ww = h.shape[:2]
         c = None if cache is None else np.ascontiguousarray(cache, np.float32)
         self._ck(self._lib.pt_upload_env(self._h, _fp(h), ww, hh, None if c is None else _fp(c)), "pt_upload_env")
+
+    def update_env(self, hdr, cache=None, rgbe: bool = False):
+        """A new environment in place (pt_update_env): hdr is (h, w, 3) float32, cache the (h, w, 3) table of
+        calculate_hdr_cache or None for the library's own, computed on the GPU; rgbe rounds every texel to
+        the RGBE texel a Radiance file would hold first (PT_ENV_RGBE), so that a map computed in floats is
+        kept in the compact forms. The context is then what upload_env of the same map would have made
+        it, and an update of the same size as the last allocates nothing. A numpy array is copied from the
+        host; a torch tensor -- float32, contiguous, on the context's device, shape (h, w, 3), else
+        ValueError -- is read in place in stream order on the context's stream (pt_update_env_device):
+        hand the stream that produced it to set_stream, or synchronise. None clears the environment.
+        Returns when the environment is ready; restart the accumulation at frame_counter 0."""
+        what = "update_env"
+        flags = ENV_RGBE if rgbe else 0
+        if hdr is None:
+            self._ck(self._lib.pt_update_env(self._h, None, 0, 0, None, flags), "pt_update_env")
+            return
+        if isinstance(hdr, np.ndarray) or not hasattr(hdr, "data_ptr"):
+            if cache is not None and hasattr(cache, "data_ptr"):
+                raise ValueError(f"{what}: hdr is a host array, cache a tensor: pass both as one kind")
+            h = np.ascontiguousarray(hdr, np.float32)
+            if h.ndim != 3 or h.shape[2] != 3:
+                raise ValueError(f"{what}: hdr must be (h, w, 3), not {h.shape}")
+            c = None if cache is None else np.ascontiguousarray(cache, np.float32)
+            if c is not None and c.shape != h.shape:
+                raise ValueError(f"{what}: cache must be {h.shape} like hdr, not {c.shape}")
+            self._ck(self._lib.pt_update_env(self._h, _fp(h), h.shape[1], h.shape[0], None if c is None else _fp(c), flags),
+                     "pt_update_env")
+            return
+        if hdr.dim() != 3 or hdr.shape[2] != 3:
+            raise ValueError(f"{what}: hdr must be (h, w, 3), not {tuple(hdr.shape)}")
+        hh, ww = int(hdr.shape[0]), int(hdr.shape[1])
+        if cache is not None and (not hasattr(cache, "data_ptr") or tuple(cache.shape) != tuple(hdr.shape)):
+            raise ValueError(f"{what}: cache must be a tensor of shape {tuple(hdr.shape)} like hdr")
+        _, p, _ = self._query_args(what, hh * ww, [("hdr", hdr, "float32", 3, True), ("cache", cache, "float32", 3, False)])
+        self._ck(self._lib.pt_update_env_device(self._h, p[0], ww, hh, p[1], flags), "pt_update_env_device")
+
+    def env_size(self):
+        """(w, h) of the environment, (0, 0) without one (pt_env_size)."""
+        w, h = C.c_int(0), C.c_int(0)
+        self._ck(self._lib.pt_env_size(self._h, C.byref(w), C.byref(h)), "pt_env_size")
+        return w.value, h.value
+
+    def download_env(self, form: int = 0):
+        """Diagnostics (pt_download_env) -> (texels (h, w, 4) f32: r g b pdf, table (h, w, 2) f32: x y) as the
+        kernels read them: form 0 the float texels and table, form 1 the same decoded from the compact forms
+        (env_compact >= 1), form 2 the table read through the row form (env_compact == 2; texels is None)."""
+        w, h = self.env_size()
+        texels = None if form == 2 else np.empty((h, w, 4), np.float32)
+        table = np.empty((h, w, 2), np.float32)
+        self._ck(self._lib.pt_download_env(self._h, int(form), None if texels is None else _fp(texels), _fp(table)),
+                 "pt_download_env")
+        return texels, table
 
     def upload_shapes(self, shapes: np.ndarray):
         """BASIC: n x 24 f64 shape records (scenes.cornell_shapes, include/pt_scene.h)."""

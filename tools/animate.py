@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A deforming scene rendered pose by pose without a trip through the host.
 
-    python tools/animate.py --config c2 --poses 8 --frames 16 --out DIR [--size WxH] [--amplitude A] [--materials]
+    python tools/animate.py --config c2 --poses 8 --frames 16 --out DIR [--size WxH] [--amplitude A] [--materials] [--sky]
 
 The scene is uploaded once. For every pose torch displaces the vertices on the stream the renderer was
 handed (pt_set_stream) -- a travelling wave, a function of each vertex's position, so shared vertices stay
@@ -9,7 +9,10 @@ shared -- and pt_update_geometry_device reads them there in stream order; then `
 the running mean and one PNG per pose (pose_000.png ..., row 0 = the top row) is written. With
 --materials torch also changes the materials per pose on that stream -- the emitters pulse, the
 roughness of everything else sweeps between 0.05 and 0.95 -- and pt_update_materials_device rebuilds the
-material table from them in place: no pose needs a new upload. One JSON line with the wall times.
+material table from them in place. With --sky torch also turns and dims the environment per pose on that
+stream -- the map rolled along its width and scaled by a power of two, both of which keep RGBE texels
+exact, so the compact forms keep serving -- and pt_update_env_device rebuilds every form of it in place:
+no pose needs a new upload. One JSON line with the wall times.
 """
 from __future__ import annotations
 
@@ -32,6 +35,7 @@ def main():
     ap.add_argument("--size", default=None, help="WxH (default: the config's)")
     ap.add_argument("--amplitude", type=float, default=0.04, help="of the scene's extent")
     ap.add_argument("--materials", action="store_true", help="also animate emission and roughness (update_materials)")
+    ap.add_argument("--sky", action="store_true", help="also turn and dim the environment (update_env)")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -46,13 +50,14 @@ def main():
     out = Path(a.out)
     out.mkdir(parents=True, exist_ok=True)
     stream = torch.cuda.Stream()
-    update_ms, material_ms, pose_ms = [], [], []
+    update_ms, material_ms, sky_ms, sky_compact, pose_ms = [], [], [], [], []
     with Renderer(w, h, cfg.integrator, max_bounce=cfg.max_bounce) as r:
         r.upload_scene(tris, nodes)
         r.upload_env(hdr)
         rest = torch.from_numpy(np.ascontiguousarray(np.asarray(tris, np.float32).reshape(-1, 36)[:, :18])).to("cuda:0")
         # Triangle_encoded floats 18..35: emissive 0..2, roughness 10 (include/pt_scene.h pt_material)
         look = torch.from_numpy(np.ascontiguousarray(np.asarray(tris, np.float32).reshape(-1, 36)[:, 18:])).to("cuda:0")
+        sky = torch.from_numpy(np.ascontiguousarray(hdr, np.float32)).to("cuda:0")
         p = rest[:, :9].reshape(-1, 3)
         ext = float((p.max(0).values - p.min(0).values).max())
         n = rest.shape[0]
@@ -76,6 +81,12 @@ def main():
                     t2 = time.perf_counter()
                     r.update_materials(m)  # in stream order too
                     material_ms.append((time.perf_counter() - t2) * 1e3)
+                if a.sky:
+                    turned = (torch.roll(sky, (k * sky.shape[1]) // max(a.poses, 1), 1) * 2.0 ** -(k % 3)).contiguous()
+                    t3 = time.perf_counter()
+                    r.update_env(turned)  # in stream order too; the same size every pose: nothing is allocated after the first
+                    sky_ms.append((time.perf_counter() - t3) * 1e3)
+                    sky_compact.append(r.stats().env_compact)
             r.render_frames(eye, rot, 0, a.frames)
             img = r.tonemap(1.5)
             pose_ms.append((time.perf_counter() - t0) * 1e3)
@@ -83,7 +94,8 @@ def main():
         r.set_stream(None)
     print(json.dumps({"config": a.config, "size": [w, h], "poses": a.poses, "frames_per_pose": a.frames,
                       "update_ms": [round(x, 3) for x in update_ms],
-                      "material_update_ms": [round(x, 3) for x in material_ms], "pose_ms": [round(x, 3) for x in pose_ms],
+                      "material_update_ms": [round(x, 3) for x in material_ms],
+                      "env_update_ms": [round(x, 3) for x in sky_ms], "env_compact": sky_compact, "pose_ms": [round(x, 3) for x in pose_ms],
                       "out": str(out)}))
 
 
