@@ -302,10 +302,42 @@ __device__ __forceinline__ int sphTexel(int W, int H, V3 v) {
   return sphTexelExact(W, H, v);
 }
 // sampleHdr IS:184-189 (clamped at 10)
+// in two parts, so a caller with several directions can have their texel loads in flight together
+// (mixFrames): the texel's index (e.hdr non-null), and the sample of the texel there
+__device__ __forceinline__ int sampleHdrTexel(const Env& e, V3 v) { return sphTexel(e.w, e.h, normalize(v)); }
+__device__ __forceinline__ V3 skyOfTexel(float4 c) { return v3(fminf(c.x, 10.0f), fminf(c.y, 10.0f), fminf(c.z, 10.0f)); }
 __device__ __forceinline__ V3 sampleHdr(const Env& e, V3 v) {
   if (!e.hdr) return v3(0, 0, 0);
-  float4 c = envTexelK(e, sphTexel(e.w, e.h, normalize(v)));
-  return v3(fminf(c.x, 10.0f), fminf(c.y, 10.0f), fminf(c.z, 10.0f));
+  return skyOfTexel(envTexelK(e, sampleHdrTexel(e, v)));
+}
+// sampleHdr of N texel indices (e.hdr non-null): envTexelK's four forms with the form chosen once, so
+// the N loads are issued before the first is decoded
+template <int N>
+__device__ __forceinline__ void sampleHdrAt(const Env& e, const int (&k)[N], V3 (&out)[N]) {
+  const int mask = (PT_DIAG_ENV_SMALL & 1) ? 1023 : -1;
+  if (e.hdr8) {
+    uint2 t[N];
+    if (e.nt) {
+#pragma unroll
+      for (int j = 0; j < N; j++) t[j] = ldStream(e.hdr8 + (k[j] & mask));
+    } else {
+#pragma unroll
+      for (int j = 0; j < N; j++) t[j] = e.hdr8[k[j] & mask];
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) out[j] = skyOfTexel(decodeHdr8(t[j]));
+  } else {
+    float4 t[N];
+    if (e.nt) {
+#pragma unroll
+      for (int j = 0; j < N; j++) t[j] = ldStream(e.hdr + (k[j] & mask));
+    } else {
+#pragma unroll
+      for (int j = 0; j < N; j++) t[j] = e.hdr[k[j] & mask];
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) out[j] = skyOfTexel(t[j]);
+  }
 }
 // hdrColor IS:647-651 (unclamped)
 __device__ __forceinline__ V3 hdrColor(const Env& e, V3 L) {

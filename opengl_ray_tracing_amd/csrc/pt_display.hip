@@ -223,63 +223,116 @@ hipError_t launchUnpackRanksStats(const RanksUnpack& d, int world, float4* accum
 // ADAPTIVE (a PT_FLAG_ADAPTIVE context, pt_adaptive.hip): a pixel whose 8x8 tile has retired
 // (retiredAt[ty * tilesX + tx] != 0) keeps its accumulation and moments -- the camera-ray pass stored it
 // no sample -- and returns before its loads; every other pixel is a MOMENTS pixel.
-template <bool MOMENTS, bool ADAPTIVE = false>
+// SKY (pt_kernels.h SkyTiles; the launch's camera-ray pass ran over its pass list): a pixel whose image
+// tile has an empty camera-ray bin was not given to the pass. Its sample of frame f is the sky's along its
+// camera ray, sampleHdr(env, cameraRay(cam, W, H, sampleIndex + f * sampleStride, px, py)) -- the functions
+// and the floats of the pass (pt_frame.h, pt_device.h), so the means are bit for bit what they were -- and
+// the update counts those rays, one atomic per wave. A retired tile (ADAPTIVE) takes no sample and counts
+// none, as in the pass. The frames' texel lookups are independent: they are taken SKY_CHUNK at a time, the
+// indices first and then the loads, so a chunk's loads are in flight together.
+// SKY is a template parameter: without it the kernels are the 16-20 VGPR streaming updates they were (the
+// lookups take 58-64), which find room beside a machine full of regen blocks sooner -- what the launches
+// without such tiles (no pass, no bins, the large scenes) keep.
+constexpr int SKY_CHUNK = 4;
+template <bool MOMENTS, bool ADAPTIVE, bool SKY>
 __device__ __forceinline__ void mixFrames(const PackParams& p, float4* accum, float2* moments, const float* col,
-                                          size_t colStride, int nFrames, uint32_t frameCounter,
-                                          const uint32_t* retiredAt = nullptr) {
+                                          size_t colStride, int nFrames, uint32_t frameCounter, const SkyTiles& sky,
+                                          const uint32_t* retiredAt) {
   long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= p.count) return;
-  int px, py;
-  if (!pixelOfSlot(p.share, k, px, py)) return;
-  if (ADAPTIVE && retiredAt[(size_t)(py >> 3) * ((p.share.width + 7) >> 3) + (px >> 3)] != 0u) return;
+  int px = 0, py = 0;
+  bool on = k < p.count && pixelOfSlot(p.share, k, px, py);
+  if (ADAPTIVE && on && retiredAt[(size_t)(py >> 3) * ((p.share.width + 7) >> 3) + (px >> 3)] != 0u) on = false;
+  bool own = false;  // the update takes this pixel's samples itself
+  if (SKY) {
+    if (on) {
+      const int t = (py >> 3) * sky.binTilesX + (px >> 3);
+      own = sky.binStart[t + 1] == sky.binStart[t];
+    }
+    // the rays the pass counted for these pixels: one per valid pixel and frame
+    const unsigned long long b = __ballot(own);
+    if ((threadIdx.x & 63) == 0 && b)
+      atomicAdd(sky.rayShards + (blockIdx.x & (RAY_SHARDS - 1)) * RAY_SHARD_STRIDE,
+                (unsigned long long)__popcll(b) * (unsigned long long)nFrames);
+  }
+  if (!on) return;
   const size_t i = (size_t)py * p.share.width + px;
   float4 a = ldStream(accum + i);
   float2 m = make_float2(0.0f, 0.0f);
   if (MOMENTS) m = ldStream(moments + i);
-  for (int f = 0; f < nFrames; f++) {
-    const float3 c = ldCol(col + ((size_t)f * colStride + k) * COL_F);
+  auto mix = [&](int f, float cx, float cy, float cz) {
     const float w = 1.0f / (float)(frameCounter + (uint32_t)f + 1u);
-    a = make_float4(mixf(a.x, c.x, w), mixf(a.y, c.y, w), mixf(a.z, c.z, w), 1.0f);
+    a = make_float4(mixf(a.x, cx, w), mixf(a.y, cy, w), mixf(a.z, cz, w), 1.0f);
     if (MOMENTS) {
-      const float l = (0.3f * c.x + 0.6f * c.y) + 0.1f * c.z;
+      const float l = (0.3f * cx + 0.6f * cy) + 0.1f * cz;
       m = make_float2(mixf(m.x, l, w), mixf(m.y, l * l, w));
+    }
+  };
+  if (!SKY || !own) {
+    for (int f = 0; f < nFrames; f++) {
+      const float3 c = ldCol(col + ((size_t)f * colStride + k) * COL_F);
+      mix(f, c.x, c.y, c.z);
+    }
+  } else if (!sky.env.hdr) {  // no environment: sampleHdr's black
+    for (int f = 0; f < nFrames; f++) mix(f, 0.0f, 0.0f, 0.0f);
+  } else {
+    for (int f0 = 0; f0 < nFrames; f0 += SKY_CHUNK) {
+      int tex[SKY_CHUNK];
+#pragma unroll
+      for (int j = 0; j < SKY_CHUNK; j++) {  // (past the batch's end: its last frame's again, not mixed)
+        const int f = min(f0 + j, nFrames - 1);
+        uint32_t seed;
+        const V3 dir = cameraRay(sky.cam, p.share.width, p.share.height, sky.sampleIndex + (uint32_t)f * sky.sampleStride,
+                                 px, py, seed);
+        tex[j] = sampleHdrTexel(sky.env, dir);
+      }
+      V3 c[SKY_CHUNK];
+      sampleHdrAt(sky.env, tex, c);
+#pragma unroll
+      for (int j = 0; j < SKY_CHUNK; j++)
+        if (f0 + j < nFrames) mix(f0 + j, c[j].x, c[j].y, c[j].z);
     }
   }
   stStream(accum + i, a);
   if (MOMENTS) stStream(moments + i, m);
 }
+template <bool SKY>
 __global__ void mixKernel(PackParams p, float4* accum, const float* col, size_t colStride, int nFrames,
-                          uint32_t frameCounter) {
-  mixFrames<false>(p, accum, nullptr, col, colStride, nFrames, frameCounter);
+                          uint32_t frameCounter, SkyTiles sky) {
+  mixFrames<false, false, SKY>(p, accum, nullptr, col, colStride, nFrames, frameCounter, sky, nullptr);
 }
+template <bool SKY>
 __global__ void mixMomentsKernel(PackParams p, float4* accum, float2* moments, const float* col, size_t colStride,
-                                 int nFrames, uint32_t frameCounter) {
-  mixFrames<true>(p, accum, moments, col, colStride, nFrames, frameCounter);
+                                 int nFrames, uint32_t frameCounter, SkyTiles sky) {
+  mixFrames<true, false, SKY>(p, accum, moments, col, colStride, nFrames, frameCounter, sky, nullptr);
 }
+template <bool SKY>
 __global__ void mixAdaptiveKernel(PackParams p, float4* accum, float2* moments, const float* col, size_t colStride,
-                                  int nFrames, uint32_t frameCounter, const uint32_t* retiredAt) {
-  mixFrames<true, true>(p, accum, moments, col, colStride, nFrames, frameCounter, retiredAt);
+                                  int nFrames, uint32_t frameCounter, const uint32_t* retiredAt, SkyTiles sky) {
+  mixFrames<true, true, SKY>(p, accum, moments, col, colStride, nFrames, frameCounter, sky, retiredAt);
 }
 hipError_t launchMix(const PackParams& p, float4* accum, const float* col, size_t colStride, int nFrames,
-                     uint32_t frameCounter, hipStream_t s) {
+                     uint32_t frameCounter, const SkyTiles& sky, hipStream_t s) {
+  if (sky.binStart && !sky.rayShards) return hipErrorInvalidValue;
   if (p.count <= 0 || nFrames <= 0) return hipSuccess;
-  hipLaunchKernelGGL(mixKernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, col, colStride,
-                     nFrames, frameCounter);
+  hipLaunchKernelGGL(sky.binStart ? mixKernel<true> : mixKernel<false>, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, col, colStride,
+                     nFrames, frameCounter, sky);
   return hipGetLastError();
 }
 hipError_t launchMixMoments(const PackParams& p, float4* accum, float2* moments, const float* col, size_t colStride,
-                            int nFrames, uint32_t frameCounter, hipStream_t s) {
+                            int nFrames, uint32_t frameCounter, const SkyTiles& sky, hipStream_t s) {
+  if (sky.binStart && !sky.rayShards) return hipErrorInvalidValue;
   if (p.count <= 0 || nFrames <= 0) return hipSuccess;
-  hipLaunchKernelGGL(mixMomentsKernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, moments, col,
-                     colStride, nFrames, frameCounter);
+  hipLaunchKernelGGL(sky.binStart ? mixMomentsKernel<true> : mixMomentsKernel<false>, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, moments, col,
+                     colStride, nFrames, frameCounter, sky);
   return hipGetLastError();
 }
 hipError_t launchMixAdaptive(const PackParams& p, float4* accum, float2* moments, const float* col, size_t colStride,
-                             int nFrames, uint32_t frameCounter, const uint32_t* retiredAt, hipStream_t s) {
-  if (!retiredAt) return hipErrorInvalidValue;
+                             int nFrames, uint32_t frameCounter, const uint32_t* retiredAt, const SkyTiles& sky,
+                             hipStream_t s) {
+  if (!retiredAt || (sky.binStart && !sky.rayShards)) return hipErrorInvalidValue;
   if (p.count <= 0 || nFrames <= 0) return hipSuccess;
-  hipLaunchKernelGGL(mixAdaptiveKernel, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, moments,
-                     col, colStride, nFrames, frameCounter, retiredAt);
+  hipLaunchKernelGGL(sky.binStart ? mixAdaptiveKernel<true> : mixAdaptiveKernel<false>, dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p, accum, moments,
+                     col, colStride, nFrames, frameCounter, retiredAt, sky);
   return hipGetLastError();
 }
 

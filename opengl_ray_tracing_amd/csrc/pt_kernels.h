@@ -397,12 +397,18 @@ struct PrimaryBins {
   float4* binGeo = nullptr;  // per entry: geo[4 tri .. 4 tri + 3] (RenderParams::binGeo)
   float4* binBox = nullptr;  // per entry: leafBox[2 tri], [2 tri + 1]
   void* tmp = nullptr;       // hipcub scan scratch
+  // the pass tiles of the context's share (buildPassList): the share's wave tiles whose image tile has a
+  // non-empty bin, ascending, then their number at passList[waveTiles(share)]
+  int* passList = nullptr;
   size_t rectCap = 0, triCountCap = 0, triOffsetCap = 0, tileCountCap = 0, binStartCap = 0, binTrisCap = 0,
-         binGeoCap = 0, binBoxCap = 0, tmpBytes = 0;
+         binGeoCap = 0, binBoxCap = 0, tmpBytes = 0, passListCap = 0;
   int tilesX = 0, tilesY = 0, entries = 0;
+  int passCount = 0;         // the list's length, read back at its build
 };
 hipError_t buildPrimaryBins(const float eye[3], const float cam[16], int width, int height, const float4* geo,
                             const float4* leafBox, int nTri, PrimaryBins& b, hipStream_t s);
+// b's pass tiles of `share` (after buildPrimaryBins, on its stream; one more host sync for the count)
+hipError_t buildPassList(const Share& share, PrimaryBins& b, hipStream_t s);
 void freePrimaryBins(PrimaryBins& b);
 
 // The runtime's own tree built on the device (pt_build.hip): a binned-SAH tree
@@ -512,7 +518,9 @@ hipError_t launchReorder(int* cost, int* costMax, int* splitLg, int* ema, int* o
 hipError_t renderBlocksPerCU(int integrator, bool cull, bool count, bool wide, int* nb);
 // the camera-ray pass: one wave per 8x8 tile of the rank's tiles, results in p.primHit
 constexpr int PRIM_MISS = -1, PRIM_RETRACE = -2, PRIM_TILE = -3;
-hipError_t launchPrimary(const RenderParams& p, hipStream_t s);
+// passList (PrimaryBins::passList, passCount > 0 entries): the pass over those tiles only -- a pipelined
+// launch, whose running-mean update takes the other tiles' samples (SkyTiles); null: every tile of the share
+hipError_t launchPrimary(const RenderParams& p, const int* passList, int passCount, hipStream_t s);
 // the live items of every work queue from the pass's tile masks (p.liveItems), for the regen kernels
 hipError_t launchLiveList(const RenderParams& p, hipStream_t s);
 // the path-regeneration kernel (pt_regen.hip): the variant and launch shape of a frame
@@ -648,19 +656,35 @@ hipError_t launchUnpack(const PackParams& p, float4* accum, const float* packed,
 constexpr int PACK_STATS_F = 5;
 hipError_t launchPackStats(const PackParams& p, const float4* accum, const float2* moments, float* packed, hipStream_t s);
 hipError_t launchUnpackRanksStats(const RanksUnpack& d, int world, float4* accum, float2* moments, hipStream_t s);
+// The samples the running-mean update takes itself: in a pipelined launch a tile whose camera-ray bin is
+// empty -- no camera ray of it, whatever its jitter, hits anything -- is not given to the camera-ray pass;
+// the update computes sampleHdr(env, cameraRay(...)) of each of its pixels and frames where it would load
+// the colour buffer (pt_display.hip mixFrames), and counts those rays. By value: the update runs on the
+// caller's stream after the slot's parameter block may have been reused. binStart null: no such tiles
+// (a launch without bins or without a pass; every sample comes from the colour buffer).
+struct SkyTiles {
+  const int* binStart;   // RenderParams::binStart of the launch
+  int binTilesX;
+  uint32_t sampleIndex;  // of the launch's first frame, and the step to the next (RenderParams)
+  uint32_t sampleStride;
+  float cam[16];
+  Env env;               // the launch's view of the environment (its nt / row-table setting included)
+  unsigned long long* rayShards;
+};
 // the running-mean updates of nFrames pipelined frames over the rank's owned pixels (PackParams
 // mapping), in frame order: for f = 0 .. nFrames-1, accum = mix(accum, col + f * colStride,
 // 1 / (frameCounter + f + 1)) (IS:868-871, pass2.fsh:15) -- each pixel read and written once
 hipError_t launchMix(const PackParams& p, float4* accum, const float* col, size_t colStride, int nFrames,
-                     uint32_t frameCounter, hipStream_t s);
+                     uint32_t frameCounter, const SkyTiles& sky, hipStream_t s);
 // launchMix of a PT_FLAG_MOMENTS context (pt_display.hip mixFrames<true>): the same update of accum, and with the same
 // weights the running means (m1, m2) of each sample's luminance l and of l * l in `moments`
 hipError_t launchMixMoments(const PackParams& p, float4* accum, float2* moments, const float* col, size_t colStride,
-                            int nFrames, uint32_t frameCounter, hipStream_t s);
+                            int nFrames, uint32_t frameCounter, const SkyTiles& sky, hipStream_t s);
 // launchMixMoments of a PT_FLAG_ADAPTIVE context (mixFrames' third case): a pixel whose 8x8 tile is
 // retired (retiredAt, RenderParams::retiredAt's plane) is left alone, before any of its loads
 hipError_t launchMixAdaptive(const PackParams& p, float4* accum, float2* moments, const float* col, size_t colStride,
-                             int nFrames, uint32_t frameCounter, const uint32_t* retiredAt, hipStream_t s);
+                             int nFrames, uint32_t frameCounter, const uint32_t* retiredAt, const SkyTiles& sky,
+                             hipStream_t s);
 // Adaptive sampling's decision (pt_adaptive.hip tileErrorKernel, pt_abi.h pt_adaptive_update): one
 // wave per 8x8 wave tile of the context's share (the whole image with world 1), which is the image's
 // tile (y / 8) * tilesX + x / 8 of the two planes; a tile not yet retired takes err2 = the largest

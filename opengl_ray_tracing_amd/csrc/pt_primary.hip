@@ -216,9 +216,66 @@ hipError_t buildPrimaryBins(const float eye[3], const float cam[16], int width, 
   return hipGetLastError();
 }
 
+// The pass tiles of a share (PrimaryBins::passList): wave tile w is one when its image tile has a
+// non-empty bin -- a share tile wholly outside the image has none. One block walks the share's tiles
+// in order, as liveListKernel walks a queue's items: a ballot per wave, the waves' counts summed
+// through LDS, so the list is ascending. Its length lands behind it, at list[numItems].
+constexpr int PASS_BS = 1024;
+__global__ __launch_bounds__(PASS_BS) void passListKernel(Share share, int per, int numItems, const int* binStart,
+                                                          int tilesX, int tilesY, int* list) {
+  __shared__ int s_wave[PASS_BS / 64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int base = 0;
+  for (int w0 = 0; w0 < numItems; w0 += PASS_BS) {
+    const int w = w0 + (int)threadIdx.x;
+    bool in = false;
+    if (w < numItems) {
+      const int2 o = tileOrigin(share, w, per);
+      const int tx = o.x >> 3, ty = o.y >> 3;
+      if (tx < tilesX && ty < tilesY) in = binStart[ty * tilesX + tx + 1] > binStart[ty * tilesX + tx];
+    }
+    const unsigned long long b = __ballot(in);
+    if (lane == 0) s_wave[wv] = __popcll(b);
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int k = 0; k < PASS_BS / 64; k++) {
+      const int c = s_wave[k];
+      before += k < wv ? c : 0;
+      all += c;
+    }
+    if (in) list[base + before + __popcll(b & ((1ull << lane) - 1ull))] = w;
+    base += all;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) list[numItems] = base;
+}
+
+hipError_t buildPassList(const Share& share, PrimaryBins& b, hipStream_t s) {
+  const int numItems = waveTiles(share);
+  b.passCount = 0;
+  if (numItems <= 0) return hipSuccess;  // a rank that owns nothing
+  if (!b.binStart) return hipErrorInvalidValue;
+  hipError_t e;
+  if ((size_t)numItems + 1 > b.passListCap) {
+    if (b.passList) (void)hipFree(b.passList);
+    b.passList = nullptr;
+    b.passListCap = 0;
+    if ((e = hipMalloc(&b.passList, ((size_t)numItems + 1) * sizeof(int))) != hipSuccess) return e;
+    b.passListCap = (size_t)numItems + 1;
+  }
+  hipLaunchKernelGGL(passListKernel, dim3(1), dim3(PASS_BS), 0, s, share, shardTiles(share), numItems, b.binStart,
+                     b.tilesX, b.tilesY, b.passList);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  int count = 0;  // the launches' grid: a second host sync of a bin build
+  if ((e = hipMemcpyAsync(&count, b.passList + numItems, sizeof(int), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+  b.passCount = count;
+  return hipSuccess;
+}
+
 void freePrimaryBins(PrimaryBins& b) {
   for (void* p : {(void*)b.rect, (void*)b.triCount, (void*)b.triOffset, (void*)b.tileCount, (void*)b.binStart,
-                  (void*)b.binTris, (void*)b.binGeo, (void*)b.binBox, b.tmp})
+                  (void*)b.binTris, (void*)b.binGeo, (void*)b.binBox, (void*)b.passList, b.tmp})
     if (p) (void)hipFree(p);
   b = PrimaryBins{};
 }
@@ -231,7 +288,11 @@ void freePrimaryBins(PrimaryBins& b) {
 // waves cannot hide; here a launch of one short wave per tile keeps up to 8
 // waves per SIMD in flight and claims nothing. Sky pixels are finished here;
 // every other pixel's result goes to primHit for the megakernel.
-__global__ __launch_bounds__(64) void primaryKernel(RenderParams p) {
+// In a pipelined launch a tile whose camera-ray bin is empty is not given to this pass: the
+// running-mean update computes its samples (pt_kernels.h SkyTiles, pt_display.hip mixFrames). The
+// grid is then passList's tiles x nFrames, and the other tiles' masks stay the zeros the runtime
+// put there (pt_runtime.cpp bindBins). passList null: every tile of the share.
+__global__ __launch_bounds__(64) void primaryKernel(RenderParams p, const int* passList) {
   __shared__ float4 s_tri[PT_PASS_BIN_CAP * 4];
   __shared__ float4 s_box[PT_PASS_BIN_CAP * 2];
   __shared__ int s_idx[PT_PASS_BIN_CAP];
@@ -239,7 +300,8 @@ __global__ __launch_bounds__(64) void primaryKernel(RenderParams p) {
   // (Blocks of 2 / 4 / 8 such one-wave items, fewer workgroups for the dispatcher: c2's 1/8 share of
   // a 20-frame batch 88.6 -> 92.2 / 93.4 / 102.2 us; one block per tile for several frames: DESIGN.md 3b.)
   const int fr = (int)(blockIdx.x % (unsigned)p.nFrames);
-  const int w = (int)(blockIdx.x / (unsigned)p.nFrames);
+  const int item = (int)(blockIdx.x / (unsigned)p.nFrames);
+  const int w = passList ? passList[item] : item;
   const int lane = threadIdx.x;
   if (p.zeroQueue && blockIdx.x == 0)  // the frame kernel's work-queue counters, zeroed for it (it runs next on this stream)
     for (int q = lane; q < NUM_QUEUES; q += 64) p.queue[q * CTL_LINE_INTS] = 0;
@@ -310,9 +372,11 @@ __global__ __launch_bounds__(64) void primaryKernel(RenderParams p) {
   addRays(p.rayShards, rays);
 }
 
-hipError_t launchPrimary(const RenderParams& p, hipStream_t s) {
+hipError_t launchPrimary(const RenderParams& p, const int* passList, int passCount, hipStream_t s) {
   if (!p.primHit || !p.primMask || !p.binStart || !p.binGeo || !p.binBox || p.numItems <= 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(primaryKernel, dim3((unsigned)p.numItems * (unsigned)p.nFrames), dim3(64), 0, s, p);
+  if (passList && (passCount <= 0 || passCount > p.numItems)) return hipErrorInvalidValue;
+  const unsigned tiles = passList ? (unsigned)passCount : (unsigned)p.numItems;
+  hipLaunchKernelGGL(primaryKernel, dim3(tiles * (unsigned)p.nFrames), dim3(64), 0, s, p, passList);
   return hipGetLastError();
 }
 

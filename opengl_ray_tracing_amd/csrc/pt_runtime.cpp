@@ -499,17 +499,25 @@ static int tileOrderLists(pt_ctx* ctx, bool ordered, int slot, int** cost, int**
 
 // Camera-ray bins, rebuilt when the camera or the scene changed (the previous frame has ended
 // first: it may still read the old bins), and with a camera-ray pass the slot's results and lists
+// The one place that decides "a pipelined launch with bins and a pass" (p->col, set by the caller, and
+// results to write): its pass runs over the bins' pass list and its running-mean update takes the
+// other tiles' samples -- *sky is filled for both (binStart non-null), else left empty.
 static int bindBins(pt_ctx* ctx, const FramePlan& pl, const FrameSlot& at, const RegenShape& rs, int nF,
-                    const float eye[3], const float cameraRotate[16], RenderParams* p) {
+                    const float eye[3], const float cameraRotate[16], RenderParams* p, SkyTiles* sky) {
   const pt_config& c = ctx->cfg;
   hipStream_t S = at.S;
   if (!ctx->binsValid || ctx->binVersion != ctx->sceneVersion || std::memcmp(ctx->binEye, eye, sizeof(ctx->binEye)) ||
       std::memcmp(ctx->binCam, cameraRotate, sizeof(ctx->binCam))) {
     if (pl.piped) {
       if (int e = waitOthers(ctx, at)) return e;
+      // ... and the running-mean updates enqueued so far read the old bin starts (SkyTiles): the last one
+      // follows the others on the caller's stream
+      if (ctx->mixPending && S != ctx->lastMixStream) CK(hipStreamWaitEvent(S, ctx->mixDone[ctx->lastCol], 0));
     }
     ctx->binsValid = false;
     CK(buildPrimaryBins(eye, cameraRotate, c.width, c.height, ctx->d_geo, ctx->d_leafBox, ctx->nTri, ctx->bins, S));
+    CK(buildPassList(shareOf(ctx, c.tile_rank, c.tile_world), ctx->bins, S));
+    ctx->binBuilds++;
     std::memcpy(ctx->binEye, eye, sizeof(ctx->binEye));
     std::memcpy(ctx->binCam, cameraRotate, sizeof(ctx->binCam));
     ctx->binVersion = ctx->sceneVersion;
@@ -542,6 +550,32 @@ static int bindBins(pt_ctx* ctx, const FramePlan& pl, const FrameSlot& at, const
     return rc;
   p->primHit = ctx->d_prim[at.slot];
   p->primMask = reinterpret_cast<unsigned long long*>(ctx->d_prim[at.slot] + (size_t)ctx->primCap[at.slot] * p->colStride);
+  // (not on the scenes that outgrow the L2s: their persistent grids fill every CU for milliseconds, and the
+  // longer update waits for room as every kernel beside them does -- c5 4.03 -> 4.13 ms per frame with the
+  // rule; they keep the pass over every tile)
+  if (p->col && p->primHit && !pl.wideScene) {
+    sky->binStart = ctx->bins.binStart;
+    sky->binTilesX = ctx->bins.tilesX;
+    sky->sampleIndex = p->sampleIndex;
+    sky->sampleStride = p->sampleStride;
+    std::memcpy(sky->cam, cameraRotate, sizeof(sky->cam));
+    sky->env = p->env;
+    sky->rayShards = p->rayShards;
+    // The pass leaves the masks of the tiles outside its list alone, and every reader of its results
+    // (liveListKernel, primTileMask in the frame kernels) must find 0 there: the slot's whole mask region
+    // is zeroed before the slot's first such launch with this bin build or this buffer. On S, so after the
+    // slot's previous launch (its stream, or ordered before it: enqueueMix, pipeIdle) and before this pass;
+    // each slot does it for itself, after its wait for binsBuilt. Until the next build the unlisted tiles are
+    // the same ones, and a launch with the full grid writes them 0 as well (an empty bin leaves no path),
+    // so the zeros hold.
+    const int k = at.slot;
+    if (ctx->maskBuild[k] != ctx->binBuilds || ctx->maskBuf[k] != ctx->d_prim[k] || ctx->maskCap[k] != ctx->primCap[k]) {
+      CK(hipMemsetAsync(p->primMask, 0, (size_t)ctx->primCap[k] * ctx->numItems * sizeof(unsigned long long), S));
+      ctx->maskBuild[k] = ctx->binBuilds;
+      ctx->maskBuf[k] = ctx->d_prim[k];
+      ctx->maskCap[k] = ctx->primCap[k];
+    }
+  }
   // the regen kernels claim from per-queue lists of the tiles the pass left paths in (all variants
   // but the large scenes' MIS one, pt_regen.hip regenLists)
   if (pl.regen && regenTakesLists(c.integrator, rs)) {
@@ -558,7 +592,7 @@ static int bindBins(pt_ctx* ctx, const FramePlan& pl, const FrameSlot& at, const
 // The launch's own kernels on its stream, between the launch's begin and end events: the slot's
 // work-queue counters zeroed, the camera-ray pass and its lists, the frame kernel, the tile reorder
 static int enqueueFrame(pt_ctx* ctx, const FramePlan& pl, const FrameSlot& at, const LaunchShape& g, RenderParams& p,
-                        int* cost, int* order, int split) {
+                        const SkyTiles& sky, int* cost, int* order, int split) {
   const pt_config& c = ctx->cfg;
   hipStream_t S = at.S;
   hipEvent_t evb, eve;
@@ -576,11 +610,14 @@ static int enqueueFrame(pt_ctx* ctx, const FramePlan& pl, const FrameSlot& at, c
   }
   p.waveTrace = dTrace;
 #endif
+  // the pass over the bins' pass list (bindBins); an empty list launches no pass: every mask is 0 already
+  const int* passList = sky.binStart ? ctx->bins.passList : nullptr;
+  const bool passRuns = p.primHit && !(passList && ctx->bins.passCount == 0);
   // the slot's work-queue counters zeroed for this launch: by the camera-ray pass (block 0), else by a memset
-  p.zeroQueue = p.primHit != nullptr;
-  if (!p.primHit) CK(hipMemsetAsync(p.queue, 0, (size_t)NUM_QUEUES * CTL_LINE_INTS * sizeof(int), S));
+  p.zeroQueue = passRuns;
+  if (!passRuns) CK(hipMemsetAsync(p.queue, 0, (size_t)NUM_QUEUES * CTL_LINE_INTS * sizeof(int), S));
   CK(hipEventRecord(evb, S));
-  if (p.primHit) CK(launchPrimary(p, S));
+  if (passRuns) CK(launchPrimary(p, passList, ctx->bins.passCount, S));
   if (p.liveItems) CK(launchLiveList(p, S));  // the frame kernel claims only tiles the pass left paths in
   if (pl.regen) CK(launchRegen(p, c.integrator, g.grid, S, pl.cull, g.rs));
   else CK(launchRender(p, c.integrator, g.grid, S, pl.cull, pl.count, pl.wide));
@@ -613,7 +650,7 @@ static int enqueueFrame(pt_ctx* ctx, const FramePlan& pl, const FrameSlot& at, c
 
 // A pipelined launch's running-mean update: on the caller's stream, in frame order, after the
 // launch's kernels (direct: the frame's kernels updated the running mean themselves)
-static int enqueueMix(pt_ctx* ctx, const FrameSlot& at, int nF, bool direct, uint32_t frameCounter) {
+static int enqueueMix(pt_ctx* ctx, const FrameSlot& at, int nF, bool direct, uint32_t frameCounter, const SkyTiles& sky) {
   const pt_config& c = ctx->cfg;
   const int slot = at.slot, colIdx = at.colIdx;
   const size_t shareN = (size_t)ctx->numItems * 64;
@@ -631,16 +668,16 @@ static int enqueueMix(pt_ctx* ctx, const FrameSlot& at, int nF, bool direct, uin
       // a clear since then would be enqueued after this, on this stream -- or on the one the caller left)
       if (int rc = joinAdaptive(ctx)) return rc;
       CK(launchMixAdaptive(packParams(ctx, c.tile_rank, c.tile_world), ctx->d_accum, ctx->d_mom, ctx->d_col[colIdx],
-                           shareN, nF, frameCounter, ctx->d_retiredAt, ctx->stream));
+                           shareN, nF, frameCounter, ctx->d_retiredAt, sky, ctx->stream));
     } else {
       CK(launchMixMoments(packParams(ctx, c.tile_rank, c.tile_world), ctx->d_accum, ctx->d_mom, ctx->d_col[colIdx],
-                          shareN, nF, frameCounter, ctx->stream));
+                          shareN, nF, frameCounter, sky, ctx->stream));
     }
     // the frames the moments hold: a restart, a continuation, or a gap (not valid)
     ctx->momFrames = frameCounter == 0 ? (uint32_t)nF : (frameCounter == ctx->momFrames ? ctx->momFrames + (uint32_t)nF : 0u);
   } else if (!direct)
     CK(launchMix(packParams(ctx, c.tile_rank, c.tile_world), ctx->d_accum, ctx->d_col[colIdx], shareN, nF,
-                 frameCounter, ctx->stream));
+                 frameCounter, sky, ctx->stream));
   CK(hipEventRecord(ctx->mixDone[colIdx], ctx->stream));  // direct: the frame's kernels updated it
   ctx->lastSlot = slot;
   ctx->lastCol = colIdx;
@@ -731,8 +768,10 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
     }
     p.retiredAt = ctx->d_retiredAt;
   }
+  SkyTiles sky;  // the tiles the running-mean update shades (bindBins); empty: none
+  std::memset(&sky, 0, sizeof(sky));
   if (pl.bins)
-    if (int rc = bindBins(ctx, pl, at, g.rs, nF, eye, cameraRotate, &p)) return rc;
+    if (int rc = bindBins(ctx, pl, at, g.rs, nF, eye, cameraRotate, &p, &sky)) return rc;
   // a frame in band order (probePolicy) records no costs and launches no reorder; the
   // slot's last order list stays valid for its next ordered frame (any list covers every tile)
   // Batches of frames run unsplit (probePolicy) -- also on small screen-tile shares, whose launch lasts
@@ -748,9 +787,9 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
   if (piped && probing) {
     if (int e = waitOthers(ctx, at)) return e;
   }
-  if (int rc = enqueueFrame(ctx, pl, at, g, p, cost, order, splitThis ? splitPct : 0)) return rc;
+  if (int rc = enqueueFrame(ctx, pl, at, g, p, sky, cost, order, splitThis ? splitPct : 0)) return rc;
   if (piped)
-    if (int rc = enqueueMix(ctx, at, nF, direct, frameCounter)) return rc;
+    if (int rc = enqueueMix(ctx, at, nF, direct, frameCounter, sky)) return rc;
   commitLaunch(ctx, nF);
   return PT_OK;
 }

@@ -186,6 +186,12 @@ struct pt_ctx {
   // every other slot waits for it once before its first frame with those bins (binGen)
   hipEvent_t binsBuilt = nullptr;
   unsigned binGen = 0, binGenSeen[MAX_SLOTS] = {};
+  // A pipelined launch's camera-ray pass visits only the tiles of bins.passList, so the other tiles' masks
+  // in the slot's results must be zeros already: the slot's mask region is zeroed when the slot first takes
+  // such a launch with a new bin build (binBuilds) or a (re)allocated d_prim (bindBins)
+  unsigned binBuilds = 0, maskBuild[PIPE] = {};
+  const void* maskBuf[PIPE] = {};
+  int maskCap[PIPE] = {};
   float* d_col[COLS] = {};                  // per-colour-buffer sample colours (COL_F floats per slot)
   int2* d_prim[PIPE] = {};                  // per-slot camera-ray results (primaryKernel)
   uint4* d_live[PIPE] = {};                 // per-slot live-item lists and their counts (liveListKernel)
