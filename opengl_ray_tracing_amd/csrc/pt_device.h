@@ -140,27 +140,16 @@ __device__ __forceinline__ Material loadMaterial(const float4* q) {
 // Streaming (non-temporal) loads and stores for the env map and the
 // accumulation buffer: their lines are touched about once per frame, so they
 // are marked to leave L2 first and not evict the BVH and triangle lines every
-// traversal re-reads (PT_NT_STREAM=0: plain accesses).
-#ifndef PT_NT_STREAM
-#define PT_NT_STREAM 1
-#endif
+// traversal re-reads.
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float4 ldStream(const float4* p) {
-#if PT_NT_STREAM
   const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p));
   return make_float4(v.x, v.y, v.z, v.w);
-#else
-  return *p;
-#endif
 }
 __device__ __forceinline__ float2 ldStream(const float2* p) {
-#if PT_NT_STREAM
   const f32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x2_t*>(p));
   return make_float2(v.x, v.y);
-#else
-  return *p;
-#endif
 }
 // a pipelined frame's sample colour: COL_F = 3 floats per pixel (alpha is always 1, IS:871), 12 bytes
 // written by the frame kernel and read once by mixKernel (16 until round 6: c2 33 -> 25 MB each way)
@@ -168,41 +157,23 @@ __device__ __forceinline__ void stCol(float* p, float r, float g, float b) {
 #if PT_DIAG_NO_STORE
   if (r != -1234.5f) return;
 #endif
-#if PT_NT_STREAM
   __builtin_nontemporal_store(r, p);
   __builtin_nontemporal_store(g, p + 1);
   __builtin_nontemporal_store(b, p + 2);
-#else
-  p[0] = r;
-  p[1] = g;
-  p[2] = b;
-#endif
 }
 __device__ __forceinline__ float3 ldCol(const float* p) {
-#if PT_NT_STREAM
   return make_float3(__builtin_nontemporal_load(p), __builtin_nontemporal_load(p + 1), __builtin_nontemporal_load(p + 2));
-#else
-  return make_float3(p[0], p[1], p[2]);
-#endif
 }
 __device__ __forceinline__ void stStream(float4* p, float4 v) {
 #if PT_DIAG_NO_STORE  // diagnostics build (traffic attribution): colours almost never stored
   if (v.x != -1234.5f) return;
 #endif
-#if PT_NT_STREAM
   const f32x4_t x = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(x, reinterpret_cast<f32x4_t*>(p));
-#else
-  *p = v;
-#endif
 }
 __device__ __forceinline__ void stStream(float2* p, float2 v) {
-#if PT_NT_STREAM
   const f32x2_t x = {v.x, v.y};
   __builtin_nontemporal_store(x, reinterpret_cast<f32x2_t*>(p));
-#else
-  *p = v;
-#endif
 }
 
 // GL_NEAREST + GL_CLAMP_TO_EDGE addressing (OpenglRayTracing/main.cpp:184-194): the texel of (u, v)
@@ -225,19 +196,11 @@ __device__ __forceinline__ T texNearest(const T* img, int w, int h, float u, flo
 }
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint2 ldStream(const uint2* p) {
-#if PT_NT_STREAM
   const u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(p));
   return make_uint2(v.x, v.y);
-#else
-  return *p;
-#endif
 }
 __device__ __forceinline__ uint32_t ldStream(const uint32_t* p) {
-#if PT_NT_STREAM
   return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
 }
 // the compact env texels (pt_kernels.h Env): RGBE channels m * 2^(E - 136) -- exact products of an
 // integer below 256 and a power of two -- and the pdf's own bits; the sample table's float(x) / w,

@@ -23,10 +23,7 @@ __global__ __launch_bounds__(BLOCK) void guidesKernel(GuideParams p) {
   Stack st;
   st.init(s_stack, p.ovf, p.ovfDepth);
   Counters C = {0, 0, 0, 0, 0};
-  SceneView S = p.scene;  // no LDS copy of the top of the tree (as the ray queries, pt_query.hip)
-  S.nTop = 0;
-  S.fnTop = 0;
-  S.f4nTop = 0;
+  const SceneView S = noTopView(p.scene);  // no LDS copy of the top of the tree (as the ray queries, pt_query.hip)
   Tracer<CULL, false> tr{S, st, C, nullptr};
   const int W = p.width, H = p.height;
   const int tilesX = (W + 7) / 8, tilesY = (H + 7) / 8;

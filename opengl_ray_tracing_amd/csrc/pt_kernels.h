@@ -6,6 +6,15 @@
 
 namespace pt {
 
+// Structural switches retired at their shipped values (DESIGN.md "Retired build switches"): a build
+// that still passes one would get the shipped code whatever value it names
+#if defined(PT_FAST_TREE) || defined(PT_WIDE4) || defined(PT_FUSED_SLABS) || defined(PT_PACKETS) ||        \
+    defined(PT_NT_STREAM) || defined(PT_TILE_PRIM) || defined(PT_LDS_TREE) || defined(PT_REGEN_TOP4_3) ||    \
+    defined(PT_SPLIT_AUTO) || defined(PT_NO_BATCH_SPLIT_PROBE) || defined(PT_DIRECT_SOLO) ||                 \
+    defined(PT_CALL_MEGAKERNEL) || defined(PT_ROW_TABLE)
+#error "retired build switch: PT_FAST_TREE, PT_WIDE4, PT_FUSED_SLABS, PT_PACKETS, PT_NT_STREAM, PT_TILE_PRIM, PT_LDS_TREE, PT_REGEN_TOP4_3, PT_SPLIT_AUTO, PT_NO_BATCH_SPLIT_PROBE, PT_DIRECT_SOLO, PT_CALL_MEGAKERNEL and PT_ROW_TABLE are fixed (DESIGN.md)"
+#endif
+
 #ifndef PT_BLOCK
 #define PT_BLOCK 256  // 64 and 128 measured: c2 +18 % / +8 %, c4 -6 % / -2 %
 #endif
@@ -63,11 +72,9 @@ constexpr int LDS_STACK = PT_LDS_STACK;
 #endif
 // top-of-tree nodes (breadth-first from the root) the megakernel keeps in LDS, 64 B each
 constexpr int LDS_NODES = PT_LDS_NODES;
+static_assert(LDS_NODES > 0, "the frame kernels always stage the top of the tree in LDS");
 #ifndef PT_SPLIT_PCT
 #define PT_SPLIT_PCT 25  // megakernel: split a tile whose longest item costs more than this % of a wave's share
-#endif
-#ifndef PT_SPLIT_AUTO
-#define PT_SPLIT_AUTO 1  // the runtime measures its tree and split policies after each running-mean restart (probePolicy)
 #endif
 #ifndef PT_WAVE_TRACE
 #define PT_WAVE_TRACE 0  // diagnostics build: record each megakernel wave's lifetime (tools/wave_trace.py)
@@ -100,24 +107,12 @@ constexpr size_t CTL_QUEUES = 0;  // MAX_SLOTS x NUM_QUEUES padded int counters
 constexpr size_t CTL_STATS = (size_t)MAX_SLOTS * 64 * 256;            // 5 u64 cumulative fetch counters
 constexpr size_t CTL_RAYS = CTL_STATS + 256;                          // RAY_SHARDS padded u64 counters
 constexpr size_t CTL_BYTES = CTL_RAYS + (size_t)RAY_SHARDS * 256;
-#ifndef PT_FAST_TREE
-#define PT_FAST_TREE 1  // build and traverse the runtime's own tree (results checked against the reference's)
-#endif
-#ifndef PT_WIDE4
-// the megakernel's traced rays walk the runtime tree collapsed to 4-wide nodes (pt_trace.h
-// traceRay4; camera rays keep their bins and the binary tree's packets): 2 = with the 4-wide
-// tree's top 64 nodes in LDS (c2 0.408 -> 0.376 ms, c4 0.498 -> 0.477, c3 0.273 -> 0.262),
-// 1 = without (c3 0.257, c2 0.380), 0 = the binary runtime tree
-#define PT_WIDE4 2
-#endif
-#ifndef PT_FUSED_SLABS
-#define PT_FUSED_SLABS 1  // the runtime tree's slab tests as packed FMAs (pt_trace.h visitNodeF)
-#endif
+// The runtime builds and traverses its own tree (results checked against the reference's): the
+// megakernel's traced rays walk it collapsed to 4-wide nodes with that tree's top 64 nodes in LDS
+// (pt_trace.h traceRay4), its camera rays keep their bins and the binary tree's wave packets
+// (tracePacket), whose slab tests are fused (visitNodeF).
 #ifndef PT_ACCEL_LEAF
 #define PT_ACCEL_LEAF 4  // most triangles per leaf of the runtime's tree
-#endif
-#ifndef PT_PACKETS
-#define PT_PACKETS 1  // megakernel: camera rays as wave packets (pt_trace.h tracePacket)
 #endif
 constexpr int PKT_DEPTH = 128;    // camera-ray packet stack entries per wave (LDS); deeper trees trace per ray
 constexpr int PAIR_F4 = 7;        // float4 per pair record (26 floats: p1, p2, p3, Ng, w of two triangles)
@@ -153,7 +148,8 @@ struct SceneView {
   const float4* fbvh;
   const float4* fpairs;
   const int* fastTri;
-  int fRoot, fnTop;
+  int fRoot;
+  int fnTop;  // (read by the fetch-counting megakernel's staging alone, pt_kernels.hip renderKernel)
   // the same tree collapsed to 4-wide nodes (pt_scene_prep.cpp encodeWide4; pt_trace.h
   // traceRay4): W4_F4 float4 per node, breadth-first ids, leaves as in fbvh; null = none
   const float4* fbvh4;
@@ -529,7 +525,7 @@ struct RegenVariant {     // one instantiation of regenKernel and what the host 
   int waves = 0;          // waves per SIMD it is compiled for (0: the integrator's default)
   int block = BLOCK;      // threads per block
   bool lists = true;      // it claims from live-item lists after a camera-ray pass
-  int top4 = 0;           // 4-wide nodes it stages in LDS (PT_REGEN_TOP4[_3])
+  int top4 = 0;           // 4-wide nodes it stages in LDS (PT_REGEN_TOP4)
 };
 struct RegenShape {
   bool wide = false;      // the large-scene variant (WIDE_REGEN_WAVES, 4-wide walk, dynamic ray fetch)

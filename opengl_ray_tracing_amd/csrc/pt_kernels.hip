@@ -129,8 +129,8 @@ __device__ __forceinline__ int primaryPacket(const RenderParams& p, const FrameR
       tri = tr.trace(eye, dir, t);
     }
   } else if (p.scene.fast) {  // through the runtime's tree, checked against the reference's
-    const int pos = tracePacket<CULL, FAST_KIND>(fastView(p.scene), eye, dir, valid, t, tie, pstack, C,
-                                                  PT_WIDE4 == 2 ? nullptr : top);
+    // (the block's LDS holds the 4-wide tree's top, not this binary tree's: no top)
+    const int pos = tracePacket<CULL, NODE_FUSED>(fastView(p.scene), eye, dir, valid, t, tie, pstack, C, nullptr);
     tri = pos >= 0 ? p.scene.fastTri[pos] : -1;
     if (valid && (tie || (tri >= 0 && !refReachable(p.scene, tri, eye, dir, t)))) {
       C.rays--;  // the same ray, counted once
@@ -140,7 +140,7 @@ __device__ __forceinline__ int primaryPacket(const RenderParams& p, const FrameR
     tri = tracePacket<CULL>(p.scene, eye, dir, valid, t, tie, pstack, C, top);
     if (valid && tie) {
       C.rays--;
-      tri = traceRay<false, CULL, false, Stack, (LDS_NODES > 0)>(p.scene, eye, dir, t, st, C, false, top);
+      tri = traceRay<false, CULL, false, Stack, true>(p.scene, eye, dir, t, st, C, false, top);
     }
   }
   if (valid && tri < 0) {
@@ -335,21 +335,19 @@ __global__ __launch_bounds__(BLOCK, WAVES > 0 ? WAVES
   __shared__ unsigned s_drained;  // the work queues this block's waves found drained (TileCursor)
   if (threadIdx.x == 0) s_drained = 0;
   // the top of the tree (every ray's first node visits) staged in LDS once per block
-#if PT_LDS_NODES > 0
   __shared__ float4 s_nodes[LDS_NODES * 4];
   {
-    const bool w4 = PT_WIDE4 == 2 && !COUNT && p.scene.fast;  // the 4-wide tree's top
-    const float4* src = w4 ? p.scene.fbvh4 : p.scene.fast ? p.scene.fbvh : p.scene.bvh;  // the tree traversed first
+    const bool w4 = !COUNT && p.scene.fast;  // the 4-wide tree's top
+    // the tree the per-ray walks traverse first. (A fetch-counting launch never has p.scene.fast set,
+    // renderOne: the fbvh / fnTop arm, the binary runtime tree's, is never taken. Without it the COUNT
+    // kernels' code is 52 bytes shorter; it stays until a change means to alter them, DESIGN.md.)
+    const float4* src = w4 ? p.scene.fbvh4 : p.scene.fast ? p.scene.fbvh : p.scene.bvh;
     // the copy's size from the staged tree's own record kind (never the other tree's: DESIGN.md §8)
     const int n = w4 ? p.scene.f4nTop * W4_F4 : p.scene.fast ? p.scene.fnTop * 4 : p.scene.nTop * 4;
     for (int i = threadIdx.x; i < n; i += BLOCK) s_nodes[i] = src[i];
   }
   __syncthreads();
   const float4* top = s_nodes;
-#else
-  __syncthreads();
-  const float4* top = nullptr;
-#endif
   Counters C = {0, 0, 0, 0, 0};
   const int lane = threadIdx.x & 63;
   const int home = blockIdx.x & (NUM_QUEUES - 1);

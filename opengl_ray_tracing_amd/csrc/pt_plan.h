@@ -28,10 +28,6 @@ static constexpr int MAX_BATCH = PT_MAX_BATCH;  // most frames per launch (pt_re
 // regen kernel (c3) keeps 16 (24 / 32: 0.1107 -> 0.1122 / 0.1148)
 #define PT_BATCH_MIS_MK 32
 #endif
-// a single frame launched while nothing else is in flight (a display() call) runs on the megakernel
-#ifndef PT_CALL_MEGAKERNEL
-#define PT_CALL_MEGAKERNEL 1
-#endif
 #ifndef PT_TILE_GROUP
 #define PT_TILE_GROUP 1  // tiles ordered by cost in groups of this many consecutive tiles (1 measured best)
 #endif
@@ -42,12 +38,6 @@ static constexpr int MAX_BATCH = PT_MAX_BATCH;  // most frames per launch (pt_re
 #ifndef PT_GRID_PCT_WIDE
 #define PT_GRID_PCT_WIDE 150  // large scenes (c5: two frames per launch, ~8 ms launches): 4.44 ms at 125
 #endif
-// the table by rows for the megakernel's frames when the table outgrows an XCD's L2 share: c4's
-// frame kernel 216 -> 147 MB DRAM-side per frame, time unchanged (0.2914 / 0.2927 ms); its extra
-// dependent load costs the regen kernels more than their misses (c5 4.20 -> 4.31 ms, c3 0.1083 -> 0.111)
-#ifndef PT_ROW_TABLE
-#define PT_ROW_TABLE 1  // 0: never, 1: the megakernel's frames, 2: every frame (when the table outgrows 4 MB)
-#endif
 
 // the scene's records on the device (uploadScene keeps it in pt_ctx::sceneBytes)
 static inline size_t sceneBytes(int nTri, int nDevNodes) {
@@ -57,11 +47,12 @@ static inline size_t sceneBytes(int nTri, int nDevNodes) {
 // the scene's records outgrow the L2s by far (pt_kernels.h PT_WIDE_SCENE_MB)
 static inline bool largeScene(const pt_ctx* ctx) { return ctx->sceneBytes > ((size_t)PT_WIDE_SCENE_MB << 20); }
 
-// the env sample table by rows (PT_ROW_TABLE) for a launch of the regen kernel or of a lock-step one (the
-// megakernel, the radiance query)
+// the env sample table by rows for a launch of a lock-step kernel (the megakernel, the radiance query)
+// when the table outgrows an XCD's L2 share, 4 MB: c4's frame kernel 216 -> 147 MB DRAM-side per frame,
+// time unchanged (0.2914 / 0.2927 ms); never for the regen kernel (regen), whose walks the extra
+// dependent load costs more than their misses (c5 4.20 -> 4.31 ms, c3 0.1083 -> 0.111)
 static inline bool rowTable(const pt_ctx* ctx, bool regen) {
-  return PT_ROW_TABLE > 0 && (PT_ROW_TABLE == 2 || !regen) &&
-         (size_t)ctx->hdrW * ctx->hdrH * sizeof(uint32_t) > ((size_t)4 << 20);
+  return !regen && (size_t)ctx->hdrW * ctx->hdrH * sizeof(uint32_t) > ((size_t)4 << 20);
 }
 
 static inline int defaultBounce(int integ) {
@@ -173,7 +164,7 @@ static inline FramePlan planFrame(const pt_ctx* ctx, bool solo, int want) {
   // ends in its waves' last paths at falling lane counts: per call c3 0.585 -> 0.373 ms, c2 0.449 ->
   // 0.439 (c4 is on the megakernel already: 0.78; its regen kernel 1.32). Streams of frames keep
   // the regen kernel (c2's batches 0.17 ms per frame). PT_FLAG_REGEN pins the regen kernel.
-  f.oneCall = f.piped && solo && want == 1 && !largeScene(ctx) && ctx->regenWide <= 0 && PT_CALL_MEGAKERNEL;
+  f.oneCall = f.piped && solo && want == 1 && !largeScene(ctx) && ctx->regenWide <= 0;
   f.regen = !f.count && ((c.flags & PT_FLAG_REGEN) ||
                          ((f.wideScene || (f.regenAll && !f.oneCall)) && !(c.flags & PT_FLAG_MEGAKERNEL)));
   // the more-waves variant of either kernel (the regen kernel's with its 4-wide walk, dynamic ray

@@ -23,13 +23,6 @@
 
 namespace pt {
 
-__device__ __forceinline__ SceneView queryScene(const QueryParams& p) {
-  SceneView S = p.scene;  // no LDS copy of the top of the tree
-  S.nTop = 0;
-  S.fnTop = 0;
-  S.f4nTop = 0;
-  return S;
-}
 // ray k's bound: a bound past PT_INF admits nothing more (the unbounded query accepts only t < PT_INF); a
 // NaN stays one (no fminf, which would drop it), and fails the callers' b > 0.0005f
 __device__ __forceinline__ float loadBound(const QueryParams& p, size_t k) {
@@ -59,7 +52,7 @@ __global__ __launch_bounds__(BLOCK) void queryKernel(QueryParams p) {
   st.init(s_stack, p.ovf, p.ovfDepth);
   const size_t gtid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
   Counters C = {0, 0, 0, 0, 0};
-  const SceneView S = queryScene(p);
+  const SceneView S = noTopView(p.scene);
   Tracer<CULL, false> tr{S, st, C, nullptr};
   for (size_t k = gtid; k < (size_t)p.n; k += (size_t)gridDim.x * BLOCK) {
     V3 o, d;

@@ -35,10 +35,7 @@ __global__ __launch_bounds__(BLOCK, radianceWaves(INTEG)) void radianceKernel(Ra
   st.reset();
   const size_t gtid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
   Counters C = {0, 0, 0, 0, 0};
-  SceneView S = p.scene;  // no LDS copy of the top of the tree (as the ray queries, pt_query.hip)
-  S.nTop = 0;
-  S.fnTop = 0;
-  S.f4nTop = 0;
+  const SceneView S = noTopView(p.scene);  // no LDS copy of the top of the tree (as the ray queries, pt_query.hip)
   Tracer<CULL, false> tr{S, st, C, nullptr};
   for (size_t k = gtid; k < (size_t)p.n; k += (size_t)gridDim.x * BLOCK) {
     const float* r = p.rays + 6 * k;

@@ -37,10 +37,11 @@ constexpr int REGEN_LDS_STACK = PT_REGEN_LDS_STACK;
 // fit 128 VGPRs without spilling; the MIS state machine does not)
 // Dynamic ray fetch for the 4-wide walk (pt_trace.h walk4Run): a wave stops walking as soon
 // as this many of its walking lanes are done, and those lanes shade and take their next ray
-// while the others resume their walks (0 = every walk runs to its end first, traceRay4).
+// while the others resume their walks. The kernel has no other walk of the 4-wide tree.
 #ifndef PT_REGEN_YIELD
-#define PT_REGEN_YIELD 40  // c5: 0 (off) 6.97 ms, 8 6.98, 16 6.59, 32 5.78, 40 5.64, 48 5.63-5.71, 56 5.85, 60 6.17
+#define PT_REGEN_YIELD 40  // c5: 8 6.98 ms, 16 6.59, 32 5.78, 40 5.64, 48 5.63-5.71, 56 5.85, 60 6.17
 #endif
+static_assert(PT_REGEN_YIELD > 0, "the 4-wide walk is the resumable one (walk4Run): a yield threshold of at least one lane");
 #ifndef PT_REGEN_MIN_WAVES_U
 #define PT_REGEN_MIN_WAVES_U 4
 #endif
@@ -51,23 +52,17 @@ constexpr int REGEN_LDS_STACK = PT_REGEN_LDS_STACK;
 // 4-wide nodes of the runtime tree (breadth-first ids) the wide variant stages in LDS per block:
 // 128 (16 KB, with the 16 KB stack rows 4 blocks per CU) measured c2 0.248 -> 0.245 ms and
 // c5 7.98 -> 7.28 ms against 64; 192 (the LDS limit at 4 blocks) c2 0.247, c5 7.60
+// (at 3 waves per SIMD 128 too: c2 0.235 ms per frame; 256, which 3 blocks per CU would fit, 0.240)
 #ifndef PT_REGEN_TOP4
 #define PT_REGEN_TOP4 128
 #endif
-// ... and at 3 waves per SIMD (the uniform integrators' variant): 128 too (c2 0.235 ms per frame;
-// 256, which 3 blocks per CU would fit, 0.240)
-#ifndef PT_REGEN_TOP4_3
-#define PT_REGEN_TOP4_3 128
-#endif
-constexpr int regenTop4W(int waves) { return waves == 3 ? PT_REGEN_TOP4_3 : PT_REGEN_TOP4; }
+constexpr int REGEN_TOP4 = PT_REGEN_TOP4;
 
-// The camera-ray pass's results of a claimed tile loaded at once (lane k: slot k) and read by
-// the refilling lanes from their neighbours (0: each refilling lane loads its own). For the
-// uniform integrators only: c2 0.2226 -> 0.2173 ms per frame; the MIS kernel (4 waves, at its
-// register limit) spills more with the tile's results live, c5 5.69 -> 5.95 ms.
-#ifndef PT_TILE_PRIM
-#define PT_TILE_PRIM 1
-#endif
+// The tile hand-out (regenKernel's TILE_PRIM): the camera-ray pass's results of a claimed tile loaded
+// at once (lane k: slot k) and read by the refilling lanes from their neighbours, where otherwise each
+// refilling lane loads its own. For the uniform integrators only: c2 0.2226 -> 0.2173 ms per frame;
+// the MIS kernel (4 waves, at its register limit) spills more with the tile's results live, c5 5.69 ->
+// 5.95 ms.
 // (The MIS kernel keeps the per-lane load: at its 128-VGPR limit it spilled 36 more VGPRs with the
 // hand-out's state; materials staged in LDS per block measured c2 -0.6 %, within noise. Both knobs
 // were deleted in round 6, git history keeps them.)
@@ -298,8 +293,7 @@ template <int INTEG, bool CULL, int WAVES = 0, bool W4 = false, int BS = BLOCK, 
 __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_WAVES_MIS : PT_REGEN_MIN_WAVES_U)) void regenKernel(
     RenderParams p) {
   static_assert(!FULL || W4, "the LDS tree is the 4-wide one");
-  static_assert(!FULL || PT_REGEN_YIELD > 0, "the whole LDS tree is walked by walk4Run (loadNode4Lds) only");
-  constexpr bool TILE_PRIM = PT_TILE_PRIM && INTEG != 2;
+  constexpr bool TILE_PRIM = INTEG != 2;
   // the large scenes' MIS variant takes no live lists (regenLists): it compiles the claim
   // it had, next() and the pass's mask array
   constexpr bool LISTS = regenLists(INTEG, WAVES);
@@ -310,9 +304,7 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
   __shared__ unsigned s_drained;  // the work queues this block's waves found drained (TileCursor)
   if (threadIdx.x == 0) s_drained = 0;
   // the top of the tree (every ray's first node visits) -- or all of it -- staged in LDS once per block
-#if PT_LDS_NODES > 0
-  constexpr int TOP4 = regenTop4W(WAVES);
-  constexpr int TOPF4 = FULL ? 1 : (W4 && TOP4 * W4_F4 > LDS_NODES * 4) ? TOP4 * W4_F4 : LDS_NODES * 4;
+  constexpr int TOPF4 = FULL ? 1 : (W4 && REGEN_TOP4 * W4_F4 > LDS_NODES * 4) ? REGEN_TOP4 * W4_F4 : LDS_NODES * 4;
   __shared__ float4 s_nodes[TOPF4];
   extern __shared__ float4 s_tree[];  // FULL: f4nTop * W4_LDS_F4 float4 (launch's dynamic LDS)
   if (FULL) {
@@ -327,10 +319,6 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
   }
   __syncthreads();
   const float4* top = FULL ? s_tree : s_nodes;
-#else
-  __syncthreads();
-  const float4* top = nullptr;
-#endif
   Counters C = {0, 0, 0, 0, 0};
   const int lane = threadIdx.x & 63;
   const int home = blockIdx.x & (NUM_QUEUES - 1);
@@ -351,7 +339,7 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
   unsigned char* s_slot = s_slotAll + (TILE_PRIM ? waveBase : 0);
   int2* s_hit = s_hitAll + (TILE_PRIM ? waveBase : 0);
   bool active = false;
-  bool walking = false;  // PT_REGEN_YIELD: the lane's ray has a walk in progress (w, st)
+  bool walking = false;  // the lane's ray has a walk in progress (w, st)
   Walk4 w;
   PathState s;
   s.px = s.py = s.fr = 0;
@@ -571,7 +559,7 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
 #if PT_PHASE_STATS
     long long phT = 0;
 #endif
-    if (PT_REGEN_YIELD > 0 && W4 && p.scene.fast) {
+    if (W4 && p.scene.fast) {
       if (!walking) {
         walk4Begin(p.scene, w, st, C);
         walking = true;
@@ -581,9 +569,8 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
       PH_ADD(5, __popcll(act));
       phT = clock64();
 #endif
-      walk4Run<CULL, StackT<REGEN_LDS_STACK, BS>, (LDS_NODES > 0), FULL,
-               INTEG == 2 ? PT_LEAF_WAIT_MIS : PT_LEAF_WAIT_U>(p.scene, s.o, s.d, s.kind == K_SHADOW, w, st, top,
-                                                              PT_REGEN_YIELD, ph);
+      walk4Run<CULL, StackT<REGEN_LDS_STACK, BS>, true, FULL, INTEG == 2 ? PT_LEAF_WAIT_MIS : PT_LEAF_WAIT_U>(
+          p.scene, s.o, s.d, s.kind == K_SHADOW, w, st, top, PT_REGEN_YIELD, ph);
 #if PT_PHASE_STATS
       PH_ADD(1, clock64() - phT);
       if (__ballot(!walk4Done(w)) == 0) PH_ADD(13, 1);
@@ -609,17 +596,9 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
       PH_ADD(6, __popcll(__ballot(1)));
       phT = clock64();
 #endif
-    } else if (W4 && p.scene.fast) {
-      bool tie = false;
-      tri = traceRay4<CULL, StackT<REGEN_LDS_STACK, BS>, (LDS_NODES > 0)>(p.scene, s.o, s.d, t, st, C,
-                                                                         s.kind == K_SHADOW, top, &tie);
-      if (tie || (tri >= 0 && !refReachable(p.scene, tri, s.o, s.d, t))) {
-        C.rays--;  // the same ray, counted once
-        tri = traceRay<false, CULL, false>(p.scene, s.o, s.d, t, st, C, s.kind == K_SHADOW);
-      }
     } else {
-      tri = traceRay<false, CULL, false, StackT<REGEN_LDS_STACK, BS>, (LDS_NODES > 0)>(
-          p.scene, s.o, s.d, t, st, C, s.kind == K_SHADOW, top);
+      tri = traceRay<false, CULL, false, StackT<REGEN_LDS_STACK, BS>, true>(p.scene, s.o, s.d, t, st, C,
+                                                                            s.kind == K_SHADOW, top);
     }
     V3 color;
     if (!advance<INTEG>(p, s, tri, t, color)) {
@@ -647,21 +626,17 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
 
 // The FULL variant: the uniform integrators' wide kernel (PT_WIDE_REGEN_WAVES_U = 4 waves per
 // SIMD) as one block of all the CU's waves, the whole tree beside their 16-entry LDS stacks
-// (PT_LDS_TREE = 0: never)
-#ifndef PT_LDS_TREE
-#define PT_LDS_TREE 1
-#endif
 constexpr int FULL_BS = 256 * PT_WIDE_REGEN_WAVES_U;  // one block per CU: all its waves share the tree
 constexpr size_t LDS_BYTES = 160 * 1024;
 // The one statement of which instantiation a frame runs and of what follows from it (RegenVariant):
 // regenShape keeps it, launchRegen launches its fn, the runtime reads its lists / top4 / block.
 template <int I, bool CULL, int WAVES = 0, bool W4 = false, int BS = BLOCK, bool FULL = false>
 static RegenVariant variantOf() {
-  return {(const void*)regenKernel<I, CULL, WAVES, W4, BS, FULL>, WAVES, BS, regenLists(I, WAVES), regenTop4W(WAVES)};
+  return {(const void*)regenKernel<I, CULL, WAVES, W4, BS, FULL>, WAVES, BS, regenLists(I, WAVES), REGEN_TOP4};
 }
 template <int I>
 static RegenVariant regenVariantI(bool cull, bool wide, bool small, bool full) {
-  if constexpr (I != 2 && PT_REGEN_YIELD > 0)  // the uniform integrators' variant only
+  if constexpr (I != 2)  // the uniform integrators' variant only
     if (full) return variantOf<I, true, wideRegenWaves(I), true, FULL_BS, true>();
   if constexpr (I == 2 && PT_WIDE_REGEN_WAVES_SMALL != PT_WIDE_REGEN_WAVES)
     if (wide && small) return variantOf<I, true, PT_WIDE_REGEN_WAVES_SMALL, true>();
@@ -688,15 +663,13 @@ hipError_t regenShape(int integrator, bool cull, bool wide, int f4nDev, bool sma
   // the FULL variant's static LDS (stack rows, hand-out rows, phase counters) as compiled
   // (a property of the code object, the same on every device: read once per integrator)
   size_t staticBytes = 0;
-  if (PT_LDS_TREE && PT_REGEN_YIELD > 0 && r.wide && integrator != 2 && f4nDev > 0) {
+  if (r.wide && integrator != 2 && f4nDev > 0) {
     static const long long cached[2] = {fullStaticLds(0), fullStaticLds(1)};
     if (cached[integrator] < 0) return hipErrorInvalidDeviceFunction;
     staticBytes = (size_t)cached[integrator];
   }
-  // the whole tree in LDS needs the resumable walk (walk4Run's ALL records): with PT_REGEN_YIELD = 0
-  // the walks run traceRay4, which reads an LDS top at the built 8-float4 stride
-  r.fullTree = PT_LDS_TREE && PT_REGEN_YIELD > 0 && r.wide && integrator != 2 && f4nDev > 0 &&
-               treeBytes + staticBytes <= LDS_BYTES;
+  // (the whole tree in LDS is read by the resumable walk alone: walk4Run's ALL records)
+  r.fullTree = r.wide && integrator != 2 && f4nDev > 0 && treeBytes + staticBytes <= LDS_BYTES;
   r.dynLds = r.fullTree ? treeBytes : 0;
   r.v = regenVariant(integrator, cull, r.wide, r.small, r.fullTree);
   const void* f = r.v.fn;

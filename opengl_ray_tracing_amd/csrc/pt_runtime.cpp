@@ -21,11 +21,6 @@
 
 using namespace pt;
 
-// a launch of one frame while nothing else is in flight mixes its samples into the running mean in
-// its own kernels (renderOne: no colour buffer, no mixKernel launch)
-#ifndef PT_DIRECT_SOLO
-#define PT_DIRECT_SOLO 1
-#endif
 static_assert(PT_PIPE >= 1 && PT_PIPE <= PIPE, "PT_PIPE: 1..MAX_SLOTS");
 static_assert(PIPE * NUM_QUEUES * CTL_LINE_INTS * 4 <= (int)CTL_STATS, "queue counters of every slot fit the control block");
 
@@ -255,7 +250,6 @@ static int probePolicy(pt_ctx* ctx, uint32_t frameCounter, bool ordered, bool fa
   *useFast = fastAllowed;
   ctx->tagSlot = -1;
   if (!ordered) return 0;
-  if (!PT_SPLIT_AUTO) return PT_SPLIT_PCT;
   if (frameCounter == 0) {
     ctx->probeGen++;
     ctx->probeFrame = 0;
@@ -272,9 +266,6 @@ static int probePolicy(pt_ctx* ctx, uint32_t frameCounter, bool ordered, bool fa
     // 1/8 share 0.075 -> 0.070 ms (20 frames) and 0.054 -> 0.048 (200 frames, split at 50 %). A launch
     // of one frame (a display() call) is split when the probe found it faster.
     // (launchReorder applies the split only to launches of one frame, renderOne)
-#if PT_NO_BATCH_SPLIT_PROBE
-    if (ctx->pipe && ctx->batchCap > 1) ctx->splitDecided = 0;
-#endif
     ctx->probedKey = ctx->policyKey;
     // split state and cost estimates start over (the camera or scene changed), in every slot's
     // stream order (after its last reorder, before its next frame): this launch's slot on the stream
@@ -734,10 +725,10 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
     p.scene.f4nTop = g.rs.fullTree ? ctx->f4nDev : std::min(regenTop4(g.rs, c.integrator), ctx->f4nDev);
   p.scene.fast = useFast ? 1 : 0;
   ctx->lastFast = useFast;
-  p.packets = PT_PACKETS && (useFast ? ctx->fDepth : ctx->depth) + 1 <= PKT_DEPTH;
-  // While the policy probe times frames (PT_SPLIT_AUTO, 20 frames after a restart) a pipelined
+  p.packets = (useFast ? ctx->fDepth : ctx->depth) + 1 <= PKT_DEPTH;
+  // While the policy probe times frames (probePolicy, 20 frames after a restart) a pipelined
   // frame starts only after the previous one has ended, and each launch is one frame.
-  const bool probing = pl.ordered && PT_SPLIT_AUTO && (ctx->treeDecided < 0 || ctx->splitDecided < 0);
+  const bool probing = pl.ordered && (ctx->treeDecided < 0 || ctx->splitDecided < 0);
   const int nF = piped && !probing ? std::max(1, std::min(want, ctx->batchCap)) : 1;
   if (done) *done = nF;
   p.nFrames = nF;
@@ -748,7 +739,7 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
   // The regen kernel keeps the update launch: the read of the running mean at each path's end stalls
   // its lock-step waves (c2 0.455 either way, c3 0.578 -> 0.587 ms)
   // A PT_FLAG_MOMENTS context never does: its samples pass through the colour buffer to mixMomentsKernel.
-  const bool direct = piped && at.solo && nF == 1 && !pl.regen && PT_DIRECT_SOLO && !ctx->d_mom;
+  const bool direct = piped && at.solo && nF == 1 && !pl.regen && !ctx->d_mom;
   if (direct && ctx->mixPending && ctx->lastMixStream != S) CK(hipStreamWaitEvent(S, ctx->mixDone[ctx->lastCol], 0));
   if (piped) {
     // its last frames' running-mean update has read the colour buffer

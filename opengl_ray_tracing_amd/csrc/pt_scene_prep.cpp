@@ -283,7 +283,6 @@ static void buildPairs(const std::vector<float4>& geo, const int* order, int nTr
 // failed build, leaves the runtime on the reference tree alone (h.fast false).
 static void prepareAccel(const float* tris, int nTri, const float* nodes, int nNodes, SceneHost& h, bool hostBuild) {
   h.fast = false;
-  if (!PT_FAST_TREE) return;
   const NodeView nv{nodes, nNodes};
   std::vector<int>& leafOf = h.leafOf;
   std::vector<int>& parent = h.parent;

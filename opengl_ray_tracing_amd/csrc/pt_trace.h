@@ -176,11 +176,10 @@ __device__ __forceinline__ FusedRay fusedRay(V3 o, V3 inv) {
   f.noi = v3(-(o.x * f.inv.x), -(o.y * f.inv.y), -(o.z * f.inv.z));
   return f;
 }
-// Node kinds, a compile-time property of a traversal: the reference tree's
-// exact records and slab tests (NODE_EXACT) or the runtime tree's records with
+// Node kinds, a compile-time property of a packet traversal (tracePacket): the reference tree's
+// exact records and slab tests (NODE_EXACT) or the binary runtime tree's records with
 // fused slab tests (NODE_FUSED).
 constexpr int NODE_EXACT = 0, NODE_FUSED = 2;
-constexpr int FAST_KIND = PT_FUSED_SLABS ? NODE_FUSED : NODE_EXACT;
 template <int KIND>
 __device__ __forceinline__ void visitAny(const float4* nd, V3 o, V3 inv, const FusedRay& fr, NodeHit& h) {
   if (KIND == NODE_FUSED) visitNodeF(nd, fr.inv, fr.noi, h);
@@ -266,6 +265,8 @@ __device__ __forceinline__ bool triHit(const float4* g, V3 o, V3 d, float tmax, 
 
 __device__ __forceinline__ bool isLeafRef(int ref) { return ref < 0 && ref != REF_NONE; }
 
+// The reference-order walk of the uploaded tree, one ray per lane: what every other walk's result
+// is checked against and retraced through.
 // hitBVH IS:335-382: same visiting order of the leaves (nearer child by the
 // reference's d first, ties to the right child), strict '<' closest update, so
 // the same triangle wins even on exact-t ties. CULL skips children whose slab
@@ -286,19 +287,13 @@ __device__ __forceinline__ bool isLeafRef(int ref) { return ref < 0 && ref != RE
 // tree -- read in place of the global records (one flat load serves lanes in
 // both address spaces).
 //
-// TIES: *tie is set when a lane meets a triangle at exactly its current closest
-// t (the visiting order decides such ties; see refReachable).
-//
 // BOUNDED (the ray queries, pt_query.hip): the closest-hit bound starts at `bound` instead of PT_INF, so
 // only triangles with t < bound can win, and among them the same least-t, first-in-order one does. A
 // compile-time switch: without it `bound` is not read, and the frame kernels' walks are what they were.
-template <bool ANYHIT, bool CULL, bool COUNT, class StackType, bool LDSTOP = false, bool TIES = false,
-          int KIND = NODE_EXACT, bool BOUNDED = false>
+template <bool ANYHIT, bool CULL, bool COUNT, class StackType, bool LDSTOP = false, bool BOUNDED = false>
 __device__ __forceinline__ int traceRay(const SceneView& S, V3 o, V3 d, float& tOut, StackType& st, Counters& C,
-                                        bool anyRT = false, const float4* top = nullptr, bool* tie = nullptr,
-                                        float bound = PT_INF) {
+                                        bool anyRT = false, const float4* top = nullptr, float bound = PT_INF) {
   V3 inv = v3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-  const FusedRay fr = fusedRay(o, inv);  // NODE_FUSED
   float tbest = BOUNDED ? bound : PT_INF;
   int best = -1;
   int ref = S.rootRef;   // next item in visiting order (REF_NONE only when the stack is empty too)
@@ -315,7 +310,7 @@ __device__ __forceinline__ int traceRay(const SceneView& S, V3 o, V3 d, float& t
       NodeHit nh;
       const float4* nd = S.bvh + (size_t)4 * ref;
       if (LDSTOP && ref < S.nTop) nd = top + 4 * ref;
-      visitAny<KIND>(nd, o, inv, fr, nh);
+      visitNode(nd, o, inv, nh);
       const int lref = nh.lref, rref = nh.rref;
       const float d1 = nh.d1, d2 = nh.d2, t0l = nh.t0l, t0r = nh.t0r;
       bool h1 = (lref != REF_NONE) && d1 > 0.0f;
@@ -384,13 +379,11 @@ __device__ __forceinline__ int traceRay(const SceneView& S, V3 o, V3 d, float& t
           if (h1 && t1 < localBest) { localBest = t1; C.mats++; }
           if (h1 && t1 < tbest) { tbest = t1; best = i + 1; }
         } else {
-          if (TIES && g0 && t0 == tbest) *tie = true;
           if (g0 && t0 < tbest) {
             tbest = t0;
             best = i;
             if (ANYHIT || anyRT) { tOut = tbest; return best; }
           }
-          if (TIES && g1 && second && t1 == tbest) *tie = true;
           if (g1 && second && t1 < tbest) {
             tbest = t1;
             best = i + 1;
@@ -412,8 +405,9 @@ __device__ __forceinline__ int traceRay(const SceneView& S, V3 o, V3 d, float& t
 // near: about half the dependent node fetches of the binary walk, for
 // memory-latency-bound walks of large scenes (the regen kernel on scenes past
 // PT_WIDE_SCENE_MB). Results are checked exactly like the binary runtime
-// tree's (the order of visits only matters for exact-t ties, which are
-// flagged: refReachable, the retrace in the reference order). The walks return the
+// tree's packets' (the order of visits only matters for exact-t ties, which are
+// flagged: *tie is set when a lane meets a triangle at exactly its current closest t;
+// refReachable, the retrace in the reference order). The walks return the
 // winner's uploaded triangle index, read from its pair record (pairTestIds), so the
 // reference check starts without a lookup of S.fastTri.
 constexpr float PT_INF_KEY = __builtin_huge_valf();  // sort key of a missed child (every entry t is finite)
@@ -562,7 +556,7 @@ __device__ __forceinline__ int traceRay4(const SceneView& S, V3 o, V3 d, float& 
 #define PT_LEAF_WAIT_MIS 12
 #endif
 // traceRay4 as a walk that can stop and resume (the regen kernel's dynamic ray
-// fetch, PT_REGEN_YIELD): the walk's state is a Walk4 plus the lane's stack, and
+// fetch, pt_regen.hip): the walk's state is a Walk4 plus the lane's stack, and
 // walk4Run returns once the lane's walk is done -- or, for the whole wave, as
 // soon as `yield` of the lanes walking with it are done, so that those lanes go
 // on with their paths (shade, take the next ray or pixel) instead of idling
@@ -767,14 +761,22 @@ template <bool UP = false>
 __device__ __forceinline__ bool refReachable(const SceneView& S, int tri, V3 o, V3 d, float t) {
   return refReachableBox<UP>(S, S.leafBox[2 * (size_t)tri], S.leafBox[2 * (size_t)tri + 1], o, d, t);
 }
-// the runtime's tree as a SceneView for traceRay / tracePacket
+// the binary runtime tree as a SceneView for tracePacket (no kernel stages its top in LDS)
 __device__ __forceinline__ SceneView fastView(const SceneView& S) {
   SceneView F = S;
   F.bvh = S.fbvh;
   F.pairs = S.fpairs;
   F.rootRef = S.fRoot;
-  F.nTop = S.fnTop;
+  F.nTop = 0;
   return F;
+}
+// the scene for walks without an LDS copy of a tree's top (Tracer::top null): the walks read `top`
+// for every node id below nTop / f4nTop, so both are 0
+__device__ __forceinline__ SceneView noTopView(const SceneView& S) {
+  SceneView V = S;
+  V.nTop = 0;
+  V.f4nTop = 0;
+  return V;
 }
 
 // ----------------------------------------------------------------- camera-ray packets
@@ -1066,32 +1068,11 @@ struct Tracer {
   const SceneView& S;
   Stack& st;
   Counters& C;
-  const float4* top;  // LDS copy of the top of the tree traversed first (null = none)
-  // closest hit: the triangle (-1 = miss) and its t. With S.fast, through the
-  // runtime's tree and checked against the reference's (pt_trace.h refReachable).
-  __device__ __forceinline__ int trace(V3 o, V3 d, float& t) {
-    if (PT_WIDE4 && !COUNT && S.fast) {  // the 4-wide runtime tree (PT_WIDE4), checked as the binary one
-      bool tie = false;
-      int tri = traceRay4<CULL, Stack, (PT_WIDE4 == 2)>(S, o, d, t, st, C, false, top, &tie);
-      if (tie || (tri >= 0 && !refReachable(S, tri, o, d, t))) {
-        C.rays--;
-        tri = traceRay<false, CULL, false, Stack>(S, o, d, t, st, C);
-      }
-      return tri;
-    }
-    if (!COUNT && S.fast) {
-      bool tie = false;
-      const SceneView F = fastView(S);
-      const int pos = traceRay<false, CULL, false, Stack, (LDS_NODES > 0), true, FAST_KIND>(F, o, d, t, st, C, false, top, &tie);
-      int tri = pos >= 0 ? S.fastTri[pos] : -1;
-      if (tie || (tri >= 0 && !refReachable(S, tri, o, d, t))) {
-        C.rays--;  // the same ray, counted once
-        tri = traceRay<false, CULL, false, Stack>(S, o, d, t, st, C);
-      }
-      return tri;
-    }
-    return traceRay<false, CULL, COUNT, Stack, (LDS_NODES > 0)>(S, o, d, t, st, C, false, top);
-  }
+  // LDS copy of the top of the tree traversed first: the 4-wide tree's (!COUNT && S.fast) or the
+  // uploaded tree's. Null = none, which requires S = noTopView(...).
+  const float4* top;
+  // closest hit: the triangle (-1 = miss) and its t
+  __device__ __forceinline__ int trace(V3 o, V3 d, float& t) { return walk<false>(o, d, false, PT_INF, t); }
   __device__ __forceinline__ bool closest(V3 o, V3 d, Hit& h) {
     float t;
     const int tri = trace(o, d, t);
@@ -1099,43 +1080,15 @@ struct Tracer {
     finishHit(S, tri, o, d, t, h);
     return true;
   }
+  // env shadow query (IS:776-779: only isHit is read)
   __device__ __forceinline__ bool occluded(V3 o, V3 d) {
     float t;
-    if (PT_WIDE4 && !COUNT && S.fast) {
-      bool tie = false;
-      const int tri = traceRay4<CULL, Stack, (PT_WIDE4 == 2)>(S, o, d, t, st, C, true, top, &tie);
-      if (tri < 0) return false;
-      if (refReachable(S, tri, o, d, t)) return true;
-      C.rays--;
-      return traceRay<true, CULL, false, Stack>(S, o, d, t, st, C) >= 0;
-    }
-    if (!COUNT && S.fast) {
-      const SceneView F = fastView(S);
-      const int pos = traceRay<true, CULL, false, Stack, (LDS_NODES > 0), false, FAST_KIND>(F, o, d, t, st, C, false, top);
-      if (pos < 0) return false;
-      if (refReachable(S, S.fastTri[pos], o, d, t)) return true;
-      C.rays--;
-      return traceRay<true, CULL, false, Stack>(S, o, d, t, st, C) >= 0;
-    }
-    // COUNT reproduces the reference's closest-hit shadow query fetch by fetch
-    return traceRay<!COUNT, CULL, COUNT, Stack, (LDS_NODES > 0)>(S, o, d, t, st, C, false, top) >= 0;
+    return walk<false>(o, d, true, PT_INF, t) >= 0;
   }
   // closest (anyhit false) or env-shadow (anyhit true: >= 0 = occluded) query through ONE call site
-  // of the traversal, so a path loop that traces its shadow and BRDF rays from the same place
-  // keeps one copy of the walk (and its registers) live: trace() / occluded() per lane
-  __device__ __forceinline__ int traceK(V3 o, V3 d, bool anyhit, float& t) {
-    if (PT_WIDE4 && !COUNT && S.fast) {
-      bool tie = false;
-      int tri = traceRay4<CULL, Stack, (PT_WIDE4 == 2)>(S, o, d, t, st, C, anyhit, top, &tie);
-      if ((tie && !anyhit) || (tri >= 0 && !refReachable(S, tri, o, d, t))) {
-        C.rays--;  // the same ray, counted once
-        tri = traceRay<false, CULL, false, Stack>(S, o, d, t, st, C, anyhit);
-      }
-      return tri;
-    }
-    if (anyhit) return occluded(o, d) ? 0 : -1;
-    return trace(o, d, t);
-  }
+  // of the walk, so a path loop that traces its shadow and BRDF rays from the same place
+  // keeps one copy of the 4-wide walk (and its registers) live: trace() / occluded() per lane
+  __device__ __forceinline__ int traceK(V3 o, V3 d, bool anyhit, float& t) { return walk<false>(o, d, anyhit, PT_INF, t); }
   // The ray queries' forms (pt_query.hip; pt_abi.h pt_trace_closest_device, pt_trace_occluded_device): trace()
   // and occluded() with the closest-hit bound starting at b (b <= PT_INF, not a NaN) instead of PT_INF, a
   // walk's BOUNDED switch. refReachable's argument holds under a bound: the runtime tree's walk meets every
@@ -1144,56 +1097,45 @@ struct Tracer {
   // costs a retrace) or an unreachable winner retraces in the reference order with the same bound; a miss
   // stands. An any-hit result stands when its triangle is reachable: the reference's closest t is then no
   // larger, so it is below b as well.
-  __device__ __forceinline__ int traceBounded(V3 o, V3 d, float b, float& t) {
-    if (PT_WIDE4 && !COUNT && S.fast) {
-      bool tie = false;
-      int tri = traceRay4<CULL, Stack, (PT_WIDE4 == 2), true>(S, o, d, t, st, C, false, top, &tie, b);
-      if (tie || (tri >= 0 && !refReachable(S, tri, o, d, t))) {
-        C.rays--;
-        tri = traceRay<false, CULL, false, Stack, false, false, NODE_EXACT, true>(S, o, d, t, st, C, false, nullptr,
-                                                                                  nullptr, b);
-      }
-      return tri;
-    }
-    if (!COUNT && S.fast) {
-      bool tie = false;
-      const SceneView F = fastView(S);
-      const int pos = traceRay<false, CULL, false, Stack, (LDS_NODES > 0), true, FAST_KIND, true>(F, o, d, t, st, C,
-                                                                                                  false, top, &tie, b);
-      int tri = pos >= 0 ? S.fastTri[pos] : -1;
-      if (tie || (tri >= 0 && !refReachable(S, tri, o, d, t))) {
-        C.rays--;
-        tri = traceRay<false, CULL, false, Stack, false, false, NODE_EXACT, true>(S, o, d, t, st, C, false, nullptr,
-                                                                                  nullptr, b);
-      }
-      return tri;
-    }
-    return traceRay<false, CULL, COUNT, Stack, (LDS_NODES > 0), false, NODE_EXACT, true>(S, o, d, t, st, C, false, top,
-                                                                                         nullptr, b);
-  }
+  __device__ __forceinline__ int traceBounded(V3 o, V3 d, float b, float& t) { return walk<true>(o, d, false, b, t); }
   __device__ __forceinline__ bool occludedBounded(V3 o, V3 d, float b) {
     float t;
-    if (PT_WIDE4 && !COUNT && S.fast) {
+    // walk<true>(o, d, true, b, t) >= 0, written out with its results as constants: through walk the
+    // compiler merges the occlusion query kernel's result stores (28 bytes less code)
+    if (!COUNT && S.fast) {
       bool tie = false;
-      const int tri = traceRay4<CULL, Stack, (PT_WIDE4 == 2), true>(S, o, d, t, st, C, true, top, &tie, b);
+      const int tri = traceRay4<CULL, Stack, true, true>(S, o, d, t, st, C, true, top, &tie, b);
       if (tri < 0) return false;
       if (refReachable(S, tri, o, d, t)) return true;
       C.rays--;
-      return traceRay<true, CULL, false, Stack, false, false, NODE_EXACT, true>(S, o, d, t, st, C, false, nullptr,
-                                                                                nullptr, b) >= 0;
+      return traceRay<true, CULL, false, Stack, false, true>(S, o, d, t, st, C, false, nullptr, b) >= 0;
     }
+    return traceRay<true, CULL, false, Stack, true, true>(S, o, d, t, st, C, false, top, b) >= 0;
+  }
+
+ private:
+  // Every query: with S.fast the 4-wide runtime tree, checked against the reference's (refReachable) -- a
+  // tie (which an any-hit query ignores) or an unreachable winner retraces in the reference order,
+  // without the LDS top, which is the other tree's, the same ray counted once; else the uploaded tree.
+  // anyhit / BOUNDED are literals at every call site but traceK's.
+  template <bool BOUNDED>
+  __device__ __forceinline__ int walk(V3 o, V3 d, bool anyhit, float bound, float& t) {
     if (!COUNT && S.fast) {
-      const SceneView F = fastView(S);
-      const int pos = traceRay<true, CULL, false, Stack, (LDS_NODES > 0), false, FAST_KIND, true>(F, o, d, t, st, C,
-                                                                                                  false, top, nullptr, b);
-      if (pos < 0) return false;
-      if (refReachable(S, S.fastTri[pos], o, d, t)) return true;
-      C.rays--;
-      return traceRay<true, CULL, false, Stack, false, false, NODE_EXACT, true>(S, o, d, t, st, C, false, nullptr,
-                                                                                nullptr, b) >= 0;
+      bool tie = false;
+      int tri = traceRay4<CULL, Stack, true, BOUNDED>(S, o, d, t, st, C, anyhit, top, &tie, bound);
+      if ((tie && !anyhit) || (tri >= 0 && !refReachable(S, tri, o, d, t))) {
+        C.rays--;
+        // (any hit chosen per lane, anyRT: a literal anyhit folds it to the ANYHIT instantiation)
+        tri = traceRay<false, CULL, false, Stack, false, BOUNDED>(S, o, d, t, st, C, anyhit, nullptr, bound);
+      }
+      return tri;
     }
-    return traceRay<true, CULL, false, Stack, (LDS_NODES > 0), false, NODE_EXACT, true>(S, o, d, t, st, C, false, top,
-                                                                                        nullptr, b) >= 0;
+    // COUNT reproduces the reference's closest-hit shadow query fetch by fetch
+    if (anyhit) {  // (the sign alone is an any-hit query's result; t stays the caller's)
+      float ta;
+      return traceRay<!COUNT, CULL, COUNT, Stack, true, BOUNDED>(S, o, d, ta, st, C, false, top, bound) >= 0 ? 0 : -1;
+    }
+    return traceRay<false, CULL, COUNT, Stack, true, BOUNDED>(S, o, d, t, st, C, false, top, bound);
   }
 };
 

@@ -19,7 +19,8 @@ import oracle
 import parity
 import query_ref as qr
 import refit_ref as rr
-from opengl_ray_tracing_amd import (FLAG_COUNT_FETCHES, FLAG_HOST_ACCEL, FLAG_NO_CULL, FLAG_REFERENCE_TREE, Renderer)
+from opengl_ray_tracing_amd import (FLAG_COUNT_FETCHES, FLAG_HOST_ACCEL, FLAG_MEGAKERNEL, FLAG_NO_BINS, FLAG_NO_CULL,
+                                    FLAG_REFERENCE_TREE, Renderer)
 from post_common import INVALID, NOSCENE, bits, rc_of
 
 pytestmark = pytest.mark.gpu
@@ -188,6 +189,19 @@ def test_the_chain_renders_and_overflows_the_on_chip_stack():
                 rays, t_o, tri_o = query_rays("chain", k)
                 t, tri = r.trace_closest(rays)
                 assert np.array_equal(tri, tri_o) and np.array_equal(bits(t[tri_o >= 0]), bits(t_o[tri_o >= 0]))
+
+
+@pytest.mark.parametrize("flags", [0, FLAG_REFERENCE_TREE], ids=["runtime-tree", "uploaded-tree"])
+def test_the_chain_traces_its_camera_rays_one_by_one(flags):
+    """The chain is deeper than the camera-ray packets' stack (300 levels against 128), so without camera-ray
+    bins the megakernel traces every camera ray on its own (primaryPacket's Tracer::trace): through the
+    4-wide runtime tree, checked and retraced, and through the uploaded tree."""
+    eye, rot = rr.scene_arrays("chain")[4:6]
+    want = rr.oracle_frames("chain", 1, "mis", 2, 2)[0]
+    with renderer("chain", "mis", 2, 1, flags | FLAG_NO_BINS | FLAG_MEGAKERNEL) as r:
+        for f in range(2):
+            assert_image(r.render_frame(eye, rot, f, download=True), want[f], f"chain, camera rays one by one, frame {f}")
+        assert r.stats().runtime_tree == (0 if flags else 1)
 
 
 # ------------------------------------------------------------------ 4. a sequence on one context
