@@ -46,6 +46,7 @@ _DEV = [CSRC / "pt_device.h", CSRC / "pt_kernels.h", INCLUDE / "pt_fmath.h"]
 _FRAME = [*_DEV, CSRC / "pt_frame.h", CSRC / "pt_trace.h"]  # pt_frame.h's device half includes pt_trace.h
 _HOST = [CSRC / "pt_runtime.h", CSRC / "pt_frame.h", CSRC / "pt_kernels.h", INCLUDE / "pt_abi.h", CSRC / "pt_rccl.h",
          CSRC / "pt_envupdate.h"]
+_UPDATE = [CSRC / "pt_update.h"]  # what the in-place updates share (pt_scene_upload.cpp, pt_env.cpp)
 _PREP = [CSRC / "pt_scene_prep.h", CSRC / "pt_kernels.h"]  # the host-only scene preparation (no context, no HIP call)
 
 SOURCES = {
@@ -71,8 +72,8 @@ SOURCES = {
     # -ffp-contract=off like the rest: its unit normal and plane offset round as the reference's do
     "pt_context.o": ("cxx", CSRC / "pt_context.cpp", [*_HOST, CSRC / "pt_plan.h", INCLUDE / "pt_fmath.h"]),
     "pt_scene_prep.o": ("cxx", CSRC / "pt_scene_prep.cpp", [*_PREP, CSRC / "pt_accel.h"]),
-    "pt_scene_upload.o": ("cxx", CSRC / "pt_scene_upload.cpp", [*_HOST, *_PREP, CSRC / "pt_plan.h"]),
-    "pt_env.o": ("cxx", CSRC / "pt_env.cpp", [*_HOST, INCLUDE / "pt_scene.h"]),
+    "pt_scene_upload.o": ("cxx", CSRC / "pt_scene_upload.cpp", [*_HOST, *_PREP, *_UPDATE, CSRC / "pt_plan.h"]),
+    "pt_env.o": ("cxx", CSRC / "pt_env.cpp", [*_HOST, *_UPDATE, INCLUDE / "pt_scene.h"]),
     "pt_runtime.o": ("cxx", CSRC / "pt_runtime.cpp", [*_HOST, CSRC / "pt_plan.h"]),  # the frame path
     "pt_queries.o": ("cxx", CSRC / "pt_queries.cpp", _HOST),
     "pt_accum.o": ("cxx", CSRC / "pt_accum.cpp", [*_HOST, CSRC / "pt_plan.h"]),
@@ -179,6 +180,20 @@ def build_plan_table(force: bool = False) -> Path:
     return PLAN_TABLE
 
 
+ENV_FORMS_TABLE_SRC = ROOT / "tests" / "native" / "env_forms_table.cpp"
+ENV_FORMS_TABLE = ROOT / "tests" / "native" / "env_forms_table"
+
+
+def build_env_forms_table(force: bool = False) -> Path:
+    """Test infrastructure: the view of the environment's store the kernels get (csrc/pt_envupdate.h envForms)
+    for stores filled by hand (tests/native/env_forms_table.cpp), host-only like plan_table."""
+    deps = [ENV_FORMS_TABLE_SRC, CSRC / "pt_envupdate.h", CSRC / "pt_kernels.h"]
+    if force or _stale(ENV_FORMS_TABLE, deps):
+        _run(["g++", "-std=c++17", "-O1", "-Wall", "-Wno-unused-function", "-D__HIP_PLATFORM_AMD__", f"-I{ROCM}/include",
+              f"-I{INCLUDE}", f"-I{CSRC}", str(ENV_FORMS_TABLE_SRC), "-o", str(ENV_FORMS_TABLE)])
+    return ENV_FORMS_TABLE
+
+
 SHARE_TABLE_SRC = ROOT / "tests" / "native" / "share_table.cpp"
 SHARE_TABLE = ROOT / "tests" / "native" / "share_table"
 
@@ -257,6 +272,7 @@ if __name__ == "__main__":
     build_abi_caller(force="--force" in sys.argv)
     build_plan_table(force="--force" in sys.argv)
     build_share_table(force="--force" in sys.argv)
+    build_env_forms_table(force="--force" in sys.argv)
     build_scene_prep_check(force="--force" in sys.argv)
     build_material_table_check(force="--force" in sys.argv)
     build_env_quantise_check(force="--force" in sys.argv)

@@ -228,10 +228,8 @@ void pt_destroy(pt_ctx* ctx) {
   dfree(ctx->d_refParent); dfree(ctx->d_refBox); dfree(ctx->d_leafBox);
   freeRefit(ctx);
   freeMaterialTables(ctx);
-  releaseEnvStore(ctx);  // pt_update_env's buffers, which the env pointers are then views of
-  dfree(ctx->d_hdr); dfree(ctx->d_cache); dfree(ctx->d_hdr8); dfree(ctx->d_cache4); dfree(ctx->d_shapes);
-  dfree(ctx->d_cacheRow); dfree(ctx->d_cacheY); dfree(ctx->d_trig); dfree(ctx->d_light);
-  dfree(ctx->d_basicImg); dfree(ctx->d_stream); dfree(ctx->d_offsets); dfree(ctx->d_overruns);
+  releaseEnv(ctx);
+  dfree(ctx->d_shapes); dfree(ctx->d_basicImg); dfree(ctx->d_stream); dfree(ctx->d_offsets); dfree(ctx->d_overruns);
   dfree(ctx->d_accum); dfree(ctx->d_ctl); dfree(ctx->d_ovf); dfree(ctx->d_cost); dfree(ctx->d_order);
   dfree(ctx->d_rgb);
   dfree(ctx->d_guide[2]);
@@ -294,7 +292,7 @@ static int statsOne(pt_ctx* ctx, pt_frame_stats* st) {
   st->launches = ctx->launches;
   st->frames = ctx->frames;
   st->frame_batch = ctx->batchCap;
-  st->env_compact = ctx->d_hdr8 ? (ctx->d_cacheRow ? 2 : 1) : 0;
+  st->env_compact = compactLevel(ctx->env);
   st->tree4_nodes = ctx->fast4Ready ? ctx->f4nDev : 0;
   st->max_stack = ctx->maxStack;
   st->split_items = 0;

@@ -389,7 +389,7 @@ __device__ __forceinline__ void hdrColorPdfOf(const Env& e, float4 c, float w, V
 // by value: an Env or an output passed by reference would live in scratch memory.)
 __device__ __noinline__ float4 hdrColorPdfCall(const uint2* hdr8, const float4* hdr, int w, int h, int res, int nt,
                                               V3 L) {
-  Env e;
+  Env e{};
   e.hdr8 = hdr8;
   e.hdr = hdr;
   e.w = w;

@@ -13,6 +13,7 @@
 #include "pt_kernels.h"
 #include "pt_runtime.h"
 #include "pt_scene.h"
+#include "pt_update.h"
 
 using namespace pt;
 
@@ -35,146 +36,158 @@ static int deviceHdrCache(pt_ctx* ctx, const float* hdr, int w, int h, float4* o
   return PT_OK;
 }
 
-static int envOne(pt_ctx* ctx, const float* hdr, int w, int h, const float* cache) {
-  if (!ctx) return PT_E_INVALID;
-  if (int rc = syncStreams(ctx)) return rc;
-  CK(hipSetDevice(ctx->cfg.device_id));
-  releaseEnvStore(ctx);  // an env pt_update_env made: its buffers go, and the pointers below are null
-  dfree(ctx->d_hdr);
-  dfree(ctx->d_cache);
-  dfree(ctx->d_hdr8);
-  dfree(ctx->d_cache4);
-  dfree(ctx->d_cacheRow);
-  dfree(ctx->d_cacheY);
-  dfree(ctx->d_trig);
-  dfree(ctx->d_light);
-  ctx->hdrW = ctx->hdrH = 0;
-  if (!hdr) return PT_OK;
-  if (w <= 0 || h <= 0) return PT_E_INVALID;
+// ------------------------------------------------------------ the environment's buffers (pt_envupdate.h EnvStore)
+static void freeStore(EnvStore& s) {
+  dfree(s.hdr); dfree(s.cache); dfree(s.hdr8); dfree(s.cache4); dfree(s.cacheRow); dfree(s.cacheY); dfree(s.rowTmp);
+  dfree(s.trig); dfree(s.light); dfree(s.flags); dfree(s.full); dfree(s.scratch); dfree(s.quant); dfree(s.stageHdr);
+  dfree(s.stageCache);
+  s = EnvStore{};
+}
+
+// the one place the context's view changes: the forms, and their size where the launch policy reads it
+static void setEnvForms(pt_ctx* ctx, const EnvForms& v) {
+  ctx->env = v;
+  ctx->hdrW = v.w;
+  ctx->hdrH = v.h;
+}
+
+void releaseEnv(pt_ctx* ctx) {
+  freeStore(ctx->envStore);
+  setEnvForms(ctx, EnvForms{});
+}
+
+template <class T>
+static bool tryAlloc(T** p, size_t count) {  // an optional table: false, and no error left behind, when it does not fit
+  if (hipMalloc(p, count * sizeof(T)) == hipSuccess) return true;
+  *p = nullptr;
+  (void)hipGetLastError();
+  return false;
+}
+
+// The compact texels (8 + 4 bytes instead of 16 + 8 per texel; pt_kernels.h Env) are kept when every
+// texel decodes back to its float bits: a Radiance map's RGBE values and calculateHdrCache's table
+// always do. c4's MIS light samples read the sample table at uniformly random (xi1, xi2): half the
+// bytes per texel, twice the texels per cached line. PT_ENV_COMPACT=0 (environment): the float texels.
+static bool compactWanted(int w, int h) {
+  const char* e = std::getenv("PT_ENV_COMPACT");
+  return (!e || std::atoi(e) != 0) && w <= 65535 && h <= 65535;
+}
+
+// what launchEnvLight reads of an Env: the texels in both forms, Env::trig and the size
+static Env lightEnv(const EnvStore& s) {
+  Env e{};
+  e.hdr = s.hdr;
+  e.hdr8 = s.hdr8;
+  e.trig = s.trig;
+  e.w = e.res = s.w;
+  e.h = s.h;
+  return e;
+}
+
+// ------------------------------------------------------------ pt_upload_env
+// The forms that serve a map from host memory, built into s and into nothing else: the float texels and
+// table, and -- each only where it is exact, and where its optional buffers fit -- the compact forms,
+// trig and light, and the table by rows. The caller frees s on a failure.
+static int buildUpload(pt_ctx* ctx, const float* hdr, int w, int h, const float* cache, EnvStore& s) {
   const size_t n = (size_t)w * h;
+  s.w = w;
+  s.h = h;
   // render layout (pt_kernels.h Env): (r, g, b, pdf) texels + (x, y) sample table
   std::vector<float4> a(n);
   for (size_t k = 0; k < n; k++)
     a[k] = make_float4(hdr[3 * k], hdr[3 * k + 1], hdr[3 * k + 2], cache ? cache[3 * k + 2] : 0.0f);
-  CK(hipMalloc(&ctx->d_hdr, n * sizeof(float4)));
-  CK(hipMalloc(&ctx->d_cache, n * sizeof(float2)));
-  CK(hipMemcpy(ctx->d_hdr, a.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+  CK(hipMalloc(&s.hdr, n * sizeof(float4)));
+  CK(hipMalloc(&s.cache, n * sizeof(float2)));
+  CK(hipMemcpy(s.hdr, a.data(), n * sizeof(float4), hipMemcpyHostToDevice));
   if (cache) {
     std::vector<float2> b(n);
     for (size_t k = 0; k < n; k++) b[k] = make_float2(cache[3 * k], cache[3 * k + 1]);
-    CK(hipMemcpy(ctx->d_cache, b.data(), n * sizeof(float2), hipMemcpyHostToDevice));
+    CK(hipMemcpy(s.cache, b.data(), n * sizeof(float2), hipMemcpyHostToDevice));
   } else {
     float4* full = nullptr;  // calculateHdrCache on the GPU, then packed into the render layout
     CK(hipMalloc(&full, n * sizeof(float4)));
     int rc = deviceHdrCache(ctx, hdr, w, h, full);
     if (!rc) {
-      hipError_t e = launchEnvPack(ctx->d_hdr, full, ctx->d_cache, (int)n, ctx->stream);
+      hipError_t e = launchEnvPack(s.hdr, full, s.cache, (int)n, ctx->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
       if (e != hipSuccess) rc = fail(ctx, PT_E_HIP, std::string("env pack: ") + hipGetErrorString(e));
     }
     (void)hipFree(full);
     if (rc) return rc;
   }
-  // The compact texels (8 + 4 bytes instead of 16 + 8 per texel; pt_kernels.h Env), kept when every
-  // texel decodes back to its float bits: a Radiance map's RGBE values and calculateHdrCache's
-  // table always do. c4's MIS light samples read the sample table at uniformly random (xi1, xi2):
-  // half the bytes per texel, twice the texels per cached line. PT_ENV_COMPACT=0: the float texels.
-  static const bool compact = [] {
-    const char* e = std::getenv("PT_ENV_COMPACT");
-    return !e || std::atoi(e) != 0;
-  }();
-  // (built into locals and handed to the context only once verified: a failure part-way leaves the
-  // float texels serving, never a half-built compact form)
-  if (compact && w <= 65535 && h <= 65535) {
-    uint2* hdr8 = nullptr;
-    uint32_t* cache4 = nullptr;
-    int* d_bad = nullptr;
-    hipError_t e = hipMalloc(&hdr8, n * sizeof(uint2));
-    if (e == hipSuccess) e = hipMalloc(&cache4, n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&d_bad, sizeof(int));
-    if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream);
-    if (e == hipSuccess) e = launchEnvCompact(ctx->d_hdr, ctx->d_cache, w, h, hdr8, cache4, d_bad, ctx->stream);
-    int bad = 1;
+  int* d_bad = nullptr;
+  int bad = 1;
+  if (compactWanted(w, h) && tryAlloc(&s.hdr8, n) && tryAlloc(&s.cache4, n) && tryAlloc(&d_bad, 1)) {
+    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(int), ctx->stream);
+    if (e == hipSuccess) e = launchEnvCompact(s.hdr, s.cache, w, h, s.hdr8, s.cache4, d_bad, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     dfree(d_bad);
-    if (e != hipSuccess || bad) {  // not exact (or failed): the float texels serve
-      dfree(hdr8);
-      dfree(cache4);
-      if (e != hipSuccess) return fail(ctx, PT_E_HIP, std::string("env compact: ") + hipGetErrorString(e));
-    } else {
-      ctx->d_hdr8 = hdr8;
-      ctx->d_cache4 = cache4;
-    }
+    if (e != hipSuccess) return fail(ctx, PT_E_HIP, std::string("env compact: ") + hipGetErrorString(e));
   }
-  if (ctx->d_cache4) {  // SampleHdr's sines and cosines of the compact table's integers (Env::trig)
-    float2* trig = nullptr;
-    hipError_t e2 = hipMalloc(&trig, (size_t)(w + h + 2) * sizeof(float2));
-    if (e2 == hipSuccess) e2 = launchEnvTrig(trig, w, h, ctx->stream);
-    if (e2 == hipSuccess) e2 = hipStreamSynchronize(ctx->stream);
-    if (e2 != hipSuccess) {
-      dfree(trig);
-      return fail(ctx, PT_E_HIP, std::string("env trig: ") + hipGetErrorString(e2));
-    }
-    ctx->d_trig = trig;
+  if (bad) {  // not exact, not wanted or no room: the float texels serve, and nothing below applies
+    dfree(s.hdr8);
+    dfree(s.cache4);
+    return PT_OK;
+  }
+  // SampleHdr's sines and cosines of the compact table's integers (Env::trig) ...
+  if (tryAlloc(&s.trig, (size_t)(w + h + 2))) {
+    hipError_t e = launchEnvTrig(s.trig, w, h, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(ctx, PT_E_HIP, std::string("env trig: ") + hipGetErrorString(e));
+    s.trigReady = true;
     // ... and every entry's light-sample color and pdf (Env::light)
-    Env e;
-    std::memset(&e, 0, sizeof(e));
-    e.hdr = ctx->d_hdr;
-    e.hdr8 = ctx->d_hdr8;
-    e.trig = ctx->d_trig;
-    e.w = e.res = w;
-    e.h = h;
-    uint2* light = nullptr;
-    e2 = hipMalloc(&light, (size_t)(w + 1) * (h + 1) * sizeof(uint2));
-    if (e2 == hipSuccess) e2 = launchEnvLight(e, light, ctx->stream);
-    if (e2 == hipSuccess) e2 = hipStreamSynchronize(ctx->stream);
-    if (e2 != hipSuccess) {
-      dfree(light);
-      return fail(ctx, PT_E_HIP, std::string("env light: ") + hipGetErrorString(e2));
-    }
-    ctx->d_light = light;
-  }
-  if (ctx->d_cache4) {
-    // the sample table by rows (pt_kernels.h Env::cacheRow), kept when every entry of every row equals
-    // its row form: each row's x is one value, and the rows of one x hold the same y's
-    std::vector<uint32_t> c4(n);
-    CK(hipMemcpy(c4.data(), ctx->d_cache4, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    std::vector<uint32_t> rows(h);
-    std::vector<unsigned short> ys;
-    std::vector<int> idOf(65536, -1);
-    bool ok = true;
-    for (int i = 0; i < h && ok; i++) {
-      const uint32_t* row = c4.data() + (size_t)i * w;
-      const uint32_t x = row[0] & 0xffffu;
-      int id = idOf[x];
-      if (id < 0) {
-        id = idOf[x] = (int)(ys.size() / (size_t)w);
-        for (int j = 0; j < w; j++) ys.push_back((unsigned short)(row[j] >> 16));
-      }
-      const unsigned short* yr = ys.data() + (size_t)id * w;
-      for (int j = 0; j < w && ok; j++) ok = (row[j] & 0xffffu) == x && (row[j] >> 16) == yr[j];
-      rows[i] = x | (uint32_t)id << 16;
-    }
-    if (ok) {  // both or neither (Env::cacheRow reads cacheY)
-      uint32_t* cr = nullptr;
-      unsigned short* cy = nullptr;
-      hipError_t e = hipMalloc(&cr, rows.size() * sizeof(uint32_t));
-      if (e == hipSuccess) e = hipMalloc(&cy, ys.size() * sizeof(unsigned short));
-      if (e == hipSuccess) e = hipMemcpy(cr, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(cy, ys.data(), ys.size() * sizeof(unsigned short), hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        dfree(cr);
-        dfree(cy);
-        return fail(ctx, PT_E_HIP, std::string("env rows: ") + hipGetErrorString(e));
-      }
-      ctx->d_cacheRow = cr;
-      ctx->d_cacheY = cy;
+    if (tryAlloc(&s.light, (size_t)(w + 1) * (h + 1))) {
+      e = launchEnvLight(lightEnv(s), s.light, ctx->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+      if (e != hipSuccess) return fail(ctx, PT_E_HIP, std::string("env light: ") + hipGetErrorString(e));
     }
   }
+  // the sample table by rows (pt_kernels.h Env::cacheRow), kept when every entry of every row equals
+  // its row form: each row's x is one value, and the rows of one x hold the same y's
+  std::vector<uint32_t> c4(n);
+  CK(hipMemcpy(c4.data(), s.cache4, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  std::vector<uint32_t> rows(h);
+  std::vector<unsigned short> ys;
+  std::vector<int> idOf(65536, -1);
+  bool ok = true;
+  for (int i = 0; i < h && ok; i++) {
+    const uint32_t* row = c4.data() + (size_t)i * w;
+    const uint32_t x = row[0] & 0xffffu;
+    int id = idOf[x];
+    if (id < 0) {
+      id = idOf[x] = (int)(ys.size() / (size_t)w);
+      for (int j = 0; j < w; j++) ys.push_back((unsigned short)(row[j] >> 16));
+    }
+    const unsigned short* yr = ys.data() + (size_t)id * w;
+    for (int j = 0; j < w && ok; j++) ok = (row[j] & 0xffffu) == x && (row[j] >> 16) == yr[j];
+    rows[i] = x | (uint32_t)id << 16;
+  }
+  if (ok && tryAlloc(&s.cacheRow, rows.size()) && tryAlloc(&s.cacheY, ys.size())) {
+    hipError_t e = hipMemcpy(s.cacheRow, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(s.cacheY, ys.data(), ys.size() * sizeof(unsigned short), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(ctx, PT_E_HIP, std::string("env rows: ") + hipGetErrorString(e));
+  }
+  if (!s.cacheY) dfree(s.cacheRow);  // both or neither (Env::cacheRow reads cacheY)
+  return PT_OK;
+}
+
+// The old environment is released first, so the peak is one environment's memory; the new one reaches the
+// context only when it is complete, and any failure leaves the context with no environment.
+static int envOne(pt_ctx* ctx, const float* hdr, int w, int h, const float* cache) {
+  if (int rc = waitForReaders(ctx)) return rc;  // of the buffers freed here
+  CK(hipSetDevice(ctx->cfg.device_id));
+  releaseEnv(ctx);
+  if (!hdr) return PT_OK;
+  if (w <= 0 || h <= 0) return PT_E_INVALID;
+  EnvStore s;
+  if (int rc = buildUpload(ctx, hdr, w, h, cache, s)) {
+    freeStore(s);
+    return rc;
+  }
+  ctx->envStore = s;
+  setEnvForms(ctx, envForms(s, true, true));  // buildUpload kept the exact forms only
   ctx->policyKey++;
-  ctx->hdrW = w;
-  ctx->hdrH = h;
   return PT_OK;
 }
 
@@ -216,36 +229,6 @@ int pt_upload_env(pt_ctx* ctx, const float* hdr, int w, int h, const float* cach
 }
 
 // ------------------------------------------------------------ environment update (pt_envupdate.hip)
-static void freeStore(EnvStore& s) {
-  dfree(s.hdr); dfree(s.cache); dfree(s.hdr8); dfree(s.cache4); dfree(s.cacheRow); dfree(s.cacheY); dfree(s.rowTmp);
-  dfree(s.trig); dfree(s.light); dfree(s.flags); dfree(s.full); dfree(s.scratch); dfree(s.quant); dfree(s.stageHdr);
-  dfree(s.stageCache);
-  s = EnvStore{};
-}
-
-void releaseEnvStore(pt_ctx* ctx) {
-  if (!ctx->envStore.w) return;
-  freeStore(ctx->envStore);
-  ctx->d_hdr = nullptr;
-  ctx->d_cache = nullptr;
-  ctx->d_hdr8 = nullptr;
-  ctx->d_cache4 = nullptr;
-  ctx->d_cacheRow = nullptr;
-  ctx->d_cacheY = nullptr;
-  ctx->d_trig = nullptr;
-  ctx->d_light = nullptr;
-}
-
-static int envCompactLevel(const pt_ctx* ctx) { return ctx->d_hdr8 ? (ctx->d_cacheRow ? 2 : 1) : 0; }  // pt_frame_stats.env_compact
-
-template <class T>
-static bool tryAlloc(T** p, size_t count) {  // an optional table: false, and no error left behind, when it does not fit
-  if (hipMalloc(p, count * sizeof(T)) == hipSuccess) return true;
-  *p = nullptr;
-  (void)hipGetLastError();
-  return false;
-}
-
 // The buffers of a w x h map, every form's: the compact forms are allocated whether or not the first map
 // is compact, so that a later one of the same size allocates nothing. The float texels, the float table
 // and the flag words are required; every other table falls back when it cannot be allocated (the compact
@@ -258,8 +241,8 @@ static int makeStore(pt_ctx* ctx, int w, int h, EnvStore& s) {
   }
   s.w = w;
   s.h = h;
-  const char* c = std::getenv("PT_ENV_COMPACT");  // as pt_upload_env: 0 keeps the float texels
-  if ((c && std::atoi(c) == 0) || w > 65535 || h > 65535) return PT_OK;
+  s.complete = true;
+  if (!compactWanted(w, h)) return PT_OK;
   if (!tryAlloc(&s.hdr8, n) || !tryAlloc(&s.cache4, n)) {
     dfree(s.hdr8);
     dfree(s.cache4);
@@ -277,14 +260,15 @@ static int makeStore(pt_ctx* ctx, int w, int h, EnvStore& s) {
 // One context's update. The map is w*h*3 floats in host memory (hdr, cache: staged here) or in the
 // context's device memory (d_hdr, d_cache), read in stream order on its stream; the caller has waited
 // for the frames and queries in flight. A map of the current store's size is written into the store's
-// buffers; any other size gets a new store, and the old environment -- the previous store, or
-// pt_upload_env's allocations -- is released only once the new one is complete.
+// buffers; any other size, and any map after a pt_upload_env (whose store is not complete), gets a new
+// store, and the old environment is released only once the new one is complete.
 static int updateEnvOne(pt_ctx* ctx, const float* hdr, const float* cache, const float* d_hdr, const float* d_cache, int w,
                         int h, uint32_t flags) {
-  CK(hipSetDevice(ctx->cfg.device_id));
+  dropHistory(ctx);  // the history and the moments saw the old light, as after an upload
+  if (int rc = dropMoments(ctx)) return rc;
   const size_t n = (size_t)w * h;
   const bool rgbe = (flags & PT_ENV_RGBE) != 0, hasTable = hdr ? cache != nullptr : d_cache != nullptr;
-  const bool fresh = ctx->envStore.w != w || ctx->envStore.h != h;
+  const bool fresh = !ctx->envStore.complete || ctx->envStore.w != w || ctx->envStore.h != h;
   EnvStore made;
   if (fresh)
     if (int rc = makeStore(ctx, w, h, made)) return rc;
@@ -300,22 +284,12 @@ static int updateEnvOne(pt_ctx* ctx, const float* hdr, const float* cache, const
     return fail(ctx, PT_E_NOMEM, "pt_update_env: table scratch or staging");
   }
   // PT_UPDATE_TIMES (environment; tools/env_time.py): the device time of each step, on stderr
-  const bool timed = std::getenv("PT_UPDATE_TIMES") != nullptr;
-  constexpr int NEV = 6;
-  struct StepEvents {  // destroyed on every way out
-    hipEvent_t ev[NEV] = {};
-    ~StepEvents() {
-      for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    }
-  } steps;
-  hipError_t e = hipSuccess;
-  if (timed)
-    for (int k = 0; k < NEV && e == hipSuccess; k++) e = hipEventCreate(&steps.ev[k]);
-  auto mark = [&](int k) {
-    if (timed && e == hipSuccess) e = hipEventRecord(steps.ev[k], ctx->stream);
-  };
+  StepEvents<6> steps;
   hipStream_t s = ctx->stream;
+  hipError_t e = steps.create("PT_UPDATE_TIMES");
+  auto mark = [&](int k) {
+    if (e == hipSuccess) e = steps.mark(k, s);
+  };
   if (e == hipSuccess && hdr) {
     e = hipMemcpyAsync(st.stageHdr, hdr, 3 * n * sizeof(float), hipMemcpyHostToDevice, s);
     if (e == hipSuccess && cache) e = hipMemcpyAsync(st.stageCache, cache, 3 * n * sizeof(float), hipMemcpyHostToDevice, s);
@@ -340,16 +314,7 @@ static int updateEnvOne(pt_ctx* ctx, const float* hdr, const float* cache, const
     e = launchEnvTrig(st.trig, w, h, s);
     st.trigReady = e == hipSuccess;
   }
-  if (e == hipSuccess && st.hdr8 && st.trig && st.light) {
-    Env v;
-    std::memset(&v, 0, sizeof(v));
-    v.hdr = st.hdr;
-    v.hdr8 = st.hdr8;
-    v.trig = st.trig;
-    v.w = v.res = w;
-    v.h = h;
-    e = launchEnvLight(v, st.light, s);
-  }
+  if (e == hipSuccess && st.hdr8 && st.trig && st.light) e = launchEnvLight(lightEnv(st), st.light, s);
   mark(4);
   if (e == hipSuccess && st.hdr8 && st.cacheRow) e = launchEnvRows(st, s);
   mark(5);
@@ -360,33 +325,20 @@ static int updateEnvOne(pt_ctx* ctx, const float* hdr, const float* cache, const
     if (fresh) freeStore(made);
     return fail(ctx, PT_E_HIP, std::string("pt_update_env: ") + hipGetErrorString(e));
   }
-  // the hand-over: the Env the kernels get, chosen from the three ints
-  const int wasW = ctx->hdrW, wasH = ctx->hdrH, wasCompact = envCompactLevel(ctx);
+  // the hand-over: the forms the kernels get, chosen from the three ints
+  const EnvForms was = ctx->env;
   if (fresh) {
-    releaseEnvStore(ctx);
-    dfree(ctx->d_hdr); dfree(ctx->d_cache); dfree(ctx->d_hdr8); dfree(ctx->d_cache4);
-    dfree(ctx->d_cacheRow); dfree(ctx->d_cacheY); dfree(ctx->d_trig); dfree(ctx->d_light);
+    freeStore(ctx->envStore);
     ctx->envStore = made;
   }
-  const EnvStore& k = ctx->envStore;
-  const bool compact = k.hdr8 && !f[ENV_BAD], rows = compact && k.cacheRow && !f[ENV_ROWS_BAD];
-  ctx->d_hdr = k.hdr;
-  ctx->d_cache = k.cache;
-  ctx->d_hdr8 = compact ? k.hdr8 : nullptr;
-  ctx->d_cache4 = compact ? k.cache4 : nullptr;
-  ctx->d_trig = compact ? k.trig : nullptr;
-  ctx->d_light = compact && k.trig ? k.light : nullptr;
-  ctx->d_cacheRow = rows ? k.cacheRow : nullptr;
-  ctx->d_cacheY = rows ? k.cacheY : nullptr;
-  ctx->hdrW = w;
-  ctx->hdrH = h;
+  setEnvForms(ctx, envForms(ctx->envStore, !f[ENV_BAD], !f[ENV_ROWS_BAD]));
   // the measured launch policies were measured for a map of this size in this form: they stay while both do
-  if (wasW != w || wasH != h || wasCompact != envCompactLevel(ctx)) ctx->policyKey++;
-  if (timed) {
-    float ms[NEV - 1] = {};
-    for (int j = 0; j + 1 < NEV; j++) CK(hipEventElapsedTime(&ms[j], steps.ev[j], steps.ev[j + 1]));
+  if (was.w != w || was.h != h || compactLevel(was) != compactLevel(ctx->env)) ctx->policyKey++;
+  if (steps.on) {
+    float ms[5] = {};
+    CK(steps.elapsed(ms));
     std::fprintf(stderr, "pt_update_env: texels %.4f table %.4f compact %.4f light %.4f rows %.4f ms, env_compact %d, %d rows\n",
-                 ms[0], ms[1], ms[2], ms[3], ms[4], envCompactLevel(ctx), rows ? f[ENV_ROW_IDS] : 0);
+                 ms[0], ms[1], ms[2], ms[3], ms[4], compactLevel(ctx->env), ctx->env.cacheRow ? f[ENV_ROW_IDS] : 0);
   }
   return PT_OK;
 }
@@ -404,53 +356,39 @@ static int envUpdateArgs(pt_ctx* ctx, const void* hdr, int w, int h, uint32_t fl
   return PT_OK;
 }
 
-static int envWait(pt_ctx* ctx) {
-  if (int rc = syncStreams(ctx)) return rc;  // no frame in flight reads the buffers rewritten here
-  if (ctx->queryIssued) CK(hipEventSynchronize(ctx->queryDone));  // nor a ray query, whichever stream it is on
-  return PT_OK;
-}
-
 int pt_update_env(pt_ctx* ctx, const float* hdr, int w, int h, const float* cache, uint32_t flags) {
   if (int rc = envUpdateArgs(ctx, hdr, w, h, flags)) return rc;
   if (!hdr) return pt_upload_env(ctx, nullptr, 0, 0, nullptr);
-  for (pt_ctx* m : members(ctx)) {
-    if (int rc = envWait(m)) return fromPeer(ctx, m, rc);
-    dropHistory(m);
-    if (int rc = dropMoments(m)) return fromPeer(ctx, m, rc);
-    if (int rc = updateEnvOne(m, hdr, cache, nullptr, nullptr, w, h, flags)) return fromPeer(ctx, m, rc);
-  }
-  return PT_OK;
+  return updateMembers(ctx, nullptr, [&](pt_ctx* m) { return updateEnvOne(m, hdr, cache, nullptr, nullptr, w, h, flags); });
 }
 
 int pt_update_env_device(pt_ctx* ctx, const void* d_hdr, int w, int h, const void* d_cache, uint32_t flags) {
   if (int rc = envUpdateArgs(ctx, d_hdr, w, h, flags)) return rc;
-  if (!ctx->peers.empty()) return fail(ctx, PT_E_INVALID, "pt_update_env_device: not on an n_devices > 1 context");
-  if (!d_hdr) return pt_upload_env(ctx, nullptr, 0, 0, nullptr);
-  if (int rc = envWait(ctx)) return rc;
-  dropHistory(ctx);
-  if (int rc = dropMoments(ctx)) return rc;
-  return updateEnvOne(ctx, nullptr, nullptr, static_cast<const float*>(d_hdr), static_cast<const float*>(d_cache), w, h, flags);
+  if (!d_hdr && ctx->peers.empty()) return pt_upload_env(ctx, nullptr, 0, 0, nullptr);
+  return updateAlone(ctx, "pt_update_env_device", nullptr, [&](pt_ctx* m) {
+    return updateEnvOne(m, nullptr, nullptr, static_cast<const float*>(d_hdr), static_cast<const float*>(d_cache), w, h, flags);
+  });
 }
 
 int pt_env_size(pt_ctx* ctx, int* w, int* h) {
   if (!ctx || !w || !h) return PT_E_INVALID;
-  *w = ctx->d_hdr ? ctx->hdrW : 0;
-  *h = ctx->d_hdr ? ctx->hdrH : 0;
+  *w = ctx->env.w;
+  *h = ctx->env.h;
   return PT_OK;
 }
 
 int pt_download_env(pt_ctx* ctx, int form, float* texels, float* table) {
   if (!ctx || (!texels && !table)) return PT_E_INVALID;
   if (form < 0 || form > 2) return fail(ctx, PT_E_INVALID, "pt_download_env: form must be 0, 1 or 2");
-  if (!ctx->d_hdr) return fail(ctx, PT_E_INVALID, "pt_download_env: no environment");
-  if (form > envCompactLevel(ctx)) return fail(ctx, PT_E_INVALID, "pt_download_env: the environment is not kept in that form");
+  if (!ctx->env.hdr) return fail(ctx, PT_E_INVALID, "pt_download_env: no environment");
+  if (form > compactLevel(ctx->env)) return fail(ctx, PT_E_INVALID, "pt_download_env: the environment is not kept in that form");
   if (form == 2 && texels) return fail(ctx, PT_E_INVALID, "pt_download_env: the row form holds no texels");
   if (int rc = syncStreams(ctx)) return rc;
   CK(hipSetDevice(ctx->cfg.device_id));
-  const size_t n = (size_t)ctx->hdrW * ctx->hdrH;
+  const size_t n = (size_t)ctx->env.w * ctx->env.h;
   if (form == 0) {
-    if (texels) CK(hipMemcpy(texels, ctx->d_hdr, n * sizeof(float4), hipMemcpyDeviceToHost));
-    if (table) CK(hipMemcpy(table, ctx->d_cache, n * sizeof(float2), hipMemcpyDeviceToHost));
+    if (texels) CK(hipMemcpy(texels, ctx->env.hdr, n * sizeof(float4), hipMemcpyDeviceToHost));
+    if (table) CK(hipMemcpy(table, ctx->env.cache, n * sizeof(float2), hipMemcpyDeviceToHost));
     return PT_OK;
   }
   float4* t4 = nullptr;

@@ -9,10 +9,13 @@
 
 namespace pt {
 
-// What pt_update_env keeps on the device for maps of one size. The context's env pointers (pt_runtime.h
-// d_hdr .. d_light) are views of these buffers, or null where a form does not serve the current map.
+// The environment's device buffers, whichever call made them: the store owns them all (pt_env.cpp freeStore
+// is the one place they are freed) and the context's EnvForms is a view of it. Two states beside empty:
+// pt_update_env's store is complete -- every form allocated, so a later map of the same size allocates
+// nothing --, pt_upload_env's holds only the forms that serve its map.
 struct EnvStore {
-  int w = 0, h = 0;                 // 0: no store (the env, if any, is pt_upload_env's own)
+  int w = 0, h = 0;                 // 0: no environment
+  bool complete = false;            // every form allocated (makeStore's; an upload's store is not)
   float4* hdr = nullptr;            // w*h (r, g, b, pdf)
   float2* cache = nullptr;          // w*h (x, y)
   uint2* hdr8 = nullptr;            // the compact forms: both or neither (w, h <= 65535)
@@ -31,6 +34,41 @@ struct EnvStore {
   float* stageHdr = nullptr;        // the host form's staging: w*h*3 texels
   float* stageCache = nullptr;      // ... and w*h*3 table entries
 };
+
+// The forms that serve the current map: what envView copies from. Null where a form does not serve.
+struct EnvForms {
+  float4* hdr = nullptr;
+  float2* cache = nullptr;            // sample table (x, y); the pdf lives in hdr[k].w
+  uint2* hdr8 = nullptr;              // the same texels compacted (pt_kernels.h Env), null = not exact
+  uint32_t* cache4 = nullptr;
+  uint32_t* cacheRow = nullptr;       // the sample table by rows (Env::cacheRow)
+  unsigned short* cacheY = nullptr;
+  float2* trig = nullptr;             // SampleHdr's sines and cosines (Env::trig)
+  uint2* light = nullptr;             // each sample-table entry's light-sample color and pdf (Env::light)
+  int w = 0, h = 0;
+};
+
+// The hand-over, the one place a view is made: the forms of store k that serve its map, given what was read
+// back about it -- the compact forms decode to the float bits (compactExact), every entry equals its row
+// form (rowsExact). The empty store gives the empty view.
+inline EnvForms envForms(const EnvStore& k, bool compactExact, bool rowsExact) {
+  EnvForms v;
+  if (!k.hdr) return v;
+  const bool compact = k.hdr8 && compactExact, rows = compact && k.cacheRow && rowsExact;
+  v.hdr = k.hdr;
+  v.cache = k.cache;
+  v.hdr8 = compact ? k.hdr8 : nullptr;
+  v.cache4 = compact ? k.cache4 : nullptr;
+  v.trig = compact ? k.trig : nullptr;
+  v.light = compact && k.trig ? k.light : nullptr;
+  v.cacheRow = rows ? k.cacheRow : nullptr;
+  v.cacheY = rows ? k.cacheY : nullptr;
+  v.w = k.w;
+  v.h = k.h;
+  return v;
+}
+
+inline int compactLevel(const EnvForms& v) { return v.hdr8 ? (v.cacheRow ? 2 : 1) : 0; }  // pt_frame_stats.env_compact
 
 constexpr int ENV_FLAGS = 4;        // flags[]: texels or table not compact, rows not in row form, distinct rows
 constexpr int ENV_BAD = 0, ENV_ROWS_BAD = 1, ENV_ROW_IDS = 2;

@@ -141,18 +141,19 @@ SceneView sceneView(const pt_ctx* ctx) {
 
 // the uploaded environment as the kernels read it (rowTable: the sample table by rows, nt: Env::nt -- pt_plan.h)
 Env envView(const pt_ctx* ctx, bool rowTable, int nt) {
+  const EnvForms& v = ctx->env;
   Env e;
-  e.hdr = ctx->d_hdr;
-  e.cache = ctx->d_cache;
-  e.hdr8 = ctx->d_hdr8;
-  e.cache4 = ctx->d_cache4;
-  e.cacheRow = rowTable ? ctx->d_cacheRow : nullptr;
-  e.cacheY = rowTable ? ctx->d_cacheY : nullptr;
-  e.trig = ctx->d_trig;
-  e.light = ctx->d_light;  // every scene: c5 too (4.25 vs 4.49 ms without the table, round 6)
-  e.w = ctx->hdrW;
-  e.h = ctx->hdrH;
-  e.res = ctx->hdrW;
+  e.hdr = v.hdr;
+  e.cache = v.cache;
+  e.hdr8 = v.hdr8;
+  e.cache4 = v.cache4;
+  e.cacheRow = rowTable ? v.cacheRow : nullptr;
+  e.cacheY = rowTable ? v.cacheY : nullptr;
+  e.trig = v.trig;
+  e.light = v.light;  // every scene: c5 too (4.25 vs 4.49 ms without the table, round 6)
+  e.w = v.w;
+  e.h = v.h;
+  e.res = v.w;
   e.nt = nt;
   return e;
 }

@@ -1,11 +1,14 @@
 // pt_runtime.h -- what the host files of the C-ABI share: the context, the error helpers, and the
 // functions one file defines and another calls. The files, by subject: pt_context.cpp (context life,
 // streams, stats), pt_scene_upload.cpp (scene upload, geometry and material updates), pt_env.cpp
-// (environment, BASIC state), pt_runtime.cpp (the frame path), pt_queries.cpp (ray and radiance queries), pt_accum.cpp (accumulation
-// access, adaptive sampling, pack and unpack), pt_group.cpp (the in-process device group) and
-// pt_post.cpp (the display post-processing). Internal: not installed.
+// (environment upload and update, BASIC state), pt_runtime.cpp (the frame path), pt_queries.cpp (ray
+// and radiance queries), pt_accum.cpp (accumulation access, adaptive sampling, pack and unpack),
+// pt_group.cpp (the in-process device group) and pt_post.cpp (the display post-processing).
+// Internal: not installed.
 // (The launch policy of the frame path -- pure functions of this context -- is pt_plan.h; the
-// host-only scene preparation, which does not know the context, is pt_scene_prep.h.)
+// host-only scene preparation, which does not know the context, is pt_scene_prep.h; what the in-place
+// updates of pt_scene_upload.cpp and pt_env.cpp share is pt_update.h; the environment's buffers and the
+// view of them the kernels get are pt_envupdate.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -117,20 +120,12 @@ struct pt_ctx {
   float* d_updMats = nullptr;   // nTri x 18 f32
   int nTri = 0, nNodes = 0, depth = 0, maxStack = 0;
   size_t sceneBytes = 0;  // the scene's records on the device (pt_plan.h sceneBytes, largeScene)
-  // env
-  float4* d_hdr = nullptr;
-  float2* d_cache = nullptr;  // sample table (x, y); the pdf lives in d_hdr[k].w
-  uint2* d_hdr8 = nullptr;    // the same texels compacted (pt_kernels.h Env), null = not exact
-  uint32_t* d_cache4 = nullptr;
-  uint32_t* d_cacheRow = nullptr;           // the sample table by rows (pt_kernels.h Env::cacheRow)
-  unsigned short* d_cacheY = nullptr;
-  float2* d_trig = nullptr;                  // SampleHdr's sines and cosines (Env::trig)
-  uint2* d_light = nullptr;                  // each sample-table entry's light-sample color and pdf (Env::light)
-  int hdrW = 0, hdrH = 0;
-  // pt_update_env: the buffers it keeps for maps of the current size (pt_envupdate.h). While envStore.w != 0
-  // it owns every env buffer and the pointers above are views of it (null where a form does not serve the
-  // current map); otherwise they are pt_upload_env's own allocations. releaseEnvStore ends the first state.
+  // env (pt_envupdate.h): the store owns every env buffer, pt_upload_env's and pt_update_env's alike; env is
+  // the view of it the kernels get (envView), made by envForms and installed by setEnvForms alone, its size
+  // also in hdrW / hdrH for the launch policy (pt_plan.h rowTable). releaseEnv empties all of it.
   EnvStore envStore;
+  EnvForms env;
+  int hdrW = 0, hdrH = 0;  // env.w, env.h
   // BASIC shapes, the double image, the replayed random stream
   double* d_shapes = nullptr;
   int nShapes = 0;
@@ -358,7 +353,7 @@ void dropHistory(pt_ctx* ctx);  // the temporal history shows another scene or a
 void freeRefit(pt_ctx* ctx);    // pt_update_geometry's device tables and staging belong to one upload
 void freeMaterialTables(pt_ctx* ctx);  // ... and so do pt_update_materials'
 // pt_env.cpp
-void releaseEnvStore(pt_ctx* ctx);  // pt_update_env's buffers freed and the env pointers nulled (no-op without a store)
+void releaseEnv(pt_ctx* ctx);  // the environment's buffers freed: an empty store and an empty view
 int ensureBasicImage(pt_ctx* ctx);  // the BASIC double image, allocated and zeroed on first use
 // pt_group.cpp
 int createGroup(pt_ctx* ctx);    // the gather's streams, events, buffers and communicators of a device group

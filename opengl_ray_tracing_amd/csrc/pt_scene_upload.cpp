@@ -9,7 +9,6 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -19,6 +18,7 @@
 #include "pt_plan.h"
 #include "pt_runtime.h"
 #include "pt_scene_prep.h"
+#include "pt_update.h"
 
 using namespace pt;
 
@@ -121,8 +121,7 @@ void freeRefit(pt_ctx* ctx) {
 }
 
 static int uploadScene(pt_ctx* ctx, const float* tris, const SceneHost& h) {
-  if (int rc = syncStreams(ctx)) return rc;  // no frame in flight reads the buffers replaced here
-  if (ctx->queryIssued) CK(hipEventSynchronize(ctx->queryDone));  // nor a ray query, whichever stream it is on
+  if (int rc = waitForReaders(ctx)) return rc;  // of the buffers replaced here
   if (int rc = invalidateScene(ctx, h.ref.depth)) return rc;
   CK(hipSetDevice(ctx->cfg.device_id));
   int rc;
@@ -217,7 +216,6 @@ static int makeRefit(pt_ctx* ctx) {
 // frames and queries in flight. What uploadScene invalidates is invalidated here (invalidateScene).
 static int updateOne(pt_ctx* ctx, const float* d_verts, int stride) {
   if (int rc = invalidateScene(ctx, ctx->depth)) return rc;
-  CK(hipSetDevice(ctx->cfg.device_id));
   if (int rc = makeRefit(ctx)) return rc;
   RefitParams p;
   p.verts = d_verts;
@@ -231,18 +229,9 @@ static int updateOne(pt_ctx* ctx, const float* d_verts, int stride) {
   p.refBox = ctx->d_refBox;
   p.leafBox = ctx->sceneFast ? ctx->d_leafBox : nullptr;
   // PT_UPDATE_TIMES (environment; tools/update_time.py): the device time of each step, on stderr
-  const bool timed = std::getenv("PT_UPDATE_TIMES") != nullptr;
-  struct StepEvents {  // destroyed on every way out
-    hipEvent_t ev[4] = {};
-    ~StepEvents() {
-      for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    }
-  } steps;
-  hipEvent_t* ev = steps.ev;
-  if (timed)
-    for (int k = 0; k < 4; k++) CK(hipEventCreate(&ev[k]));
-  CK(launchRefit(p, ctx->refit, ctx->refitStart.data(), timed ? ev : nullptr, ctx->stream));
+  StepEvents<4> steps;
+  CK(steps.create("PT_UPDATE_TIMES"));
+  CK(launchRefit(p, ctx->refit, ctx->refitStart.data(), steps.events(), ctx->stream));
   ctx->sceneVersion++;  // guides and camera-ray bins of the old positions are stale, runtime tree or not
   bool built = false;
   if (ctx->sceneFast) {
@@ -253,9 +242,9 @@ static int updateOne(pt_ctx* ctx, const float* d_verts, int stride) {
     ctx->accelDepth = ctx->fDepth;
     runtimeTreeReady(ctx);
   }
-  if (timed) {
+  if (steps.on) {
     float ms[3] = {};
-    for (int k = 0; k < 3; k++) CK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+    CK(steps.elapsed(ms));
     std::fprintf(stderr, "pt_update_geometry: records %.4f refit %.4f reencode %.4f build %.4f ms, %d heights, tail from %d\n",
                  ms[0], ms[1], ms[2], ctx->accelMs, ctx->refit.heights, ctx->refit.tailFrom);
   }
@@ -272,38 +261,18 @@ static int updateArgs(pt_ctx* ctx, const void* verts, int nTri, int stride) {
   return PT_OK;
 }
 
-static int updateWait(pt_ctx* ctx) {
-  if (int rc = syncStreams(ctx)) return rc;  // no frame in flight reads the buffers rewritten here
-  if (ctx->queryIssued) CK(hipEventSynchronize(ctx->queryDone));  // nor a ray query, whichever stream it is on
-  return PT_OK;
-}
-
 int pt_update_geometry(pt_ctx* ctx, const float* verts, int nTri, int stride) {
   if (int rc = updateArgs(ctx, verts, nTri, stride)) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  for (pt_ctx* m : members(ctx)) {
-    if (int rc = updateWait(m)) return fromPeer(ctx, m, rc);
-    CK(hipSetDevice(m->cfg.device_id));
-    if (!m->d_updVerts) {
-      hipError_t e = hipMalloc(&m->d_updVerts, (size_t)nTri * 18 * sizeof(float));
-      if (e != hipSuccess) return fail(ctx, PT_E_NOMEM, "pt_update_geometry: vertex staging");
-    }
-    CK(hipMemcpy2DAsync(m->d_updVerts, 18 * sizeof(float), verts, (size_t)stride * sizeof(float), 18 * sizeof(float),
-                        (size_t)nTri, hipMemcpyHostToDevice, m->stream));
-    if (int rc = updateOne(m, m->d_updVerts, 18)) return fromPeer(ctx, m, rc);
-  }
-  ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PT_OK;
+  return updateMembers(ctx, &ctx->uploadMs, [&](pt_ctx* m) {
+    if (int rc = stageRecords(m, &m->d_updVerts, verts, nTri, 18, stride, "pt_update_geometry: vertex staging")) return rc;
+    return updateOne(m, m->d_updVerts, 18);
+  });
 }
 
 int pt_update_geometry_device(pt_ctx* ctx, const void* d_verts, int nTri, int stride) {
   if (int rc = updateArgs(ctx, d_verts, nTri, stride)) return rc;
-  if (!ctx->peers.empty()) return fail(ctx, PT_E_INVALID, "pt_update_geometry_device: not on an n_devices > 1 context");
-  const auto t0 = std::chrono::steady_clock::now();
-  if (int rc = updateWait(ctx)) return rc;
-  if (int rc = updateOne(ctx, static_cast<const float*>(d_verts), stride)) return rc;
-  ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PT_OK;
+  return updateAlone(ctx, "pt_update_geometry_device", &ctx->uploadMs,
+                     [&](pt_ctx* m) { return updateOne(m, static_cast<const float*>(d_verts), stride); });
 }
 
 // ------------------------------------------------------------ material update (pt_materials.hip)
@@ -355,7 +324,6 @@ static int updateMaterialsOne(pt_ctx* ctx, const float* d_mats, int stride) {
   dropHistory(ctx);
   if (int rc = dropMoments(ctx)) return rc;
   ctx->guidesValid = false;
-  CK(hipSetDevice(ctx->cfg.device_id));
   if (int rc = makeMaterialTables(ctx)) return rc;
   MaterialParams p;
   p.mats = d_mats;
@@ -364,25 +332,16 @@ static int updateMaterialsOne(pt_ctx* ctx, const float* d_mats, int stride) {
   p.hitRec = ctx->d_hit;
   p.table = ctx->d_mats;
   // PT_MATERIAL_TIMES (environment; tools/material_time.py): the device time of each step, on stderr
-  const bool timed = std::getenv("PT_MATERIAL_TIMES") != nullptr;
-  struct StepEvents {  // destroyed on every way out
-    hipEvent_t ev[4] = {};
-    ~StepEvents() {
-      for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    }
-  } steps;
-  hipEvent_t* ev = steps.ev;
-  if (timed)
-    for (int k = 0; k < 4; k++) CK(hipEventCreate(&ev[k]));
-  CK(launchMaterials(p, ctx->matTab, timed ? ev : nullptr, ctx->stream));
+  StepEvents<4> steps;
+  CK(steps.create("PT_MATERIAL_TIMES"));
+  CK(launchMaterials(p, ctx->matTab, steps.events(), ctx->stream));
   int nMats = 0;
   CK(hipMemcpyAsync(&nMats, ctx->matTab.count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   CK(hipStreamSynchronize(ctx->stream));
   ctx->nMats = nMats;
-  if (timed) {
+  if (steps.on) {
     float ms[3] = {};
-    for (int k = 0; k < 3; k++) CK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+    CK(steps.elapsed(ms));
     std::fprintf(stderr, "pt_update_materials: insert %.4f scan %.4f scatter %.4f ms, %d materials, %d slots\n", ms[0], ms[1],
                  ms[2], nMats, ctx->matTab.nSlots);
   }
@@ -399,30 +358,16 @@ static int materialArgs(pt_ctx* ctx, const void* mats, int nTri, int stride) {
 
 int pt_update_materials(pt_ctx* ctx, const float* mats, int nTri, int stride) {
   if (int rc = materialArgs(ctx, mats, nTri, stride)) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
-  for (pt_ctx* m : members(ctx)) {
-    if (int rc = updateWait(m)) return fromPeer(ctx, m, rc);
-    CK(hipSetDevice(m->cfg.device_id));
-    if (!m->d_updMats) {
-      hipError_t e = hipMalloc(&m->d_updMats, (size_t)nTri * MAT_KEY * sizeof(float));
-      if (e != hipSuccess) return fail(ctx, PT_E_NOMEM, "pt_update_materials: record staging");
-    }
-    CK(hipMemcpy2DAsync(m->d_updMats, MAT_KEY * sizeof(float), mats, (size_t)stride * sizeof(float), MAT_KEY * sizeof(float),
-                        (size_t)nTri, hipMemcpyHostToDevice, m->stream));
-    if (int rc = updateMaterialsOne(m, m->d_updMats, MAT_KEY)) return fromPeer(ctx, m, rc);
-  }
-  ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PT_OK;
+  return updateMembers(ctx, &ctx->uploadMs, [&](pt_ctx* m) {
+    if (int rc = stageRecords(m, &m->d_updMats, mats, nTri, MAT_KEY, stride, "pt_update_materials: record staging")) return rc;
+    return updateMaterialsOne(m, m->d_updMats, MAT_KEY);
+  });
 }
 
 int pt_update_materials_device(pt_ctx* ctx, const void* d_mats, int nTri, int stride) {
   if (int rc = materialArgs(ctx, d_mats, nTri, stride)) return rc;
-  if (!ctx->peers.empty()) return fail(ctx, PT_E_INVALID, "pt_update_materials_device: not on an n_devices > 1 context");
-  const auto t0 = std::chrono::steady_clock::now();
-  if (int rc = updateWait(ctx)) return rc;
-  if (int rc = updateMaterialsOne(ctx, static_cast<const float*>(d_mats), stride)) return rc;
-  ctx->uploadMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return PT_OK;
+  return updateAlone(ctx, "pt_update_materials_device", &ctx->uploadMs,
+                     [&](pt_ctx* m) { return updateMaterialsOne(m, static_cast<const float*>(d_mats), stride); });
 }
 
 int pt_material_count(pt_ctx* ctx, int* nMats) {

@@ -174,16 +174,11 @@ class Renderer:
         produced it to set_stream, or synchronise. Returns when the scene is ready; restart the
         accumulation at frame_counter 0."""
         what = "update_geometry"
-        if isinstance(verts, np.ndarray) or not hasattr(verts, "data_ptr"):
-            v = np.ascontiguousarray(verts, np.float32)
-            if v.ndim != 2 or v.shape[1] not in (18, 36):
-                raise ValueError(f"{what}: verts must be (n, 18) or (n, 36), not {v.shape}")
-            self._ck(self._lib.pt_update_geometry(self._h, _fp(v), v.shape[0], v.shape[1]), "pt_update_geometry")
+        host, v, (n, stride) = Renderer._update_source(what, "verts", verts, "(n, 18) or (n, 36)", 2, (18, 36))
+        if host:
+            self._ck(self._lib.pt_update_geometry(self._h, _fp(v), n, stride), "pt_update_geometry")
             return
-        if verts.dim() != 2 or verts.shape[1] not in (18, 36):
-            raise ValueError(f"{what}: verts must be (n, 18) or (n, 36), not {tuple(verts.shape)}")
-        n, stride = int(verts.shape[0]), int(verts.shape[1])
-        _, p, _ = self._query_args(what, n, [("verts", verts, "float32", stride, True)])
+        _, p, _ = self._query_args(what, n, [("verts", v, "float32", stride, True)])
         self._ck(self._lib.pt_update_geometry_device(self._h, p[0], n, stride), "pt_update_geometry_device")
 
     def update_materials(self, mats):
@@ -197,20 +192,15 @@ class Renderer:
         or synchronise. Returns when the scene is ready; the guides are stale until the next
         render_guides; restart the accumulation at frame_counter 0."""
         what = "update_materials"
-        if isinstance(mats, np.ndarray) or not hasattr(mats, "data_ptr"):
-            m = np.ascontiguousarray(mats, np.float32)
-            if m.ndim != 2 or m.shape[1] not in (18, 36):
-                raise ValueError(f"{what}: mats must be (n, 18) or (n, 36), not {m.shape}")
-            p = m.ctypes.data + (72 if m.shape[1] == 36 else 0)  # floats 18..35 of a whole record
-            self._ck(self._lib.pt_update_materials(self._h, C.cast(p, _native.c_float_p), m.shape[0], m.shape[1]),
+        host, m, (n, stride) = Renderer._update_source(what, "mats", mats, "(n, 18) or (n, 36)", 2, (18, 36))
+        skip = 72 if stride == 36 else 0  # floats 18..35 of a whole record
+        if host:
+            self._ck(self._lib.pt_update_materials(self._h, C.cast(m.ctypes.data + skip, _native.c_float_p), n, stride),
                      "pt_update_materials")
             return
-        if mats.dim() != 2 or mats.shape[1] not in (18, 36):
-            raise ValueError(f"{what}: mats must be (n, 18) or (n, 36), not {tuple(mats.shape)}")
-        n, stride = int(mats.shape[0]), int(mats.shape[1])
-        self._query_args(what, n, [("mats", mats, "float32", stride, True)])
-        p = C.c_void_p(mats.data_ptr() + (72 if stride == 36 else 0))
-        self._ck(self._lib.pt_update_materials_device(self._h, p, n, stride), "pt_update_materials_device")
+        self._query_args(what, n, [("mats", m, "float32", stride, True)])
+        self._ck(self._lib.pt_update_materials_device(self._h, C.c_void_p(m.data_ptr() + skip), n, stride),
+                 "pt_update_materials_device")
 
     def material_count(self) -> int:
         """The number of distinct materials of the scene (pt_material_count)."""
@@ -266,24 +256,18 @@ class Renderer:
         if hdr is None:
             self._ck(self._lib.pt_update_env(self._h, None, 0, 0, None, flags), "pt_update_env")
             return
-        if isinstance(hdr, np.ndarray) or not hasattr(hdr, "data_ptr"):
+        host, h, (hh, ww, _) = Renderer._update_source(what, "hdr", hdr, "(h, w, 3)", 3, (3,))
+        if host:
             if cache is not None and hasattr(cache, "data_ptr"):
                 raise ValueError(f"{what}: hdr is a host array, cache a tensor: pass both as one kind")
-            h = np.ascontiguousarray(hdr, np.float32)
-            if h.ndim != 3 or h.shape[2] != 3:
-                raise ValueError(f"{what}: hdr must be (h, w, 3), not {h.shape}")
             c = None if cache is None else np.ascontiguousarray(cache, np.float32)
             if c is not None and c.shape != h.shape:
                 raise ValueError(f"{what}: cache must be {h.shape} like hdr, not {c.shape}")
-            self._ck(self._lib.pt_update_env(self._h, _fp(h), h.shape[1], h.shape[0], None if c is None else _fp(c), flags),
-                     "pt_update_env")
+            self._ck(self._lib.pt_update_env(self._h, _fp(h), ww, hh, None if c is None else _fp(c), flags), "pt_update_env")
             return
-        if hdr.dim() != 3 or hdr.shape[2] != 3:
-            raise ValueError(f"{what}: hdr must be (h, w, 3), not {tuple(hdr.shape)}")
-        hh, ww = int(hdr.shape[0]), int(hdr.shape[1])
-        if cache is not None and (not hasattr(cache, "data_ptr") or tuple(cache.shape) != tuple(hdr.shape)):
-            raise ValueError(f"{what}: cache must be a tensor of shape {tuple(hdr.shape)} like hdr")
-        _, p, _ = self._query_args(what, hh * ww, [("hdr", hdr, "float32", 3, True), ("cache", cache, "float32", 3, False)])
+        if cache is not None and (not hasattr(cache, "data_ptr") or tuple(cache.shape) != tuple(h.shape)):
+            raise ValueError(f"{what}: cache must be a tensor of shape {tuple(h.shape)} like hdr")
+        _, p, _ = self._query_args(what, hh * ww, [("hdr", h, "float32", 3, True), ("cache", cache, "float32", 3, False)])
         self._ck(self._lib.pt_update_env_device(self._h, p[0], ww, hh, p[1], flags), "pt_update_env_device")
 
     def env_size(self):
@@ -398,6 +382,20 @@ class Renderer:
         self._ck(self._lib.pt_trace_occluded(self._h, _fp(r), None if b is None else _fp(b), n,
                                              occ.ctypes.data_as(C.POINTER(C.c_uint8))), "pt_trace_occluded")
         return occ
+
+    @staticmethod
+    def _update_source(what, name, value, wanted, ndim, last):
+        """The in-place updates' argument in either form -> (host, value, shape): a host array (anything
+        without data_ptr, made a contiguous float32 numpy array; host True) or a device tensor (as given,
+        for _query_args to check; host False), of ndim dimensions, the last one of `last` -- else
+        ValueError naming the wanted shape."""
+        host = isinstance(value, np.ndarray) or not hasattr(value, "data_ptr")
+        if host:
+            value = np.ascontiguousarray(value, np.float32)
+        shape = tuple(int(k) for k in value.shape)
+        if len(shape) != ndim or shape[-1] not in last:
+            raise ValueError(f"{what}: {name} must be {wanted}, not {shape}")
+        return host, value, shape
 
     def _query_args(self, what, n, specs):
         """The device queries' arguments: specs = [(name, value, dtype name, elements per ray, required)].

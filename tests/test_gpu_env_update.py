@@ -390,3 +390,65 @@ def test_error_paths():
         assert_equals_oracle(frames_of(r), ref, "after the failed calls")
     with Renderer(64, 64, "basic") as r:
         assert rc_of(r.update_env, hdr) == INVALID and rc_of(r.update_env, d) == INVALID and rc_of(r.update_env, None) == INVALID
+
+
+# ------------------------------------------------------------------ 10. uploads and updates in turn: one owner of the buffers
+@pytest.fixture(scope="module")
+def fresh_exact():
+    """An RGBE-exact 37 x 19 map and download_env forms 0, 1 and 2 of a fresh context's upload_env of it."""
+    hdr = env_maps.random_map(37, 19, 21)
+    with Renderer(8, 8) as r:
+        r.upload_env(hdr)
+        assert r.stats().env_compact == 2
+        return hdr, [r.download_env(form) for form in range(3)]
+
+
+def assert_state(r, want, what):
+    assert r.env_size() == (37, 19) and r.stats().env_compact == 2, what
+    for form in (0, 1):
+        same_env(r.download_env(form), want[form], f"{what}: form {form}")
+    none, table = r.download_env(2)
+    assert none is None and env_maps.same_bits_or_nan(table, want[2][1]), f"{what}: row form"
+
+
+def test_update_after_an_upload_of_the_same_size(fresh_exact):
+    """An upload's store holds only the forms that serve its map: the update that follows gets a complete
+    store though the size is the same, and the update after that one allocates nothing."""
+    import torch
+    hdr, want = fresh_exact
+    d, other = tensor(hdr), tensor(env_maps.random_map(37, 19, 22))
+    with Renderer(8, 8) as r:
+        r.upload_env(eu.unquantised_map(37, 19, 43))
+        assert r.env_size() == (37, 19) and r.stats().env_compact == 0
+        r.update_env(d)
+        assert_state(r, want, "upload, update")
+        torch.cuda.synchronize()
+        free = torch.cuda.mem_get_info()[0]
+        r.update_env(other)
+        torch.cuda.synchronize()
+        assert torch.cuda.mem_get_info()[0] == free  # nothing allocated, nothing freed
+        assert r.stats().env_compact == 2
+
+
+def test_upload_between_updates_of_the_same_size(fresh_exact):
+    hdr, want = fresh_exact
+    d = tensor(hdr)
+    with Renderer(8, 8) as r:
+        r.update_env(d)
+        assert r.stats().env_compact == 2
+        r.upload_env(eu.unquantised_map(37, 19, 43))
+        assert r.env_size() == (37, 19) and r.stats().env_compact == 0
+        r.update_env(d)
+        assert_state(r, want, "update, upload, update")
+
+
+def test_a_rejected_upload_leaves_no_environment():
+    """pt_upload_env releases the old environment before it looks at the new one's size."""
+    hdr = env_maps.random_map(37, 19, 21)
+    fp = hdr.ctypes.data_as(C.POINTER(C.c_float))
+    with renderer("lambert", 2, 8, 8) as r, renderer("lambert", 2, 8, 8) as never:
+        r.upload_env(hdr)
+        assert r.env_size() == (37, 19)
+        assert r._lib.pt_upload_env(r._h, fp, 0, 19, None) == INVALID
+        assert r.env_size() == (0, 0) and r.stats().env_compact == 0
+        assert np.array_equal(bits(frames_of(r)), bits(frames_of(never)))

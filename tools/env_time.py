@@ -20,18 +20,16 @@ update is compared with. One JSON line per map.
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import re
 import statistics
 import sys
-import time
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
-from update_time import captured_stderr  # noqa: E402
+from update_common import emit, step_times, wall, write_lines  # noqa: E402
 
 
 def main():
@@ -55,11 +53,6 @@ def main():
         with Renderer(64, 64, "mis") as r:
             has_update = hasattr(r, "update_env")
 
-            def wall(fn):
-                t0 = time.perf_counter()
-                fn()
-                return (time.perf_counter() - t0) * 1e3
-
             ways = {"upload": lambda q: r.upload_env(host[q]), "upload_table": lambda q: r.upload_env(host[q], table[q])}
             if has_update:
                 dev = [torch.from_numpy(m).to("cuda:0") for m in host]
@@ -78,9 +71,7 @@ def main():
             if has_update:
                 for way in ("device", "device_table"):
                     ways[way](0)
-                    os.environ["PT_UPDATE_TIMES"] = "1"
-                    text = captured_stderr(lambda: ways[way](1))
-                    del os.environ["PT_UPDATE_TIMES"]
+                    text = step_times("PT_UPDATE_TIMES", lambda: ways[way](1))
                     m = re.search(r"texels ([\d.]+) table ([\d.]+) compact ([\d.]+) light ([\d.]+) rows ([\d.]+) ms, env_compact (\d), (\d+) rows", text)
                     steps[way] = None if not m else {
                         "texels_ms": float(m.group(1)), "table_ms": float(m.group(2)), "compact_ms": float(m.group(3)),
@@ -96,11 +87,8 @@ def main():
         if has_update:
             line["upload_over_device"] = round(statistics.median(ms["upload"]) / statistics.median(ms["device"]), 2)
             line["upload_table_over_device_table"] = round(statistics.median(ms["upload_table"]) / statistics.median(ms["device_table"]), 2)
-        print(json.dumps(line), flush=True)
-        lines.append(line)
-    if a.out:
-        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.out).write_text("".join(json.dumps(x) + "\n" for x in lines))
+        emit(lines, line)
+    write_lines(a.out, lines)
 
 
 if __name__ == "__main__":

@@ -20,17 +20,15 @@ One JSON line per config.
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import re
 import sys
-import time
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
-from update_time import captured_stderr  # noqa: E402
+from update_common import emit, step_times, wall, write_lines  # noqa: E402
 
 
 def looks(tris):
@@ -64,11 +62,6 @@ def main():
         nodes = np.ascontiguousarray(nodes, np.float32).reshape(-1, 12)
         host = looks(tris)
         with Renderer(cfg.width, cfg.height, cfg.integrator, max_bounce=cfg.max_bounce) as r:
-            def wall(fn):
-                t0 = time.perf_counter()
-                fn()
-                return (time.perf_counter() - t0) * 1e3
-
             first_upload = wall(lambda: r.upload_scene(tris, nodes))
             r.upload_env(hdr)
             dev = [torch.from_numpy(m).to("cuda:0") for m in host]
@@ -91,9 +84,7 @@ def main():
                 r.update_materials(dev[q])  # untimed: the upload freed the update's tables (first_update_ms has that cost)
             breakdown = []
             for q in range(2):
-                os.environ["PT_MATERIAL_TIMES"] = "1"
-                text = captured_stderr(lambda: r.update_materials(dev[q]))
-                del os.environ["PT_MATERIAL_TIMES"]
+                text = step_times("PT_MATERIAL_TIMES", lambda: r.update_materials(dev[q]))
                 m = re.search(r"insert ([\d.]+) scan ([\d.]+) scatter ([\d.]+) ms, (\d+) materials, (\d+) slots", text)
                 breakdown.append(None if not m else {
                     "insert_ms": float(m.group(1)), "scan_ms": float(m.group(2)), "scatter_ms": float(m.group(3)),
@@ -113,11 +104,8 @@ def main():
             "hw_queues_env": os.environ.get("GPU_MAX_HW_QUEUES"), "frames_in_flight": st.frames_in_flight,
             "device": torch.cuda.get_device_name(0),
         }
-        print(json.dumps(line), flush=True)
-        lines.append(line)
-    if a.out:
-        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.out).write_text("".join(json.dumps(x) + "\n" for x in lines))
+        emit(lines, line)
+    write_lines(a.out, lines)
 
 
 if __name__ == "__main__":

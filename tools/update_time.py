@@ -24,16 +24,15 @@ One JSON line per config.
 from __future__ import annotations
 
 import argparse
-import json
-import os
 import re
 import statistics
 import sys
-import tempfile
-import time
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+
+from update_common import emit, step_times, wall, write_lines  # noqa: E402
 
 
 def deformed(tris, phase):
@@ -45,21 +44,6 @@ def deformed(tris, phase):
     ext = F((p.max((0, 1)) - p.min((0, 1))).max())
     p += (F(0.01) * ext) * np.sin((F(9.0) / ext) * p[..., [1, 2, 0]] + F(phase)).astype(F)
     return v
-
-
-def captured_stderr(fn):
-    """fn() with the process's stderr (the library writes there) into a string."""
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile(mode="w+b") as tmp:
-        os.dup2(tmp.fileno(), 2)
-        try:
-            fn()
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-        tmp.seek(0)
-        return tmp.read().decode(errors="replace")
 
 
 def main():
@@ -82,11 +66,6 @@ def main():
         eye, rot = orbit_camera(*cfg.camera)
         poses = [deformed(tris, 0.0), deformed(tris, 1.5)]
         with Renderer(cfg.width, cfg.height, cfg.integrator, max_bounce=cfg.max_bounce) as r:
-            def wall(fn):
-                t0 = time.perf_counter()
-                fn()
-                return (time.perf_counter() - t0) * 1e3
-
             first_upload = wall(lambda: r.upload_scene(tris, nodes))
             r.upload_env(hdr)
             dev = [torch.from_numpy(p).to("cuda:0") for p in poses]
@@ -108,9 +87,7 @@ def main():
                 stats["update"] = r.stats()
                 ms["upload"].append(wall(lambda: r.upload_scene(*fresh[q])))
                 stats["upload"] = r.stats()
-            os.environ["PT_UPDATE_TIMES"] = "1"
-            text = captured_stderr(lambda: r.update_geometry(dev[0]))
-            del os.environ["PT_UPDATE_TIMES"]
+            text = step_times("PT_UPDATE_TIMES", lambda: r.update_geometry(dev[0]))
             m = re.search(r"records ([\d.]+) refit ([\d.]+) reencode ([\d.]+) build ([\d.]+) ms, (\d+) heights, tail from (\d+)", text)
             first = [wall(lambda f=f: r.render_frame(eye, rot, f)) for f in range(32)]
             st = r.stats()
@@ -130,11 +107,8 @@ def main():
             "steady_frame_ms": round(statistics.median(first[24:]), 3),
             "max_stack": st.max_stack, "accel_nodes": st.accel_nodes,
         }
-        print(json.dumps(line), flush=True)
-        lines.append(line)
-    if a.out:
-        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(a.out).write_text("".join(json.dumps(x) + "\n" for x in lines))
+        emit(lines, line)
+    write_lines(a.out, lines)
 
 
 if __name__ == "__main__":
