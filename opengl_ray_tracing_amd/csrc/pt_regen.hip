@@ -4,7 +4,9 @@
 // Every lane owns one path at a time and runs one loop: trace the lane's
 // current ray (closest hit, or any hit for an env shadow ray) through the single
 // traversal call site, then advance the path by one event (primary hit/miss,
-// bounce hit/miss, shadow result). A lane whose path has ended writes its
+// bounce hit/miss, shadow result; the uniform integrators in two stages, resolve
+// after the walk and one hit-shading site at the top of the loop, below). A lane
+// whose path has ended writes its
 // pixel's running mean and immediately takes the next pixel of its wave's 8x8
 // tile (ballot + prefix over the idle lanes); a wave takes a new tile from the
 // per-XCD-group work queues when its tile is used up. Lanes therefore never
@@ -73,7 +75,9 @@ constexpr int REGEN_TOP4 = PT_REGEN_TOP4;
 constexpr bool regenLists(int integ, int waves) {
   return !(integ == 2 && waves == PT_WIDE_REGEN_WAVES && PT_WIDE_REGEN_WAVES_SMALL != PT_WIDE_REGEN_WAVES);
 }
-enum : int { K_NONE = 0, K_PRIMARY = 1, K_BOUNCE = 2, K_SHADOW = 3 };
+// K_HIT (uniform integrators): the K_PRIMARY / K_BOUNCE ray has hit and the path goes on; its hit waits,
+// in the lane's Walk4 (best, tbest), for the shade stage at the top of the next loop turn
+enum : int { K_NONE = 0, K_PRIMARY = 1, K_BOUNCE = 2, K_SHADOW = 3, K_HIT = 4 };
 
 struct PathState {
   int px, py;
@@ -222,18 +226,79 @@ __device__ __forceinline__ bool continueFromHit(const RenderParams& p, PathState
   return false;
 }
 
-// Advance the path by the result (tri, t) of its ray in flight. Returns false
-// when the path has ended (its final color in `color`). A camera ray's hit and a
-// bounce ray's hit go through ONE finishHit and ONE continueFromHit (the same
-// operations on the same values as separate paths would make): the lanes of a wave
-// holding either kind shade together, and each call site of advance holds one copy
-// of the shading code (the MIS wide kernel 14.3k -> 11.0k instructions; c2 and c5
-// frame times unchanged, tools/tune.py). Shading the camera-ray pass's hits in the
-// main loop instead of the refill loop (no second call site) made the kernel smaller
-// still (7.5k) but slower -- c2 0.233 -> 0.266 ms, c5 5.55 -> 5.64 -- the lanes
-// holding them sat out a walk step before their first bounce.
+// The uniform integrators advance a path in two stages, so that a loop turn runs the hit-shading code
+// (finishHit + continueFromHit: 14 float4 loads a lane, two divisions, a normalise, the BRDF) ONCE, for
+// the camera hits the hand-out has just taken and the bounce hits of the turn before together. With a
+// second site after the walk that code ran again almost every turn for the few lanes holding a bounce
+// hit -- c2: about 9 of 64, against 40 at the top -- at the same issue slots. The bounce
+// hits move up, not the camera hits down: a lane still shades directly before its next walk step, so
+// none sits out a step (moving the camera hits to the bottom did, c2 0.233 -> 0.266 ms, round 5).
+//
+// resolve: the result (tri, t) of the lane's K_PRIMARY / K_BOUNCE ray, with everything that may end the
+// path. A miss (O:347-360 / D:463-479; the camera ray's IS:857-859) ends it. A hit at the last level --
+// no ray would follow -- ends it too, and only its material's emission is read (finishHit's
+// h.m.emissive, the same bits; the hist update is dead there). Any other hit stays pending on the lane
+// (K_HIT). Returns false when the path has ended (its final color in `color`).
+template <int INTEG>
+__device__ __forceinline__ bool resolve(const RenderParams& p, PathState& s, int tri, V3& color) {
+  static_assert(INTEG != 2, "the uniform integrators' stages");
+  const bool primary = s.kind == K_PRIMARY;
+  const float pdf = 1.0f / (2.0f * PT_PI);
+  if (tri < 0) {
+    const V3 sky = sampleHdr(p.env, s.d);
+    if (primary) {
+      color = sky;
+    } else {
+      s.Lo = s.Lo + ((s.hist * sky) * s.f_r * s.cosL) / pdf;
+      color = s.Le0 + s.Lo;
+    }
+    return false;
+  }
+  if ((primary ? 0 : s.bounce + 1) >= p.maxBounce) {
+    const V3 Le = emissiveOf(p.scene, tri);
+    if (primary) s.Le0 = Le;
+    else s.Lo = s.Lo + ((s.hist * Le) * s.f_r * s.cosL) / pdf;
+    color = s.Le0 + s.Lo;
+    return false;
+  }
+  s.kind |= K_HIT;
+  return true;
+}
+
+// shadeHit: the pending hit (tri, t) of a K_HIT lane, a camera ray's or a bounce ray's, through ONE
+// finishHit and ONE continueFromHit (the same operations on the same values as separate paths would
+// make). Returns false when the path has ended (max_bounce 0: at a camera hit of the camera-ray pass).
+template <int INTEG>
+__device__ __forceinline__ bool shadeHit(const RenderParams& p, PathState& s, int tri, float t, V3& color) {
+  static_assert(INTEG != 2, "the uniform integrators' stages");
+  const bool primary = s.kind == (K_PRIMARY | K_HIT);
+  s.kind &= ~K_HIT;
+  Hit hit;
+  finishHit(p.scene, tri, s.o, s.d, t, hit);  // O:331-333 / D:445-446 (a bounce), IS:852-856 (the camera ray)
+  const V3 Le = hit.m.emissive;
+  if (primary) {
+    s.Le0 = Le;
+  } else {
+    const float pdf = 1.0f / (2.0f * PT_PI);
+    s.Lo = s.Lo + ((s.hist * Le) * s.f_r * s.cosL) / pdf;
+    s.hist = s.hist * ((s.f_r * s.cosL) / pdf);
+  }
+  if (continueFromHit<INTEG>(p, s, hit, primary ? 0 : s.bounce + 1)) return true;
+  color = s.Le0 + s.Lo;
+  return false;
+}
+
+// The MIS integrator's one stage: advance the path by the result (tri, t) of its ray in flight.
+// Returns false when the path has ended (its final color in `color`). A camera ray's hit and a
+// bounce ray's hit go through ONE finishHit and ONE continueFromHit (the same operations on the
+// same values as separate paths would make): the lanes of a wave holding either kind shade
+// together, and each call site of advance -- the hand-out and after the walk -- holds one copy of
+// the shading code (the MIS wide kernel 14.3k -> 11.0k instructions; c5's frame time unchanged,
+// tools/tune.py). The uniform integrators' split above is not applied here: the MIS kernels sit at
+// their register limit and c3 has 3 k bounce hits a frame.
 template <int INTEG>
 __device__ __forceinline__ bool advance(const RenderParams& p, PathState& s, int tri, float t, V3& color) {
+  static_assert(INTEG == 2, "the uniform integrators advance by resolve + shadeHit");
   const SceneView& S = p.scene;
   if (s.kind == K_SHADOW) {  // IS:776-790
     if (tri < 0) s.Lo = s.Lo + s.shC;
@@ -251,18 +316,12 @@ __device__ __forceinline__ bool advance(const RenderParams& p, PathState& s, int
       color = sampleHdr(p.env, s.d);
       return false;
     }
-    if (INTEG == 2) {  // IS:819-829
-      V3 c;
-      float pdf_light;
-      hdrColorPdf(p.env, s.d, c, pdf_light);
-      float mis_weight = misWeight(s.pdfB, pdf_light);
-      V3 cc = ((s.hist * mis_weight) * c) * s.f_r;
-      s.Lo = s.Lo + (cc * s.cosL) / s.pdfB;
-    } else {  // O:347-360 / D:463-479
-      const float pdf = 1.0f / (2.0f * PT_PI);
-      V3 sky = sampleHdr(p.env, s.d);
-      s.Lo = s.Lo + ((s.hist * sky) * s.f_r * s.cosL) / pdf;
-    }
+    V3 c;  // IS:819-829
+    float pdf_light;
+    hdrColorPdf(p.env, s.d, c, pdf_light);
+    float mis_weight = misWeight(s.pdfB, pdf_light);
+    V3 cc = ((s.hist * mis_weight) * c) * s.f_r;
+    s.Lo = s.Lo + (cc * s.cosL) / s.pdfB;
     color = camEmission<INTEG>(p, s) + s.Lo;
     return false;
   }
@@ -270,10 +329,9 @@ __device__ __forceinline__ bool advance(const RenderParams& p, PathState& s, int
   finishHit(S, tri, s.o, s.d, t, hit);  // IS:833-837 (a bounce), IS:852-856 (the camera ray)
   const V3 Le = hit.m.emissive;
   if (primary) {
-    if (INTEG == 2) s.mat0 = hit.matId;
-    else s.Le0 = Le;
+    s.mat0 = hit.matId;
   } else {
-    const float pdf = INTEG == 2 ? s.pdfB : 1.0f / (2.0f * PT_PI);
+    const float pdf = s.pdfB;
     s.Lo = s.Lo + ((s.hist * Le) * s.f_r * s.cosL) / pdf;
     s.hist = s.hist * ((s.f_r * s.cosL) / pdf);
   }
@@ -352,12 +410,14 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
 #endif
 #if PT_PHASE_STATS
   // diagnostics build: per wave, in LDS (first active lane adds): [0] refill cycles, [1] walk
-  // cycles, [2] reference-check cycles, [3] shading cycles, [4] main-loop iterations, [5] lanes
-  // walking, [6] lanes shading, [7]/[8] node iterations / lanes, [9]/[10] pair tests / lanes,
-  // [11] refill iterations, [12] lanes whose walk ran out of the yield, [13] walk calls that end
-  // every walk, [14] retraced lanes, [15] wave lifetime (clock64 cycles); the TILE_PRIM hand-out:
-  // [16] hand-out cycles, [17] tile claims, [18] claim cycles (atomic + camera-ray results),
-  // [19] camera-hit shading cycles, [20] lanes shaded there, [21] camera-hit shading passes
+  // cycles, [2] reference-check cycles, [3] cycles after the walk (the uniform integrators' resolve
+  // stage, MIS: advance), [4] main-loop iterations, [5] lanes walking, [6] lanes with a finished walk,
+  // [7]/[8] node iterations / lanes, [9]/[10] pair tests / lanes, [11] refill iterations, [12] lanes
+  // whose walk ran out of the yield, [13] walk calls that end every walk, [14] retraced lanes,
+  // [15] wave lifetime (clock64 cycles); the TILE_PRIM hand-out: [16] hand-out cycles, [17] tile
+  // claims, [18] claim cycles (atomic + camera-ray results), [19] shade-stage cycles, [20] lanes
+  // shaded there (camera and bounce hits), [21] shade-stage passes with a lane; after the walk:
+  // [22] lanes holding a hit, [23] those of them at the last level (no ray follows)
   __shared__ unsigned long long s_ph[BS / 64][PHASE_WORDS];
   unsigned long long* ph = s_ph[threadIdx.x >> 6];
   if (lane < PHASE_WORDS) ph[lane] = 0;
@@ -383,8 +443,9 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
       // need a path -- the claimed tile's camera-ray results are loaded at once (lane k: slot k)
       // and its non-sky slots compacted into s_slot, so one pass hands every idle lane a pixel
       // (sky pixels, finished by the camera-ray pass, are never handed out) -- and then the camera
-      // hits taken here are shaded together, once (shading inside the hand-out loop ran that code
-      // once per hand-out pass, for a few lanes each time)
+      // hits taken here are shaded, once, together with the bounce hits the resolve stage left
+      // pending (shading inside the hand-out loop ran that code once per hand-out pass, for a few
+      // lanes each time; shading the bounce hits after the walk ran it a second time every turn)
       while (true) {
         bool pend = false;
         int2 hP = make_int2(0, 0);
@@ -458,26 +519,34 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
           }
           cursor = min(nValid, cursor + __popcll(idle));
         }
-        // the camera hits just taken, shaded together (a PRIM_RETRACE / PRIM_TILE camera ray is
-        // traced below like any ray)
+        // the shade stage: the camera hits just taken and the bounce hits resolve left pending, shaded
+        // together (a PRIM_RETRACE / PRIM_TILE camera ray is traced below like any ray). A pending hit
+        // lies in the lane's Walk4, which nothing else uses until walk4Begin
 #if PT_PHASE_STATS
         PH_ADD(16, clock64() - phH);
         const long long phS = clock64();
-        if (__ballot(pend)) {
-          PH_ADD(21, 1);
-          PH_ADD(20, __popcll(__ballot(pend)));
-        }
 #endif
-        bool ended = false;
         if (pend) {
           startPath(p, s);
           if (hP.x >= 0) {
-            V3 color;
-            if (!advance<INTEG>(p, s, hP.x, __int_as_float(hP.y), color)) {
-              writeAccum(p, s, color);
-              active = false;
-              ended = true;
-            }
+            s.kind = K_PRIMARY | K_HIT;
+            w.best = hP.x;
+            w.tbest = __int_as_float(hP.y);
+          }
+        }
+#if PT_PHASE_STATS
+        if (__ballot((s.kind & K_HIT) != 0)) {
+          PH_ADD(21, 1);
+          PH_ADD(20, __popcll(__ballot((s.kind & K_HIT) != 0)));
+        }
+#endif
+        bool ended = false;
+        if (s.kind & K_HIT) {
+          V3 color;
+          if (!shadeHit<INTEG>(p, s, w.best, w.tbest, color)) {
+            writeAccum(p, s, color);
+            active = false;
+            ended = true;
           }
         }
 #if PT_PHASE_STATS
@@ -601,9 +670,27 @@ __global__ __launch_bounds__(BS, WAVES > 0 ? WAVES : (INTEG == 2 ? PT_REGEN_MIN_
                                                                             s.kind == K_SHADOW, top);
     }
     V3 color;
-    if (!advance<INTEG>(p, s, tri, t, color)) {
-      writeAccum(p, s, color);
-      active = false;
+#if PT_PHASE_STATS
+    {
+      const bool hitNow = tri >= 0 && s.kind != K_SHADOW;
+      PH_ADD(22, __popcll(__ballot(hitNow)));
+      PH_ADD(23, __popcll(__ballot(hitNow && (s.kind == K_PRIMARY ? 0 : s.bounce + 1) >= p.maxBounce)));
+    }
+#endif
+    if constexpr (TILE_PRIM) {
+      // the resolve stage: the path ends, or its hit waits for the shade stage at the top of the loop
+      if (!resolve<INTEG>(p, s, tri, color)) {
+        writeAccum(p, s, color);
+        active = false;
+      } else {
+        w.best = tri;  // (the retrace's triangle and t, where it ran)
+        w.tbest = t;
+      }
+    } else {
+      if (!advance<INTEG>(p, s, tri, t, color)) {
+        writeAccum(p, s, color);
+        active = false;
+      }
     }
 #if PT_PHASE_STATS
     PH_ADD(3, clock64() - phT);

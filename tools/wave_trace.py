@@ -45,7 +45,9 @@ def regen(path, per=None):
                         for k in last))
 
 
-PHASES = ["refill", "walk", "reference check", "shading"]
+# [3]: the cycles after the walk -- the uniform integrators' resolve stage (misses, last-level hits; the
+# hits that go on are shaded in the refill's shade stage), the MIS kernel's whole advance
+PHASES = ["refill", "walk", "reference check", "resolve"]
 
 
 def phases(path):
@@ -59,15 +61,18 @@ def phases(path):
         print(f"  {name:16s} {t[k] / life:6.3f} of wave time")
     print(f"  (unaccounted      {1 - t[:4].sum() / life:6.3f})")
     it = max(t[4], 1)
-    print(f"main-loop iterations with a walk {t[4]:.3g}: lanes walking {t[5] / it:5.1f}, lanes shading {t[6] / it:5.1f}"
+    print(f"main-loop iterations with a walk {t[4]:.3g}: lanes walking {t[5] / it:5.1f}, lanes resolved {t[6] / it:5.1f}"
           f" (walks cut by the yield {t[12] / it:5.1f} lanes; iterations ending every walk {t[13] / it:.3f})")
     print(f"node iterations {t[7]:.3g} ({t[7] / it:.1f} per walk call), lanes {t[8] / max(t[7], 1):5.1f} of 64")
     print(f"pair tests      {t[9]:.3g} ({t[9] / it:.1f} per walk call), lanes {t[10] / max(t[9], 1):5.1f} of 64")
     print(f"refill iterations {t[11]:.3g}; retraced lanes {t[14]:.3g}")
     if t[17] > 0:  # the uniform integrators' hand-out (TILE_PRIM)
         print(f"  refill = hand-out {t[16] / life:6.3f} (of it tile claims {t[18] / life:6.3f}: {t[17]:.3g} claims, "
-              f"{t[18] / max(t[17], 1) / 2.4e3:.2f} us each) + camera-hit shading {t[19] / life:6.3f} "
-              f"({t[21]:.3g} passes, {t[20] / max(t[21], 1):.1f} lanes each)")
+              f"{t[18] / max(t[17], 1) / 2.4e3:.2f} us each) + shade stage {t[19] / life:6.3f} "
+              f"({t[21]:.3g} passes, {t[20] / max(t[21], 1):.1f} lanes each: camera and bounce hits)")
+    # the event mix after the walk: of the resolved lanes, those holding a hit and the last-level ones among them
+    print(f"resolved after the walk: {t[6]:.4g} lanes, {t[22]:.4g} hits ({t[22] / it:.1f} per turn), "
+          f"{t[23]:.4g} of them at the last level ({t[23] / it:.1f} per turn)")
 
 
 def main():
