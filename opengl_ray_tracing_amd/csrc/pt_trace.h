@@ -219,6 +219,14 @@ __device__ __forceinline__ bool triTest(float4 A, float4 B, float4 C, float4 Nn,
 // c4 0.2888 -> 0.2803, c5 5.48 -> 5.34.)
 // g0/g1: accepted apart from the caller's closest-hit bound.
 // ids (pairTestIds): the two triangles' uploaded indices stored in the record (buildPairs)
+//
+// pairHalf evaluates every test for every lane, like triTest, and takes its operands as values
+// that pairTestT has already pinned in registers: the && chain of g short-circuits, and with the
+// record's loads still movable the compiler split them around it -- the normals, w and the second
+// triangle's vertices first (11 loads, 8 of them single dwords), then a branch on the first
+// triangle's plane test, and only behind it 9 more single-dword loads of the first triangle's
+// vertices: two dependent round trips and ~20 VMEM instructions per pair test where the record
+// is 7 float4.
 __device__ __forceinline__ void pairHalf(float p1x, float p1y, float p1z, float p2x, float p2y, float p2z, float p3x,
                                          float p3y, float p3z, float nx, float ny, float nz, float w, V3 o, V3 d,
                                          float& t, bool& g) {
@@ -242,7 +250,13 @@ __device__ __forceinline__ void pairHalf(float p1x, float p1y, float p1z, float 
 template <bool IDS = false>
 __device__ __forceinline__ void pairTestT(const float4* r, V3 o, V3 d, float& t0, float& t1, bool& g0, bool& g1,
                                           int* ids = nullptr) {
-  const float4 q0 = r[0], q1 = r[1], q2 = r[2], q3 = r[3], q4 = r[4], q5 = r[5], q6 = r[6];
+  // The record in one round trip: seven 16-byte loads, all passed through one empty asm before the
+  // first arithmetic. The asm makes every component a value defined at that point, so no load can
+  // be narrowed to the dwords a path uses, split, or sunk behind pairHalf's tests (see pairHalf:
+  // without the pin the leaf step took two dependent trips). Plain loads: the cache scope stays.
+  const f32x4_t* rv = reinterpret_cast<const f32x4_t*>(r);
+  f32x4_t q0 = rv[0], q1 = rv[1], q2 = rv[2], q3 = rv[3], q4 = rv[4], q5 = rv[5], q6 = rv[6];
+  asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3), "+v"(q4), "+v"(q5), "+v"(q6));
   if (IDS) ids[0] = __float_as_int(q6.z), ids[1] = __float_as_int(q6.w);
   // (p1.x, p1.y, p1.z, p2.x, ..., Ng.z, w) of triangle i in the x halves, i + 1 in the y halves
   pairHalf(q0.x, q0.z, q1.x, q1.z, q2.x, q2.z, q3.x, q3.z, q4.x, q4.z, q5.x, q5.z, q6.x, o, d, t0, g0);
@@ -1038,6 +1052,9 @@ __device__ __forceinline__ void finishHit(const SceneView& S, int tri, V3 o, V3 
   // the triangle's vertices and normal from its pair record (the x halves), the
   // record the leaf test of an uploaded-tree traversal has just read
   const float4* pr = S.pairs + PAIR_F4 * (size_t)tri;
+  // (Loading the six float4 whole and pinned with the hitRec loads, as pairTestT does, was measured in
+  // round 24 and not kept: c2 0.1435-0.1453 ms against 0.1431-0.1441, and the Disney and MIS regen
+  // kernels spill 3 and 4 more VGPRs. DESIGN.md 3m.)
   const float4 r0 = pr[0], r1 = pr[1], r2 = pr[2], r3 = pr[3], r4 = pr[4], r5 = pr[5];
   V3 p1 = v3(r0.x, r0.z, r1.x), p2 = v3(r1.z, r2.x, r2.z), p3 = v3(r3.x, r3.z, r4.x);
   bool inside = dot(v3(r4.z, r5.x, r5.z), d) > 0.0f;
