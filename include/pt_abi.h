@@ -457,7 +457,8 @@ int pt_trace_occluded_device(pt_ctx* ctx, const void* d_rays, const void* d_tmax
  * camera and image size, out[k].rgb is bit for bit the sample a frame with sample index s (frameCounter *
  * sample_world + sample_rank) gives that pixel -- whatever k, n, the other rays and this context's own
  * width and height are.
- * One sample per call: fold several calls with the running-mean weights 1 / (i + 1). The context's flags
+ * One sample per call: fold several calls with the running-mean weights 1 / (i + 1), or let
+ * pt_radiance_mean_device below take and fold many samples in one call. The context's flags
  * apply as they do to the ray queries (PT_FLAG_NO_CULL, PT_FLAG_REFERENCE_TREE, PT_FLAG_COUNT_FETCHES; the
  * default is the runtime's tree with the reference check). pt_frame_stats is not touched. With
  * n_devices > 1 the call runs on device_ids[0]. PT_E_NOSCENE before pt_upload_scene and on a
@@ -470,6 +471,37 @@ int pt_trace_occluded_device(pt_ctx* ctx, const void* d_rays, const void* d_tmax
 int pt_radiance_device(pt_ctx* ctx, const void* d_rays /* n x 6 f32 */, const void* d_ids /* n x 2 i32 or NULL */,
                        int n, uint32_t sampleIndex, void* d_out /* n x 4 f32: r, g, b, t */);
 int pt_radiance(pt_ctx* ctx, const float* rays, const int* ids, int n, uint32_t sampleIndex, float* out);
+/* Many samples per call, folded on the GPU: the radiance query's counterpart of pt_render_frames_async and
+ * PT_FLAG_MOMENTS. For ray k and j = 0 .. nSamples-1, with s = firstSample + j:
+ *   - c_j is pt_radiance_device's out[k].rgb for sample index s along ray rays[k], bit for bit -- or, with
+ *     PT_RADIANCE_RAYS_PER_SAMPLE, along ray rays[j * n + k]: the array is then nSamples x n x 6 f32, for a
+ *     caller who jitters per sample;
+ *   - the fold, one IEEE f32 operation per step (no fused multiply-add), is the frames' running-mean update:
+ *       w = 1.0f / (float)(s + 1u);  a = mixf(a, c_j, w) per channel, mixf(x, y, w) = x * (1.0f - w) + y * w;
+ *       l = (0.3f r + 0.6f g) + 0.1f b of c_j;  m1 = mixf(m1, l, w);  m2 = mixf(m2, l * l, w);
+ *   - firstSample == 0 starts from a = 0 and m = 0: d_mean and d_moments are not read, whatever they hold.
+ *     Otherwise a is read from d_mean[k].rgb and m from d_moments[k], so a picture goes on across calls
+ *     exactly as frames do across launches;
+ *   - d_mean[k] = (a, t of the last sample's ray, 2147483648.f on a miss); d_moments[k] = (m1, m2), not
+ *     touched when d_moments is NULL.
+ * Without PT_RADIANCE_RAYS_PER_SAMPLE the ray's closest hit is searched once for all its samples, and a
+ * ray that leaves the scene folds its one sky colour nSamples times.
+ * The consequence: with per-sample rays equal to pt_camera_rays_device's of samples 0 .. N-1 and ids (px, py),
+ * firstSample 0 and nSamples N, d_mean.rgb is bit for bit the accumulation of pt_render_frames_async(.., 0, N)
+ * and d_moments bit for bit a PT_FLAG_MOMENTS context's plane.
+ * Everything else as pt_radiance_device: the default ids, the context's flags, device_ids[0], pt_frame_stats
+ * untouched, stream order on the context's stream, its turn among the queries (one overflow area), frames in
+ * flight may overlap it, no allocation in the steady state; d_mean must be 16-byte aligned, d_moments 8-byte.
+ * PT_E_INVALID for nSamples < 1, firstSample + nSamples > 2^32 - 1 (the weight's s + 1u must not wrap),
+ * unknown flag bits, n < 0, or a NULL rays or mean with n > 0; PT_E_NOSCENE before pt_upload_scene and on a
+ * PT_BASIC_CPU_COMPAT context; n == 0 is PT_OK and reads and writes nothing.
+ * The host form stages rays, ids, mean and moments in and mean and moments out, and is synchronous. */
+#define PT_RADIANCE_RAYS_PER_SAMPLE 0x1u /* rays is nSamples x n x 6 f32: sample j's ray k at rays[j * n + k] */
+int pt_radiance_mean_device(pt_ctx* ctx, const void* d_rays, const void* d_ids /* n x 2 i32 or NULL */, int n,
+                            uint32_t firstSample, int nSamples, uint32_t flags,
+                            void* d_mean /* n x 4 f32: r, g, b, t */, void* d_moments /* n x 2 f32 or NULL */);
+int pt_radiance_mean(pt_ctx* ctx, const float* rays, const int* ids, int n, uint32_t firstSample, int nSamples,
+                     uint32_t flags, float* mean, float* moments);
 /* The frame kernels' camera rays of sample sampleIndex, jitter included, for every pixel of the context's
  * width x height: ray py * width + px = (eye, the pixel's jittered direction), id = (px, py). Asynchronous on
  * the context's stream. PT_E_INVALID on a PT_BASIC_CPU_COMPAT context or for a NULL d_rays. */

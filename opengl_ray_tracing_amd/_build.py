@@ -68,6 +68,8 @@ SOURCES = {
     "pt_temporal.o": ("hip", CSRC / "pt_temporal.hip", _DEV),
     "pt_variance.o": ("hip", CSRC / "pt_variance.hip", [CSRC / "pt_atrous.h", *_DEV]),
     "pt_adaptive.o": ("hip", CSRC / "pt_adaptive.hip", _FRAME),
+    # (last of the device objects: the order bench.py's c2 line was measured with)
+    "pt_radiance_mean.o": ("hip", CSRC / "pt_radiance_mean.hip", [*_FRAME, CSRC / "pt_paths.h"]),
     # the host runtime by subject (pt_runtime.h lists the files); the host-only scene preparation keeps
     # -ffp-contract=off like the rest: its unit normal and plane offset round as the reference's do
     "pt_context.o": ("cxx", CSRC / "pt_context.cpp", [*_HOST, CSRC / "pt_plan.h", INCLUDE / "pt_fmath.h"]),

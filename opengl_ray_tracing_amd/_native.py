@@ -126,6 +126,10 @@ SIGNATURES = {
     "pt_trace_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pt_radiance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]),
     "pt_radiance": (C.c_int, [C.c_void_p, c_float_p, c_int_p, C.c_int, C.c_uint32, c_float_p]),
+    "pt_radiance_mean_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_uint32,
+                                          C.c_void_p, C.c_void_p]),
+    "pt_radiance_mean": (C.c_int, [C.c_void_p, c_float_p, c_int_p, C.c_int, C.c_uint32, C.c_int, C.c_uint32, c_float_p,
+                                   c_float_p]),
     "pt_camera_rays_device": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pt_build_bvh_device": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, c_float_p, C.c_int, c_int_p, c_int_p]),
     "pt_download_accum": (C.c_int, [C.c_void_p, c_float_p]),

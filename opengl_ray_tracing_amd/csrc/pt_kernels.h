@@ -328,6 +328,25 @@ struct RadianceParams {
 #define PT_RADIANCE_WAVES_MIS 3
 #endif
 hipError_t launchRadiance(const RadianceParams& p, int integrator, int grid, hipStream_t s, bool cull);
+// nSamples samples per ray folded into a running mean and the luminance moments (pt_radiance_mean.hip
+// radianceMeanKernel; pt_abi.h pt_radiance_mean_device): sample j of ray k is radianceKernel's for sample
+// index firstSample + j, the fold pt_display.hip mixFrames'
+struct RadianceMeanParams {
+  SceneView scene;
+  Env env;
+  const float* rays;   // n x 6, or nSamples x n x 6 (perSample): sample j's ray k at rays + 6 * (j * n + k)
+  const int* ids;      // n x 2 (px, py); null: (k & 4095, k >> 12)
+  int n;
+  uint32_t firstSample;
+  int nSamples;        // >= 1, firstSample + nSamples <= 2^32 - 1
+  int perSample;
+  int maxBounce;
+  float4* mean;        // n x (r, g, b, t of the last sample's ray); read when firstSample != 0
+  float2* moments;     // n x (m1, m2), may be null; read when firstSample != 0
+  int* ovf;            // the queries' traversal stack overflow (per thread ovfDepth ints), may be null
+  int ovfDepth;
+};
+hipError_t launchRadianceMean(const RadianceMeanParams& p, int integrator, int grid, hipStream_t s, bool cull);
 // The frame kernels' camera rays of one sample (pt_frame.h cameraRay) for every pixel of a width x height
 // image: ray py * width + px = (eye, direction) into rays (6 floats each), (px, py) into ids (may be null)
 struct CameraRaysParams {

@@ -2,8 +2,9 @@
 // without a bound per ray, on device memory in stream order or on host arrays. One kernel
 // (pt_query.hip queryKernel) and one host path (queryHost) serve every entry point. And the radiance
 // query (pt_radiance_device, pt_radiance: pt_radiance.hip radianceKernel), which shares the queries'
-// overflow area and their one-at-a-time ordering, with the camera rays it is specified against
-// (pt_camera_rays_device).
+// overflow area and their one-at-a-time ordering, with its many-sample form folded on the GPU
+// (pt_radiance_mean_device, pt_radiance_mean: pt_radiance_mean.hip) and the camera rays it is specified
+// against (pt_camera_rays_device).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -201,6 +202,75 @@ int pt_radiance(pt_ctx* ctx, const float* rays, const int* ids, int n, uint32_t 
   if (ids) CK(hipMemcpyAsync(dIds, ids, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   if (int rc = radianceOne(ctx, dRays, ids ? dIds : nullptr, n, sampleIndex, dOut)) return rc;
   CK(hipMemcpyAsync(out, dOut, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  CK(hipStreamSynchronize(ctx->stream));
+  return PT_OK;
+}
+
+// nSamples samples (firstSample ...) along n > 0 rays in device memory, folded into d_mean (and d_moments,
+// nullable) by pt_radiance_mean.hip; otherwise as radianceOne
+static int radianceMeanOne(pt_ctx* ctx, const void* d_rays, const void* d_ids, int n, uint32_t firstSample,
+                           int nSamples, uint32_t flags, void* d_mean, void* d_moments) {
+  int ovfDepth = 0;
+  if (int rc = beginQuery(ctx, &ovfDepth)) return rc;
+  RadianceMeanParams p;
+  p.scene = queryScene(ctx);
+  p.env = envView(ctx, rowTable(ctx, false), largeScene(ctx) ? 1 : 0);  // as radianceOne
+  p.rays = static_cast<const float*>(d_rays);
+  p.ids = static_cast<const int*>(d_ids);
+  p.n = n;
+  p.firstSample = firstSample;
+  p.nSamples = nSamples;
+  p.perSample = (flags & PT_RADIANCE_RAYS_PER_SAMPLE) ? 1 : 0;
+  p.maxBounce = maxBounce(ctx->cfg);
+  p.mean = static_cast<float4*>(d_mean);
+  p.moments = static_cast<float2*>(d_moments);
+  p.ovf = ovfDepth ? ctx->d_queryOvf : nullptr;
+  p.ovfDepth = ovfDepth;
+  CK(launchRadianceMean(p, ctx->cfg.integrator, queryGrid(ctx, n), ctx->stream, queryCull(ctx)));
+  return endQuery(ctx);
+}
+
+// the checks of the two forms: the sample range and the flags first, then queryArgs
+static int radianceMeanArgs(pt_ctx* ctx, int n, uint32_t firstSample, int nSamples, uint32_t flags, bool pointers,
+                            bool* run) {
+  *run = false;
+  if (nSamples < 1 || (uint64_t)firstSample + (uint64_t)nSamples > 0xFFFFFFFFull) return PT_E_INVALID;  // s + 1u must not wrap
+  if (flags & ~(uint32_t)PT_RADIANCE_RAYS_PER_SAMPLE) return PT_E_INVALID;
+  return queryArgs(ctx, n, pointers, run);
+}
+
+int pt_radiance_mean_device(pt_ctx* ctx, const void* d_rays, const void* d_ids, int n, uint32_t firstSample,
+                            int nSamples, uint32_t flags, void* d_mean, void* d_moments) {
+  bool run;
+  if (int rc = radianceMeanArgs(ctx, n, firstSample, nSamples, flags, d_rays && d_mean, &run)) return rc;
+  return run ? radianceMeanOne(ctx, d_rays, d_ids, n, firstSample, nSamples, flags, d_mean, d_moments) : PT_OK;
+}
+
+// The host form, staged like pt_radiance: per ray 4 floats of mean and 2 of moments (in when the picture
+// goes on, and out), 2 ints of id, and 6 floats per ray the caller gave (n, or nSamples x n)
+int pt_radiance_mean(pt_ctx* ctx, const float* rays, const int* ids, int n, uint32_t firstSample, int nSamples,
+                     uint32_t flags, float* mean, float* moments) {
+  bool run;
+  if (int rc = radianceMeanArgs(ctx, n, firstSample, nSamples, flags, rays && mean, &run)) return rc;
+  if (!run) return PT_OK;
+  CK(hipSetDevice(ctx->cfg.device_id));
+  const size_t nRays = (flags & PT_RADIANCE_RAYS_PER_SAMPLE) ? (size_t)nSamples * (size_t)n : (size_t)n;
+  if (int rc = ensureStage(ctx, (size_t)n * 8 + nRays * 6)) return rc;
+  float* dMean = ctx->d_queryStage;  // first: 16-byte aligned
+  float* dMoments = dMean + (size_t)n * 4;
+  int* dIds = reinterpret_cast<int*>(dMoments + (size_t)n * 2);
+  float* dRays = dMoments + (size_t)n * 4;
+  CK(hipMemcpyAsync(dRays, rays, nRays * 6 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (ids) CK(hipMemcpyAsync(dIds, ids, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  if (firstSample != 0u) {
+    CK(hipMemcpyAsync(dMean, mean, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (moments) CK(hipMemcpyAsync(dMoments, moments, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (int rc = radianceMeanOne(ctx, dRays, ids ? dIds : nullptr, n, firstSample, nSamples, flags, dMean,
+                               moments ? dMoments : nullptr))
+    return rc;
+  CK(hipMemcpyAsync(mean, dMean, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (moments) CK(hipMemcpyAsync(moments, dMoments, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   CK(hipStreamSynchronize(ctx->stream));
   return PT_OK;
 }

@@ -41,6 +41,7 @@ FLAG_MOMENTS = 0x1000
 FLAG_ADAPTIVE = 0x2000
 FLAG_SHARE_MOMENTS = 0x4000
 ENV_RGBE = 0x1  # pt_update_env's PT_ENV_RGBE (update_env(rgbe=True))
+RADIANCE_RAYS_PER_SAMPLE = 0x1  # pt_radiance_mean's PT_RADIANCE_RAYS_PER_SAMPLE (radiance_mean(per_sample_rays=True))
 PACK_STATS_F = 5 # f32 per packed slot of pack_owned_stats: r, g, b, m1, m2
 GATHER = {"auto": 0, "copy": 1, "rccl": 2}
 
@@ -526,6 +527,78 @@ class Renderer:
         self._ck(self._lib.pt_radiance(self._h, _fp(r), None if i is None else i.ctypes.data_as(_native.c_int_p), n,
                                        int(sample_index) & 0xFFFFFFFF, _fp(out)), "pt_radiance")
         return out
+
+    @staticmethod
+    def _mean_samples(what, first_sample, n_samples):
+        first_sample, n_samples = int(first_sample), int(n_samples)
+        if n_samples < 1:
+            raise ValueError(f"{what}: n_samples must be >= 1")
+        if first_sample < 0 or first_sample + n_samples > 0xFFFFFFFF:
+            raise ValueError(f"{what}: samples {first_sample} .. {first_sample + n_samples - 1} leave the 32-bit sample index")
+        return first_sample, n_samples
+
+    def radiance_mean_device(self, rays, ids=None, first_sample: int = 0, n_samples: int = 1, per_sample_rays: bool = False,
+                             mean=None, moments=None, n=None):
+        """n_samples samples of this context's integrator along each ray, folded on the GPU into a running
+        mean (pt_radiance_mean_device): sample j is radiance_device's rgb for sample index first_sample + j,
+        folded in sample order with the frames' weights 1 / (s + 1) and the frames' floats, so a picture goes
+        on across calls as frames do across launches. first_sample 0 starts from zero (mean and moments are
+        not read); otherwise they are read and must be given. mean[k] = (r, g, b, t of the last sample's ray).
+        moments: None -- none kept; True -- allocated (first_sample 0 only); or given -- (n x 2 float32) the
+        running means of the sample luminance and its square, a FLAG_MOMENTS context's plane.
+        per_sample_rays: rays is (n_samples x n x 6), sample j's ray k at [j, k] (a caller's own jitter);
+        otherwise (n x 6), and the ray's closest hit is searched once for all its samples.
+        rays, ids (n x 2 int32 or None), mean (n x 4 float32) and moments are torch tensors or raw device
+        pointers (ints, with n) as in radiance_device; mean not given is allocated with tensor rays.
+        Asynchronous, in stream order on the context's stream. Returns (mean, moments)."""
+        what = "radiance_mean_device"
+        first_sample, n_samples = self._mean_samples(what, first_sample, n_samples)
+        per = 6 * n_samples if per_sample_rays else 6
+        specs = [("rays", rays, "float32", per, True), ("ids", ids, "int32", 2, False)]
+        n, _, torch = self._query_args(what, n, specs)
+        if (mean is None or moments is True) and first_sample:
+            raise ValueError(f"{what}: first_sample {first_sample} continues a mean (and moments): give them")
+        if torch is not None and torch.is_tensor(rays):
+            if mean is None:
+                mean = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+            if moments is True:
+                moments = torch.empty((n, 2), dtype=torch.float32, device=rays.device)
+        if moments is True:
+            raise ValueError(f"{what}: moments=True needs tensor rays; give a pointer")
+        specs += [("mean", mean, "float32", 4, True), ("moments", moments, "float32", 2, False)]
+        n, p, _ = self._query_args(what, n, specs)
+        flags = RADIANCE_RAYS_PER_SAMPLE if per_sample_rays else 0
+        self._ck(self._lib.pt_radiance_mean_device(self._h, p[0], p[1], n, first_sample, n_samples, flags, p[2], p[3]),
+                 "pt_radiance_mean_device")
+        return mean, moments
+
+    def radiance_mean(self, rays: np.ndarray, ids=None, first_sample: int = 0, n_samples: int = 1,
+                      per_sample_rays: bool = False, mean=None, moments=None):
+        """radiance_mean_device on host arrays (pt_radiance_mean). rays (n, 6) or, per_sample_rays,
+        (n_samples, n, 6). mean (n, 4) and moments (n, 2) are float32 arrays to go on from (required when
+        first_sample is not 0; updated copies are returned), moments None for none or True for new ones.
+        Synchronous. Returns (mean, moments)."""
+        what = "radiance_mean"
+        first_sample, n_samples = self._mean_samples(what, first_sample, n_samples)
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        if per_sample_rays and r.shape[0] % n_samples:
+            raise ValueError(f"{what}: {r.shape[0]} rays are no multiple of {n_samples} samples")
+        n = r.shape[0] // n_samples if per_sample_rays else r.shape[0]
+        i = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(-1, 2)
+        if i is not None and i.shape[0] != n:
+            raise ValueError(f"ids has {i.shape[0]} entries for {n} rays")
+        if first_sample and (mean is None or moments is True):
+            raise ValueError(f"{what}: first_sample {first_sample} continues a mean (and moments): give them")
+        mean = np.zeros((n, 4), np.float32) if mean is None else np.array(mean, np.float32).reshape(-1, 4)
+        if moments is not None:
+            moments = np.zeros((n, 2), np.float32) if moments is True else np.array(moments, np.float32).reshape(-1, 2)
+        if mean.shape[0] != n or (moments is not None and moments.shape[0] != n):
+            raise ValueError(f"{what}: mean and moments must have {n} rows")
+        flags = RADIANCE_RAYS_PER_SAMPLE if per_sample_rays else 0
+        self._ck(self._lib.pt_radiance_mean(self._h, _fp(r), None if i is None else i.ctypes.data_as(_native.c_int_p), n,
+                                            first_sample, n_samples, flags, _fp(mean),
+                                            None if moments is None else _fp(moments)), "pt_radiance_mean")
+        return mean, moments
 
     def build_bvh_device(self, tris: np.ndarray, leaf_size: int = 4):
         """pt_build_bvh_device: the GPU binned-SAH tree over tris (n x 36 f32) in the reference's

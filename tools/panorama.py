@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """An equirectangular panorama of a config from a point, path-traced through the radiance query.
 
-    python tools/panorama.py --config c2 --frames N --out pano.png [--size 1024x512] [--eye X Y Z] [--gamma 2.2]
+    python tools/panorama.py --config c2 --frames N --out pano.png [--size 1024x512] [--eye X Y Z] [--gamma 2.2] [--batch B]
 
 A camera the frame kernels do not have: torch builds one ray per pixel of a W x H equirectangular image
 from the eye (default: the config's camera position), column = azimuth over 360 degrees, row = elevation
@@ -11,6 +11,9 @@ seeded as (k & 4095, k >> 12), distinct for W * H < 2^23), and the N samples are
 mean with the frames' weights 1 / (i + 1) in torch. The mean is tone-mapped as pass3 does (limit 1.5)
 and written as an 8-bit PNG. Rays, samples and mean stay on the GPU, on the stream the renderer was
 handed (pt_set_stream); one image leaves it at the end.
+With --batch B the jittered rays of B samples are built at once and pt_radiance_mean_device folds them on
+the GPU, one call per B samples and no fold in torch: the mean goes on from call to call in the call's own
+buffer, with the frames' weights and floats.
 """
 from __future__ import annotations
 
@@ -43,10 +46,18 @@ def panorama_rays(w: int, h: int, eye, sample: int, device="cuda"):
     return torch.cat([o, d], dim=2).reshape(-1, 6).contiguous()
 
 
-def render(r, w: int, h: int, eye, frames: int, stream):
-    """-> the running mean of `frames` samples, (h, w, 3) float32 tensor, row 0 = up. r renders on `stream`."""
+def render(r, w: int, h: int, eye, frames: int, stream, batch: int = 0):
+    """-> the running mean of `frames` samples, (h, w, 3) float32 tensor, row 0 = up. r renders on `stream`.
+    batch > 0: that many samples per pt_radiance_mean_device call."""
     import torch
     with torch.cuda.stream(stream):
+        if batch > 0:
+            mean4 = torch.empty((h * w, 4), dtype=torch.float32, device="cuda")
+            for i in range(0, frames, batch):
+                b = min(batch, frames - i)
+                rays = torch.stack([panorama_rays(w, h, eye, i + j) for j in range(b)])
+                r.radiance_mean_device(rays, None, i, b, per_sample_rays=True, mean=mean4)
+            return mean4[:, 0:3].reshape(h, w, 3)
         mean = torch.zeros((h * w, 3), dtype=torch.float32, device="cuda")
         out = torch.empty((h * w, 4), dtype=torch.float32, device="cuda")
         for i in range(frames):
@@ -70,6 +81,7 @@ def main():
     ap.add_argument("--eye", type=float, nargs=3, default=None)
     ap.add_argument("--gamma", type=float, default=2.2)
     ap.add_argument("--out", default="pano.png")
+    ap.add_argument("--batch", type=int, default=0, help="samples per pt_radiance_mean_device call (0: one pt_radiance_device call per sample, folded in torch)")
     a = ap.parse_args()
     w, h = (int(x) for x in a.size.lower().split("x"))
     if w * h >= 1 << 23:
@@ -87,10 +99,10 @@ def main():
         r.upload_scene(tris, nodes)
         r.upload_env(hdr)
         r.set_stream(stream.cuda_stream)
-        render(r, w, h, eye, 1, stream)  # first use: the query's own resources, torch's kernels
+        render(r, w, h, eye, 1, stream, a.batch)  # first use: the query's own resources, torch's kernels
         stream.synchronize()
         t0 = time.perf_counter()
-        mean = render(r, w, h, eye, a.frames, stream)
+        mean = render(r, w, h, eye, a.frames, stream, a.batch)
         with torch.cuda.stream(stream):  # behind the last sample's fold, not on torch's default stream
             img = tonemap(mean)
         stream.synchronize()
@@ -99,7 +111,7 @@ def main():
         r.set_stream(None)
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     write_png(a.out, img, gamma=a.gamma, flip_rows=False)
-    print(json.dumps({"config": a.config, "width": w, "height": h, "frames": a.frames, "seconds": round(seconds, 4),
+    print(json.dumps({"config": a.config, "width": w, "height": h, "frames": a.frames, "batch": a.batch, "seconds": round(seconds, 4),
                       "ms_per_frame": round(1e3 * seconds / a.frames, 4),
                       "mpaths_per_s": round(w * h * a.frames / seconds / 1e6, 1), "mean": float(img.mean()),
                       "finite": bool((img == img).all()), "out": a.out}))

@@ -13,6 +13,18 @@ Per config, at its own size (1920 x 1080) and camera, every ray one sample of it
   camera_rays      the device time of pt_camera_rays_device
 The sides alternate round by round in one process; every round's figure is kept. Before timing, the radiance
 of the camera rays is checked against the frame of the same sample, bit for bit. One JSON line per config.
+
+    python tools/radiance_time.py [c2 c3 c4] --samples 16 [--rounds 5] [--out out/radiance_mean.json]
+
+With --samples S the many-sample call instead (pt_radiance_mean_device, mean and moments), device events
+around each side, per config and for both forms of its rays:
+  singles_fixed       S pt_radiance_device calls, sample indices 0 .. S-1, on the camera rays of sample 0: the
+                      yardstick (what a caller's loop costs on the device before it folds anything)
+  mean_fixed          one pt_radiance_mean_device call of S samples on those rays
+  singles_per_sample  S pt_radiance_device calls, call j on the camera rays of sample j
+  mean_per_sample     one call with PT_RADIANCE_RAYS_PER_SAMPLE on the S x n rays
+Before timing, each batched result is checked on bits against the single calls folded in torch with the
+frames' expressions (one kernel per operation: nothing is fused).
 """
 from __future__ import annotations
 
@@ -34,12 +46,94 @@ def spread(xs, nd=4):
             "rounds": [round(x, nd) for x in xs]}
 
 
+def mean_config(name, S, rounds, stream):
+    """--samples: one config's result line (a dict)"""
+    import torch
+
+    from opengl_ray_tracing_amd import Renderer, orbit_camera, scenes
+    cfg, tris, nodes, hdr = scenes.build_config(name)
+    eye, rot = orbit_camera(*cfg.camera)
+    w, h = cfg.width, cfg.height
+    n = w * h
+    with Renderer(w, h, cfg.integrator, max_bounce=cfg.max_bounce) as r:
+        r.upload_scene(tris, nodes)
+        r.upload_env(hdr)
+        r.set_stream(stream.cuda_stream)
+        with torch.cuda.stream(stream):
+            per = torch.empty((S, n, 6), dtype=torch.float32, device="cuda:0")
+            ids = torch.empty((n, 2), dtype=torch.int32, device="cuda:0")
+            for j in range(S):
+                r.camera_rays_device(eye, rot, j, per[j], ids)
+            fixed = per[0]
+            out = torch.empty((n, 4), dtype=torch.float32, device="cuda:0")
+            mean = torch.empty((n, 4), dtype=torch.float32, device="cuda:0")
+            mom = torch.empty((n, 2), dtype=torch.float32, device="cuda:0")
+
+            def singles(rays_of):
+                for j in range(S):
+                    r.radiance_device(rays_of(j), ids, j, out)
+
+            sides = {"singles_fixed": lambda: singles(lambda j: fixed),
+                     "mean_fixed": lambda: r.radiance_mean_device(fixed, ids, 0, S, False, mean, mom),
+                     "singles_per_sample": lambda: singles(lambda j: per[j]),
+                     "mean_per_sample": lambda: r.radiance_mean_device(per, ids, 0, S, True, mean, mom)}
+            # the batched results against the folded single calls, on bits
+            equal = {}
+            for form, rays_of in (("fixed", lambda j: fixed), ("per_sample", lambda j: per[j])):
+                a3 = torch.zeros((n, 3), dtype=torch.float32, device="cuda:0")
+                m1 = torch.zeros(n, dtype=torch.float32, device="cuda:0")
+                m2 = torch.zeros(n, dtype=torch.float32, device="cuda:0")
+                for j in range(S):
+                    r.radiance_device(rays_of(j), ids, j, out)
+                    wt = torch.tensor(1.0, dtype=torch.float32, device="cuda:0") / float(j + 1)
+                    c = out[:, 0:3]
+                    a3 = a3 * (1.0 - wt) + c * wt
+                    lum = (c[:, 0] * 0.3 + c[:, 1] * 0.6) + c[:, 2] * 0.1
+                    m1 = m1 * (1.0 - wt) + lum * wt
+                    m2 = m2 * (1.0 - wt) + (lum * lum) * wt
+                sides[f"mean_{form}"]()
+                want = torch.cat([a3, out[:, 3:4], m1[:, None], m2[:, None]], dim=1)
+                got = torch.cat([mean, mom], dim=1)
+                equal[form] = bool(((got.view(torch.int32) == want.view(torch.int32)) | (got.isnan() & want.isnan())).all())
+            stream.synchronize()
+            if not all(equal.values()):
+                raise RuntimeError(f"{name}: the batched call is not the folded single calls: {equal}")
+
+            def events(fn):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                fn()
+                e1.record(stream)
+                e1.synchronize()
+                return e0.elapsed_time(e1)
+
+            for fn in sides.values():  # warm
+                fn()
+            stream.synchronize()
+            ms = {k: [] for k in sides}
+            for i in range(rounds):
+                order = list(sides) if i % 2 == 0 else list(sides)[::-1]
+                for k in order:
+                    ms[k].append(events(sides[k]))
+            hit_share = round(float((mean[:, 3] < 2147483648.0).float().mean()), 4)
+        r.set_stream(None)
+    res = {"config": name, "width": w, "height": h, "rays": n, "integrator": cfg.integrator, "max_bounce": cfg.max_bounce,
+           "samples": S, "rounds": rounds, "hit_share": hit_share, "equals_folded_singles_bits": equal}
+    for k, xs in ms.items():
+        res[f"{k}_ms"] = spread(xs, 3)
+    for form in ("fixed", "per_sample"):
+        res[f"speedup_{form}"] = round(statistics.median(ms[f"singles_{form}"]) / statistics.median(ms[f"mean_{form}"]), 3)
+        res[f"mean_{form}_ms_per_sample"] = round(statistics.median(ms[f"mean_{form}"]) / S, 4)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("configs", nargs="*", default=["c2", "c3", "c4"])
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--samples", type=int, default=0, help="time the many-sample call of this many samples instead")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
@@ -53,6 +147,12 @@ def main():
         raise RuntimeError("radiance_time: no GPU visible")
     stream = torch.cuda.Stream()
     lines = []
+    if a.samples > 0:
+        for name in a.configs:
+            line = json.dumps(mean_config(name, a.samples, a.rounds, stream))
+            print(line, flush=True)
+            lines.append(line)
+        a.configs = []
     for name in a.configs:
         cfg, tris, nodes, hdr = scenes.build_config(name)
         eye, rot = orbit_camera(*cfg.camera)
