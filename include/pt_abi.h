@@ -405,6 +405,18 @@ int pt_render_frames_async(pt_ctx* ctx, const float eye[3], const float cameraRo
 int pt_build_bvh_device(pt_ctx* ctx, const float* tris, int nTriangles, int leafSize, float* nodes_out,
                         int max_nodes, int* nNodes_out, int* order_out);
 
+/* The origin domain. Every result is the reference traversal's whichever tree is walked, for every ray
+ * origin and every eye. The runtime's own tree is walked only from origins in its domain:
+ *     max(|o.x|, |o.y|, |o.z|) <= 32 x the scene scale,
+ * the scene scale being the largest coordinate magnitude of the uploaded (or last updated) triangles' vertices
+ * (csrc/pt_scene_prep.cpp prepareAccel derives the 32 from the widening of that tree's boxes). Outside it,
+ * and for an origin with a NaN or an infinite coordinate, the results are the same ones, found through the
+ * uploaded tree alone: per ray in pt_trace_closest, the ranged and occlusion queries, pt_radiance* and
+ * pt_radiance_mean* (a path's bounce rays start on the scene and are in the domain), per launch for the eye
+ * of pt_render_frame* and pt_render_guides -- pt_frame_stats.runtime_tree then reads 0 for that frame, and
+ * what the launch policy measured with such an eye is measured again at the next restart. Only the time
+ * differs: the uploaded tree's walk is the slower one on most scenes. */
+
 /* Batch hitBVH (pass1.fsh:335-382; BVH/main.cpp:571 debug-ray query). rays =
  * n x 6 f32 (origin, direction); miss -> t = 2147483648.f, tri = -1. */
 int pt_trace_closest(pt_ctx* ctx, const float* rays, int n, float* t_out, int* tri_out);

@@ -80,7 +80,7 @@ SOURCES = {
     "pt_queries.o": ("cxx", CSRC / "pt_queries.cpp", _HOST),
     "pt_accum.o": ("cxx", CSRC / "pt_accum.cpp", [*_HOST, CSRC / "pt_plan.h"]),
     "pt_group.o": ("cxx", CSRC / "pt_group.cpp", _HOST),
-    "pt_post.o": ("cxx", CSRC / "pt_post.cpp", _HOST),
+    "pt_post.o": ("cxx", CSRC / "pt_post.cpp", [*_HOST, CSRC / "pt_plan.h"]),
     "pt_rccl.o": ("cxx", CSRC / "pt_rccl.cpp", [CSRC / "pt_rccl.h"]),
     "scene.o": ("cxx", CSRC / "scene.cpp", [INCLUDE / "pt_scene.h", CSRC / "pt_accel.h", CSRC / "pt_introsort.h"]),
 }

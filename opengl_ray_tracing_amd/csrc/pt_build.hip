@@ -36,6 +36,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "pt_kernels.h"
@@ -835,15 +836,20 @@ hipError_t buildAccelDevice(const float4* geo, int nTri, int leafSize, float inf
 }
 
 hipError_t collapseWide4Device(const BuildNode* nodes, int nNodes, int leafSize, float inflate, float inflateRelAbs,
-                               float4** out, int* rootRef, int* nDev, int* depth, hipStream_t s) {
+                               float4** out, int* rootRef, int* nDev, int* depth, float* scale, hipStream_t s) {
   *out = nullptr;
   *nDev = 0;
   *depth = 1;
+  *scale = 0.0f;
   if (nNodes < 1) return hipErrorInvalidValue;
   BuildNode root;
   hipError_t e = hipMemcpyAsync(&root, nodes, sizeof(root), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) return e;
+  // the scale encodeKernel and w4EncodeKernel widen by (the same maximum, which no order of evaluation changes)
+  *scale = std::max(std::max(std::max(std::fabs(root.lo.x), std::fabs(root.hi.x)),
+                             std::max(std::fabs(root.lo.y), std::fabs(root.hi.y))),
+                    std::max(std::fabs(root.lo.z), std::fabs(root.hi.z)));
   int rootCount;
   std::memcpy(&rootCount, &root.hi.w, 4);
   if (rootCount <= leafSize) {  // one leaf: no wide node

@@ -161,6 +161,17 @@ struct SceneView {
   const float4* leafBox;
 };
 
+// The origin domain of the runtime tree (derived where its boxes' widening is set: pt_scene_prep.cpp
+// prepareAccel): a ray is in domain iff every |origin coordinate| <= PT_ORIGIN_K x the scene scale, the
+// largest coordinate magnitude of the tree's root box. Out of it -- a NaN or an infinite coordinate fails
+// the comparisons too -- the fused slab tests no longer hold their rounding below the widening, so the ray
+// never enters the runtime tree: it takes the reference-order walk of the uploaded tree, which is exact
+// for every origin. limit = PT_ORIGIN_K x scale, computed once per runtime tree (pt_ctx::originLimit).
+constexpr float PT_ORIGIN_K = 32.0f;
+__host__ __device__ inline bool originInDomain(float ox, float oy, float oz, float limit) {
+  return fabsf(ox) <= limit && fabsf(oy) <= limit && fabsf(oz) <= limit;
+}
+
 // HDR environment (hdrMap + hdrCache textures, IS main.cpp:843-853), float4 texels
 // Render layout: one 16-byte texel serves hdrColor and hdrPdf of a direction
 // together (every MIS lookup pairs them), so a miss costs one line, not two.
@@ -301,6 +312,7 @@ struct QueryParams {
   uint8_t* occ;        // occluded: n bytes, 0 / 1
   int* ovf;            // the queries' own traversal stack overflow (per thread ovfDepth ints), may be null
   int ovfDepth;
+  float originLimit;   // the runtime tree's origin domain (originInDomain): rays from beyond it walk the uploaded tree
 };
 
 // Radiance along caller-supplied rays (pt_radiance.hip radianceKernel; pt_abi.h pt_radiance_device): one
@@ -316,6 +328,7 @@ struct RadianceParams {
   float4* out;         // n x (r, g, b, t); a miss (sky, PT_INF)
   int* ovf;            // the queries' traversal stack overflow (per thread ovfDepth ints), may be null
   int ovfDepth;
+  float originLimit;   // as QueryParams': the caller's ray alone is checked, a bounce starts on the scene
 };
 // waves per SIMD the radiance kernel is compiled for, per integrator
 #ifndef PT_RADIANCE_WAVES_LAMBERT
@@ -345,6 +358,7 @@ struct RadianceMeanParams {
   float2* moments;     // n x (m1, m2), may be null; read when firstSample != 0
   int* ovf;            // the queries' traversal stack overflow (per thread ovfDepth ints), may be null
   int ovfDepth;
+  float originLimit;   // as RadianceParams'
 };
 hipError_t launchRadianceMean(const RadianceMeanParams& p, int integrator, int grid, hipStream_t s, bool cull);
 // The frame kernels' camera rays of one sample (pt_frame.h cameraRay) for every pixel of a width x height
@@ -450,8 +464,9 @@ hipError_t buildAccelDevice(const float4* geo, int nTri, int leafSize, float inf
 void freeAccelBuild(AccelBuild& a);
 // the build nodes collapsed to 4-wide records (SceneView::fbvh4, pt_scene_prep.cpp encodeWide4's
 // layout, ids and widening) on the device; *out allocated here (W4_F4 float4 per wide node)
+// *scale: the scene scale the widening used, the root box's largest coordinate magnitude
 hipError_t collapseWide4Device(const BuildNode* nodes, int nNodes, int leafSize, float inflate, float inflateRelAbs,
-                               float4** out, int* rootRef, int* nDev, int* depth, hipStream_t s);
+                               float4** out, int* rootRef, int* nDev, int* depth, float* scale, hipStream_t s);
 
 // New vertex positions in place (pt_refit.hip, pt_abi.h pt_update_geometry): the geometry, pair and
 // shading records rewritten from the caller's vertex records, the uploaded tree's boxes refitted

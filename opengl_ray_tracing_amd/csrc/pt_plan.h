@@ -137,12 +137,22 @@ struct FramePlan {
   bool piped;      // the launch runs on a slot of the pipeline (a colour buffer, a running-mean update launch)
 };
 
+// The eye of a frame or guide launch against the origin domain of the runtime tree in place (pt_kernels.h
+// originInDomain; pt_scene_prep.cpp prepareAccel derives it). A launch whose eye is outside runs without
+// that tree -- SceneView::fast 0, no 4-wide walk, no camera-ray bins (their winners are checked by the
+// same margin argument) -- so every ray of it takes the reference-order walk of the uploaded tree, and
+// pt_frame_stats.runtime_tree reads 0 for it. The paths' bounce rays start on the scene, always in domain,
+// but one launch walks one tree.
+static inline bool eyeInDomain(const pt_ctx* ctx, const float eye[3]) {
+  return originInDomain(eye[0], eye[1], eye[2], ctx->originLimit);
+}
+
 // a launch of this context is one of the frames in flight
 static inline bool pipedFrames(const pt_ctx* ctx) { return ctx->pipe && !(ctx->cfg.flags & PT_FLAG_COUNT_FETCHES); }
 
 // solo: the launch is issued while no other is in flight, on the caller's stream; want: the frames
-// the caller asked for
-static inline FramePlan planFrame(const pt_ctx* ctx, bool solo, int want) {
+// the caller asked for; eyeIn: the launch's eye is in the runtime tree's origin domain (eyeInDomain)
+static inline FramePlan planFrame(const pt_ctx* ctx, bool solo, int want, bool eyeIn = true) {
   const pt_config& c = ctx->cfg;
   FramePlan f;
   f.count = (c.flags & PT_FLAG_COUNT_FETCHES) != 0;
@@ -170,7 +180,7 @@ static inline FramePlan planFrame(const pt_ctx* ctx, bool solo, int want) {
   // the more-waves variant of either kernel (the regen kernel's with its 4-wide walk, dynamic ray
   // fetch and camera-ray pass; on small trees with the whole tree in LDS)
   f.wide = f.wideScene || (f.regen && f.regenAll);
-  f.walk4 = f.wide && ctx->fast4Ready && !(c.flags & PT_FLAG_REFERENCE_TREE);
+  f.walk4 = f.wide && ctx->fast4Ready && eyeIn && !(c.flags & PT_FLAG_REFERENCE_TREE);
   f.rowTable = rowTable(ctx, f.regen);
   f.envNt = largeScene(ctx) ? 1 : 0;
   const int group = std::max(1, PT_TILE_GROUP);
@@ -183,6 +193,6 @@ static inline FramePlan planFrame(const pt_ctx* ctx, bool solo, int want) {
   // of a PT_FLAG_ADAPTIVE context runs behind it
   f.pass = (c.flags & (PT_FLAG_PRIMARY_PASS | PT_FLAG_ADAPTIVE)) || (f.regen && f.wide);
   // camera-ray bins need the reference facts refReachable checks a bin's winner against
-  f.bins = PT_BINS && !f.count && ctx->fastReady && !(c.flags & PT_FLAG_NO_BINS) && (!f.regen || f.pass);
+  f.bins = PT_BINS && !f.count && ctx->fastReady && eyeIn && !(c.flags & PT_FLAG_NO_BINS) && (!f.regen || f.pass);
   return f;
 }

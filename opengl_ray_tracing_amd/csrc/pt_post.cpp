@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "pt_plan.h"
 #include "pt_runtime.h"
 
 // an H x W plane of T the context allocates when it is first needed
@@ -138,8 +139,12 @@ int pt_render_guides(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
   }
   GuideParams p;
   p.scene = sceneView(ctx);
-  // the hit search of pt_trace_closest: the runtime's own tree, results reference-exact
-  p.scene.fast = ctx->fastReady && !(ctx->cfg.flags & (PT_FLAG_REFERENCE_TREE | PT_FLAG_COUNT_FETCHES)) ? 1 : 0;
+  // the hit search of pt_trace_closest: the runtime's own tree, results reference-exact -- for an eye in
+  // its origin domain (pt_plan.h eyeInDomain), else the uploaded tree alone
+  p.scene.fast = ctx->fastReady && eyeInDomain(ctx, eye) &&
+                         !(ctx->cfg.flags & (PT_FLAG_REFERENCE_TREE | PT_FLAG_COUNT_FETCHES))
+                     ? 1
+                     : 0;
   p.width = W;
   p.height = H;
   std::memcpy(p.eye, eye, sizeof(p.eye));

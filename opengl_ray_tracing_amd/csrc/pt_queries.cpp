@@ -52,7 +52,8 @@ static int endQuery(pt_ctx* ctx) {
   ctx->queryIssued = true;
   return PT_OK;
 }
-// the scene as a query walks it: the runtime's own tree, results reference-exact (pt_trace.h refReachable)
+// the scene as a query walks it: the runtime's own tree, results reference-exact (pt_trace.h refReachable);
+// the kernels keep each ray from outside the tree's origin domain off it (QueryParams::originLimit)
 static SceneView queryScene(const pt_ctx* ctx) {
   SceneView s = sceneView(ctx);
   s.fast = ctx->fastReady && !(ctx->cfg.flags & (PT_FLAG_REFERENCE_TREE | PT_FLAG_COUNT_FETCHES)) ? 1 : 0;
@@ -77,6 +78,7 @@ static int queryOne(pt_ctx* ctx, const void* d_rays, const void* d_tmax, int n, 
   p.occ = static_cast<uint8_t*>(d_occ);
   p.ovf = ovfDepth ? ctx->d_queryOvf : nullptr;
   p.ovfDepth = ovfDepth;
+  p.originLimit = ctx->originLimit;
   CK(launchQuery(p, queryGrid(ctx, n), ctx->stream, d_occ != nullptr, queryCull(ctx)));
   return endQuery(ctx);
 }
@@ -178,6 +180,7 @@ static int radianceOne(pt_ctx* ctx, const void* d_rays, const void* d_ids, int n
   p.out = static_cast<float4*>(d_out);
   p.ovf = ovfDepth ? ctx->d_queryOvf : nullptr;
   p.ovfDepth = ovfDepth;
+  p.originLimit = ctx->originLimit;
   CK(launchRadiance(p, ctx->cfg.integrator, queryGrid(ctx, n), ctx->stream, queryCull(ctx)));
   return endQuery(ctx);
 }
@@ -226,6 +229,7 @@ static int radianceMeanOne(pt_ctx* ctx, const void* d_rays, const void* d_ids, i
   p.moments = static_cast<float2*>(d_moments);
   p.ovf = ovfDepth ? ctx->d_queryOvf : nullptr;
   p.ovfDepth = ovfDepth;
+  p.originLimit = ctx->originLimit;
   CK(launchRadianceMean(p, ctx->cfg.integrator, queryGrid(ctx, n), ctx->stream, queryCull(ctx)));
   return endQuery(ctx);
 }

@@ -6,7 +6,8 @@
 // walk whose closest-hit bound starts at b gives exactly that -- a triangle at or beyond b cannot win,
 // and among the others the same least-t, first-in-order one does -- so the kernel runs the frames'
 // hit search (Tracer) with the walks' BOUNDED switch: the runtime's tree checked against the
-// reference's (refReachable), or the uploaded tree alone. A ray with !(b > 0.0005f) -- hitTriangle's
+// reference's (refReachable), or the uploaded tree alone -- per ray for an origin outside the runtime
+// tree's origin domain (Tracer's GUARD; pt_kernels.h originInDomain). A ray with !(b > 0.0005f) -- hitTriangle's
 // own lower bound, and a NaN -- is a miss without a walk. Nothing is counted: pt_frame_stats stays as it was.
 //
 // One lane per ray in a grid-stride loop. A loop that refills a wave's finished lanes with
@@ -53,7 +54,8 @@ __global__ __launch_bounds__(BLOCK) void queryKernel(QueryParams p) {
   const size_t gtid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
   Counters C = {0, 0, 0, 0, 0};
   const SceneView S = noTopView(p.scene);
-  Tracer<CULL, false> tr{S, st, C, nullptr};
+  // (GUARD: a ray from outside the runtime tree's origin domain walks the uploaded tree alone)
+  Tracer<CULL, false, true> tr{S, st, C, nullptr, p.originLimit};
   for (size_t k = gtid; k < (size_t)p.n; k += (size_t)gridDim.x * BLOCK) {
     V3 o, d;
     float b;

@@ -36,7 +36,9 @@ __global__ __launch_bounds__(BLOCK, radianceWaves(INTEG)) void radianceKernel(Ra
   const size_t gtid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
   Counters C = {0, 0, 0, 0, 0};
   const SceneView S = noTopView(p.scene);  // no LDS copy of the top of the tree (as the ray queries, pt_query.hip)
-  Tracer<CULL, false> tr{S, st, C, nullptr};
+  // (GUARD: the caller's ray is checked against the runtime tree's origin domain, traceFrom; the path's own
+  // rays start on the scene)
+  Tracer<CULL, false, true> tr{S, st, C, nullptr, p.originLimit};
   for (size_t k = gtid; k < (size_t)p.n; k += (size_t)gridDim.x * BLOCK) {
     const float* r = p.rays + 6 * k;
     const V3 o = v3(r[0], r[1], r[2]);
@@ -44,7 +46,7 @@ __global__ __launch_bounds__(BLOCK, radianceWaves(INTEG)) void radianceKernel(Ra
     const int px = p.ids ? p.ids[2 * k] : (int)(k & 4095);
     const int py = p.ids ? p.ids[2 * k + 1] : (int)(k >> 12);
     float t;
-    const int tri = tr.trace(o, d, t);
+    const int tri = tr.traceFrom(o, d, t);
     V3 color;
     if (tri < 0) {
       color = sampleHdr(p.env, d);

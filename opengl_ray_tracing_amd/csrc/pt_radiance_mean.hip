@@ -60,7 +60,7 @@ __global__ __launch_bounds__(BLOCK, radianceMeanWaves(INTEG)) void radianceMeanK
   const size_t gtid = (size_t)blockIdx.x * BLOCK + threadIdx.x;
   Counters C = {0, 0, 0, 0, 0};
   const SceneView S = noTopView(p.scene);  // as radianceKernel
-  Tracer<CULL, false> tr{S, st, C, nullptr};
+  Tracer<CULL, false, true> tr{S, st, C, nullptr, p.originLimit};  // as radianceKernel
   for (size_t k = gtid; k < (size_t)p.n; k += (size_t)gridDim.x * BLOCK) {
     const int px = p.ids ? p.ids[2 * k] : (int)(k & 4095);
     const int py = p.ids ? p.ids[2 * k + 1] : (int)(k >> 12);
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(BLOCK, radianceMeanWaves(INTEG)) void radianceMeanK
         const float* r = p.rays + 6 * ((p.perSample ? (size_t)j * (size_t)p.n : (size_t)0) + k);
         o = v3(r[0], r[1], r[2]);
         d = v3(r[3], r[4], r[5]);
-        tri = tr.trace(o, d, t);
+        tri = tr.traceFrom(o, d, t);
         if (tri < 0) {
           sky = sampleHdr(p.env, d);
           t = PT_INF;

@@ -201,11 +201,15 @@ __device__ __forceinline__ bool continueFromHit(const RenderParams& p, PathState
   V3 L = sampleBRDF(u, v, xi_3, V, N, hit.m);
   float NdotL = dot(N, L);
   s.haveB = false;
-  if (NdotL > 0.0f) {
+  // The reference's own predicates, negated: `NdotL <= 0` and `pdf <= 0` (IS:816) end the path, and
+  // both are false for a NaN, which therefore goes on and makes the sample a NaN -- as on c2 scaled by 2^10
+  // and more, where `NdotL > 0` and `pdf > 0` ended 276 of a 33 x 31 frame's paths at 0 instead
+  // (tests/test_gpu_scaled_scenes.py)
+  if (!(NdotL <= 0.0f)) {
     V3 f_r = brdfIso(V, N, L, hit.m);
     float pdf_brdf = brdfPdf(V, N, L, hit.m);
     // IS:816: pdf <= 0 ends the path (the reference traces the ray first and discards it)
-    if (pdf_brdf > 0.0f) {
+    if (!(pdf_brdf <= 0.0f)) {
       s.f_r = f_r;
       s.cosL = NdotL;
       s.pdfB = pdf_brdf;

@@ -700,7 +700,8 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
     at.colIdx = (int)(ctx->frameNo % (unsigned)at.nCol);
     at.solo = ctx->solo && pipeIdle(ctx, at.D);
   }
-  const FramePlan pl = planFrame(ctx, at.solo, want);
+  const bool eyeIn = eyeInDomain(ctx, eye);  // else this launch runs without the runtime tree (pt_plan.h)
+  const FramePlan pl = planFrame(ctx, at.solo, want, eyeIn);
   const hipStream_t S = at.S = piped && !at.solo ? ctx->slotStream[at.slot] : ctx->stream;
   LaunchShape g;
   if (int rc = gridFor(ctx, pl, at, &g)) return rc;
@@ -717,8 +718,11 @@ static int renderOne(pt_ctx* ctx, const float eye[3], const float cameraRotate[1
   // the tree (the runtime's own, checked against the uploaded one, unless asked
   // not to) and the split policy: probePolicy
   bool useFast = false;
+  // (a probe that times such a launch compares the uploaded tree with itself: its decisions are not kept
+  // past the next restart)
+  if (!eyeIn) ctx->policyKey++;
   const int splitPct = probePolicy(ctx, frameCounter, pl.ordered,
-                                   !pl.count && !pl.regen && ctx->fastReady && !(c.flags & PT_FLAG_REFERENCE_TREE),
+                                   !pl.count && !pl.regen && ctx->fastReady && eyeIn && !(c.flags & PT_FLAG_REFERENCE_TREE),
                                    &useFast, at.slot, S);
   // the large-scene regen kernel walks the 4-wide runtime tree (checked against the uploaded one)
   if (pl.regen && pl.walk4) useFast = true;

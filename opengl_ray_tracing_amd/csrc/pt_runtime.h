@@ -99,6 +99,9 @@ struct pt_ctx {
   float4* d_fbvh4 = nullptr;
   bool fast4Ready = false;
   int f4Root = REF_NONE, f4nDev = 0, f4Depth = 0;
+  // the origin domain of the runtime tree in place (pt_kernels.h originInDomain): PT_ORIGIN_K x the scale
+  // its boxes were widened by, set with every build of it (an upload's, a geometry update's rebuild)
+  float originLimit = 0.0f;
   // the last pt_upload_scene (pt_frame_stats upload_ms, accel_*)
   float uploadMs = 0.0f, accelMs = 0.0f;
   int accelDevice = -1, accelNodes = 0, accelDepth = 0;

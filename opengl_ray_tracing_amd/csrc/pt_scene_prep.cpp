@@ -343,12 +343,29 @@ static void prepareAccel(const float* tris, int nTri, const float* nodes, int nN
   h.accelNodes = (int)(an.size() / 12) - 1;
   h.accelRef = an;
 
-  // widened by 1e-5 of each box's own magnitude plus 3e-5 of the scene's: above
-  // the rounding of a slab test (~1.2e-7 x the origin-box distance) for ray origins
-  // up to ~100x the scene scale away, so a ray that hits a triangle enters every box around it
+  // Widened by 1e-5 of each box's own magnitude plus 3e-5 of the scene's, so that a ray that hits a
+  // triangle enters every box around it although the walks' slab tests are fused (pt_trace.h visitNodeF,
+  // traceRay4). THE ORIGIN DOMAIN -- the one derivation; pt_abi.h, DESIGN.md and pt_trace.h quote it.
+  // s = sceneScale, the largest coordinate magnitude of the scene (of the tree's root box: the device
+  // builder's encodeKernel takes it from there). One fused slab value of plane p, origin o, direction d on
+  // one axis is fl(fma(p, inv, noi)) with inv = fl(1/d) and noi = fl(-o inv): three roundings e1, e2, e3,
+  // each at most 2^-24 relative. Times d, in position space, it differs from the exact p - o by
+  //   (p - o) e1 + o e2 + (p - o) e3  <=  (2 |p - o| + |o|) 2^-24.
+  // With |o| <= K s and |p| <= s that is at most (3 K + 2) s 2^-24. An axis's two slab values move by that
+  // much; its box planes were moved outwards by at least 3e-5 s, so while the first stays below the second
+  // the computed slab of every axis still holds the exact ray's hit parameter, and the box passes.
+  // 4 (3 K + 2) 2^-24 <= 3e-5 -- a factor 4 between rounding and widening -- holds for K <= 41.3: K = 32,
+  // the largest power of two (K = 32: 5.8e-6 s against 3e-5 s, a factor 5.1; K = 64 would leave 2.6).
+  // That is pt_kernels.h PT_ORIGIN_K. A ray is in domain iff max(|o.x|, |o.y|, |o.z|) <= 32 s
+  // (originInDomain); any other ray, a NaN or infinite origin included, never enters this tree: the
+  // query kernels send it through the reference-order walk of the uploaded tree per ray, a frame or
+  // guide launch whose eye is outside runs without the runtime tree (pt_plan.h eyeInDomain).
+  // tests/test_accel_domain.py restates the fused test on this tree's dumped boxes: no hit is lost out
+  // to 16 K (the margin it pins), some are at 1e5 s and beyond.
   float sceneScale = 0.0f;
   for (int i = 0; i < nTri; i++)
     for (int k = 0; k < 9; k++) sceneScale = std::max(sceneScale, std::fabs(tris[(size_t)i * 36 + k]));
+  h.sceneScale = sceneScale;
   if (!encodeWideTree(an.data(), (int)(an.size() / 12), nTri, 1e-5f, h.fastTree, 3e-5f * sceneScale).empty()) return;
   buildPairs(h.geo, h.order.data(), nTri, h.fpairs);
   h.accelMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -53,6 +53,7 @@ struct SceneHost {
   bool deviceBuild = false;  // the tree itself is built on each device (pt_build.hip) by uploadScene
   float accelMs = 0.0f;      // host build time (deviceBuild false)
   int accelNodes = 0;
+  float sceneScale = 0.0f;   // host build: the scale its boxes' widening used (prepareAccel: the origin domain)
   std::vector<float> accelRef;  // host build: its nodes in the reference encoding (encodeWide4)
   WideTree fastTree;
   std::vector<float4> fpairs, leafBox;

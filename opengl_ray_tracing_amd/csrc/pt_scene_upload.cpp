@@ -53,6 +53,7 @@ static int invalidateScene(pt_ctx* ctx, int depth) {
   ctx->maxStack = depth + 1;
   ctx->fastReady = false;
   ctx->fast4Ready = false;
+  ctx->originLimit = 0.0f;
   ctx->accelDevice = -1;
   ctx->accelMs = 0.0f;
   ctx->accelNodes = ctx->accelDepth = 0;
@@ -73,9 +74,12 @@ static int buildRuntimeTree(pt_ctx* ctx, bool* built) {
     return PT_OK;
   }
   // the 4-wide collapse, on the device too (the large-scene regen kernel's and the megakernel's tree)
+  // ... which hands back the scale both encodings widened by, this build's root box's: the origin domain
+  // is the domain of the tree in place, after an update's rebuild as after an upload (never a stale scale)
   float4* w4 = nullptr;
+  float scale = 0.0f;
   e = collapseWide4Device(ab.nodes, ab.nNodes, PT_ACCEL_LEAF, 1e-5f, 3e-5f, &w4, &ctx->f4Root, &ctx->f4nDev,
-                          &ctx->f4Depth, ctx->stream);
+                          &ctx->f4Depth, &scale, ctx->stream);
   dfree(ab.nodes);
   if (e != hipSuccess) {
     freeAccelBuild(ab);
@@ -95,6 +99,7 @@ static int buildRuntimeTree(pt_ctx* ctx, bool* built) {
   ctx->accelMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   ctx->accelDevice = 1;
   ctx->accelNodes = ab.nNodes;
+  ctx->originLimit = PT_ORIGIN_K * scale;
   *built = true;
   return PT_OK;
 }
@@ -164,16 +169,17 @@ static int uploadScene(pt_ctx* ctx, const float* tris, const SceneHost& h) {
     ctx->accelMs = h.accelMs;
     ctx->accelDevice = 0;
     ctx->accelNodes = h.accelNodes;
+    ctx->originLimit = PT_ORIGIN_K * h.sceneScale;
   }
   ctx->accelDepth = ctx->fDepth;
   // the host-built tree's 4-wide collapse (the device build collapsed on the device above)
   if (!h.deviceBuild) {
     const std::vector<float>& an = h.accelRef;
     const int nn = (int)(an.size() / 12);
-    float scale = 0.0f;  // the scene's largest coordinate magnitude: the root box's
-    for (int k = 6; k < 12 && nn > 1; k++) scale = std::max(scale, std::fabs(an[12 + k]));
+    // (the scale of prepareAccel's widening: the root box bounds every vertex, so its largest coordinate
+    // magnitude is the triangles')
     std::vector<float4> w4;
-    encodeWide4(an.data(), nn, h.nTri, 1e-5f, 3e-5f * scale, w4, ctx->f4Root, ctx->f4nDev, ctx->f4Depth);
+    encodeWide4(an.data(), nn, h.nTri, 1e-5f, 3e-5f * h.sceneScale, w4, ctx->f4Root, ctx->f4nDev, ctx->f4Depth);
     if ((rc = upload(ctx, &ctx->d_fbvh4, w4))) return rc;
   }
   runtimeTreeReady(ctx);

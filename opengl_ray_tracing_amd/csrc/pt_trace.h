@@ -122,10 +122,13 @@ __device__ __forceinline__ void visitNode(const float4* nd, V3 o, V3 inv, NodeHi
 }
 // The runtime tree's slab tests fused: (plane - o) * inv as fma(plane, inv,
 // -o * inv), one packed FMA per axis and child pair instead of a subtract and a
-// multiply. The rounding differs from hitAABB's by about |o| * 2^-23 along each
-// axis, far inside the widening of the runtime tree's boxes (pt_scene_prep.cpp
-// prepareAccel), so the walk still meets every triangle the ray hits; results
-// found through it are checked against the reference tree as before. Never
+// multiply. Its three roundings move a slab value by at most (2 |p - o| + |o|) 2^-24
+// in position space, a factor 4 or more inside the widening of the runtime tree's
+// boxes for every origin of the origin domain, max |o| <= 32 x the scene scale
+// (pt_scene_prep.cpp prepareAccel has the derivation; pt_kernels.h originInDomain):
+// there the walk still meets every triangle the ray hits, and results found through
+// it are checked against the reference tree as before. Rays from outside the domain
+// never get here (Tracer's GUARD, pt_plan.h eyeInDomain). Never
 // used on the reference tree, whose d must be hitAABB's bit for bit.
 __device__ __forceinline__ void visitNodeF(const float4* nd, V3 inv, V3 noi, NodeHit& h) {
   const float4 q0 = nd[0], q1 = nd[1], q2 = nd[2], q3 = nd[3];
@@ -1080,7 +1083,15 @@ __device__ __forceinline__ void finishHit(const SceneView& S, int tri, V3 o, V3 
 // Closest-hit and shadow queries of one lane over the scene, with the reference's results whichever
 // tree is walked: the megakernel's integrators, the guide buffers (pt_guides.hip) and the ray
 // queries (pt_query.hip: pt_trace_closest and the ranged forms) share it.
-template <bool CULL, bool COUNT>
+//
+// GUARD (the ray queries and the radiance queries, whose rays are the caller's): a ray whose origin lies
+// outside the runtime tree's origin domain (pt_kernels.h originInDomain, originLimit) skips the 4-wide
+// walk and takes the reference-order walk a tie or an unreachable winner is retraced through, which is exact
+// for every origin (a branch of its own in front of walk: a second traceRay in those kernels). Checked for
+// the rays that come from the caller (traceFrom, traceBounded, occludedBounded); trace, occluded and traceK
+// carry the paths' bounce rays, which start on the scene. Without GUARD (the frame kernels and the guides,
+// whose one caller-given origin, the eye, is checked per launch on the host) nothing is compared.
+template <bool CULL, bool COUNT, bool GUARD = false>
 struct Tracer {
   const SceneView& S;
   Stack& st;
@@ -1088,8 +1099,11 @@ struct Tracer {
   // LDS copy of the top of the tree traversed first: the 4-wide tree's (!COUNT && S.fast) or the
   // uploaded tree's. Null = none, which requires S = noTopView(...).
   const float4* top;
+  float originLimit = 0.0f;  // GUARD alone reads it
   // closest hit: the triangle (-1 = miss) and its t
   __device__ __forceinline__ int trace(V3 o, V3 d, float& t) { return walk<false>(o, d, false, PT_INF, t); }
+  // ... of a ray the caller gave (GUARD: its origin may lie outside the runtime tree's domain)
+  __device__ __forceinline__ int traceFrom(V3 o, V3 d, float& t) { return walk<false, true>(o, d, false, PT_INF, t); }
   __device__ __forceinline__ bool closest(V3 o, V3 d, Hit& h) {
     float t;
     const int tri = trace(o, d, t);
@@ -1114,17 +1128,21 @@ struct Tracer {
   // costs a retrace) or an unreachable winner retraces in the reference order with the same bound; a miss
   // stands. An any-hit result stands when its triangle is reachable: the reference's closest t is then no
   // larger, so it is below b as well.
-  __device__ __forceinline__ int traceBounded(V3 o, V3 d, float b, float& t) { return walk<true>(o, d, false, b, t); }
+  __device__ __forceinline__ int traceBounded(V3 o, V3 d, float b, float& t) {
+    return walk<true, true>(o, d, false, b, t);
+  }
   __device__ __forceinline__ bool occludedBounded(V3 o, V3 d, float b) {
     float t;
-    // walk<true>(o, d, true, b, t) >= 0, written out with its results as constants: through walk the
+    // walk<true, true>(o, d, true, b, t) >= 0, written out with its results as constants: through walk the
     // compiler merges the occlusion query kernel's result stores (28 bytes less code)
     if (!COUNT && S.fast) {
-      bool tie = false;
-      const int tri = traceRay4<CULL, Stack, true, true>(S, o, d, t, st, C, true, top, &tie, b);
-      if (tri < 0) return false;
-      if (refReachable(S, tri, o, d, t)) return true;
-      C.rays--;
+      if (!GUARD || originInDomain(o.x, o.y, o.z, originLimit)) {
+        bool tie = false;
+        const int tri = traceRay4<CULL, Stack, true, true>(S, o, d, t, st, C, true, top, &tie, b);
+        if (tri < 0) return false;
+        if (refReachable(S, tri, o, d, t)) return true;
+        C.rays--;
+      }
       return traceRay<true, CULL, false, Stack, false, true>(S, o, d, t, st, C, false, nullptr, b) >= 0;
     }
     return traceRay<true, CULL, false, Stack, true, true>(S, o, d, t, st, C, false, top, b) >= 0;
@@ -1134,10 +1152,14 @@ struct Tracer {
   // Every query: with S.fast the 4-wide runtime tree, checked against the reference's (refReachable) -- a
   // tie (which an any-hit query ignores) or an unreachable winner retraces in the reference order,
   // without the LDS top, which is the other tree's, the same ray counted once; else the uploaded tree.
-  // anyhit / BOUNDED are literals at every call site but traceK's.
-  template <bool BOUNDED>
+  // anyhit / BOUNDED are literals at every call site but traceK's. FROM: the ray is the caller's (GUARD).
+  template <bool BOUNDED, bool FROM = false>
   __device__ __forceinline__ int walk(V3 o, V3 d, bool anyhit, float bound, float& t) {
     if (!COUNT && S.fast) {
+      // GUARD: a caller's ray from outside the domain takes the reference-order walk at once. A branch of
+      // its own, so that the in-domain path below stays the text the frame kernels share.
+      if (GUARD && FROM && !originInDomain(o.x, o.y, o.z, originLimit))
+        return traceRay<false, CULL, false, Stack, false, BOUNDED>(S, o, d, t, st, C, anyhit, nullptr, bound);
       bool tie = false;
       int tri = traceRay4<CULL, Stack, true, BOUNDED>(S, o, d, t, st, C, anyhit, top, &tie, bound);
       if ((tie && !anyhit) || (tri >= 0 && !refReachable(S, tri, o, d, t))) {

@@ -73,6 +73,10 @@ int main(int argc, char** argv) {
     dumpI("fastTree.ids", h.fastTree.ids);
     dumpInts("fastTree.shape", {h.fastTree.rootRef, h.fastTree.nDev, h.fastTree.depth});
     dumpF4("fpairs", h.fpairs);
+    // ... and the scale its boxes were widened by, which the origin domain is a multiple of (tests/test_accel_domain.py)
+    dump("sceneScale", "f4", &h.sceneScale, 1, 4);
+    // ... and its nodes before the widening, in the reference encoding (12 floats per node, root 1)
+    dump("accelRef", "f4", h.accelRef.data(), h.accelRef.size(), 4);
   }
   return std::fclose(g_out) == 0 ? 0 : 2;
 }

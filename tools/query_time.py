@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import os
 import sys
 import time
 from pathlib import Path
@@ -57,6 +58,9 @@ def main():
 
     import ao
     from opengl_ray_tracing_amd import Renderer, orbit_camera, scenes
+    if os.environ.get("PT_VARIANT"):  # an in-tree build variant (a parent commit's library beside this tree's)
+        from opengl_ray_tracing_amd import _native
+        _native.use_variant(os.environ["PT_VARIANT"])
     if not torch.cuda.is_available():
         raise RuntimeError("query_time: no GPU visible")
     stream = torch.cuda.Stream()
