@@ -17,6 +17,15 @@ def bits(a):
     return np.ascontiguousarray(a, F).view(np.uint32)
 
 
+def same(a, b):
+    """Elementwise: equal bits, or both NaN (fmath_sets.same_bits_or_nan: a NaN's sign and payload
+    differ between an x86 host and the GPU). Infinities, signed zeros and denormals compare by bits."""
+    from fmath_sets import same_bits_or_nan
+    a, b = np.ascontiguousarray(a, F), np.ascontiguousarray(b, F)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    return same_bits_or_nan(a, b)
+
+
 @functools.lru_cache(maxsize=None)
 def config(name):
     cfg, tris, nodes, hdr = scenes.build_config(name)
